@@ -31,6 +31,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import socket
 import subprocess
@@ -50,6 +51,9 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_PEAK_TF = {"f32": 157.3, "f64": 46.0}
 MFMA_DATASHEET_TF = {"f32": 157.3, "f64": 78.6}
 MFMA_MEASURED_TF = {"f32": 152.7, "f64": 46.0}
+# --preheat-ms as a step count: the headline rate (n = 10 003, f32, look-ahead windows)
+HEADLINE_N = 10003
+PREHEAT_STEPS_PER_MS = 13.75
 
 
 def parse_args():
@@ -64,10 +68,12 @@ def parse_args():
                          "(tools/drift_probe.py; f64 N=1000: warm-up 20/400/1000 + 1000 steps -> 80 / 123 / 68.7 us per "
                          "step).  A long warm-up gets that one-time event out of the way")
     ap.add_argument("--preheat-ms", type=float, default=400.0,
-                    help="ekf: when --warmup is short (< 400 steps), the same step loop is first run untimed for this long "
-                         "so that the W warm-up + K timed steps meet a GPU at its working clocks (a cold MI355X runs the "
-                         "first milliseconds ~12 %% slower: 20 steps after 5 measured 8 830 steps/s against 9 950 in a long "
-                         "run); the step count is reported as preheat_steps.  0 disables")
+                    help="ekf: when --warmup is short (< 400 steps), the same step loop is first run untimed for about this "
+                         "long, so that the W warm-up + K timed steps meet a GPU at its working clocks (a cold MI355X runs "
+                         "the first milliseconds ~12 %% slower: 20 steps after 5 measured 8 830 steps/s against 9 950 in a "
+                         "long run).  The preheat is a step count fixed by the arguments (this long at the headline rate, "
+                         "scaled by n^2, at most 8000), so that every run starts the timed steps from the same state; it "
+                         "is reported as preheat_steps.  0 disables")
     ap.add_argument("--landmarks", type=int, default=None, help="default 5000 (ekf) / 2000 (mc)")
     ap.add_argument("--obs", type=int, default=32, help="observations per batch update (k = 2*obs)")
     ap.add_argument("--dtype", choices=["f32", "f64"], default="f32")
@@ -97,6 +103,13 @@ def parse_args():
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a box with ONE GPU: every rank uses device 0 and the ranks rendezvous "
                          "over gloo (RCCL refuses one device twice); exercises the launcher / rank logic, not xGMI")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (rank 0's filter "
+                         "state) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: a covariance as its diagonal, "
+                         "its pose columns and a fixed, seeded sample of its entries (all of them up to 2^21).  The inputs "
+                         "depend on the arguments only, so two builds can be compared output for output (bench_outputs/ "
+                         "is git-ignored for this).  The timed steps are unaffected; the sub-records measured after them "
+                         "follow the read-back, which leaves the GPU idle for a moment")
     return ap.parse_args()
 
 
@@ -332,6 +345,58 @@ def quantiles_ms(ts):
             "p90_ms": float(a[int(0.9 * (len(a) - 1))]), "calls": int(len(a))}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT_BYTES = 64 << 20
+P_SAMPLE_ENTRIES = 1 << 21  # covariance entries kept per dump (P is 400 MB at the headline size)
+DUMP_SEED = 2024
+
+
+def p_sample_index(n, count):
+    """Column-major flat indices of a fixed, seeded sample of an n x n covariance: every P of size n in full when it has
+    at most `count` entries."""
+    if n * n <= count:
+        return np.arange(n * n)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n * n, size=count))
+
+
+def filter_outputs(X, P, idx):
+    """What a caller of predict() / update() receives: X, and P as its diagonal, its three pose columns (the pose-landmark
+    cross-covariances) and its entries at the flat column-major indices idx."""
+    return {"X": X, "P_diag": np.diagonal(P).copy(), "P_pose": np.ascontiguousarray(P[:, :3]),
+            "P_sample": P.reshape(-1, order="F")[idx]}
+
+
+def filters_outputs(get_states, n):
+    """filter_outputs of several filters (one `get_state` callable each), stacked along a leading instance axis; the
+    covariance sample is shared out between them."""
+    idx = p_sample_index(n, P_SAMPLE_ENTRIES // len(get_states))
+    outs = [filter_outputs(*get(), idx) for get in get_states]
+    return {k: np.stack([o[k] for o in outs]) for k in outs[0]}
+
+
+def particle_outputs(sh):
+    """Every particle of the shard (weight, pose, pose covariance, feature means, feature covariances), or a fixed, seeded
+    sample of the particles when all of them would pass the size limit."""
+    per = (13 + 6 * sh.n_features) * sh.dtype.itemsize
+    keep = np.arange(sh.n_local)
+    if sh.n_local * per > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(sh.n_local, DUMP_LIMIT_BYTES // per, replace=False))
+    parts = [sh.get_particle(int(i)) for i in keep]
+    names = ("weights", "pose", "pose_cov", "features", "feature_cov")
+    return {name: np.stack([np.asarray(p[j], dtype=sh.dtype) for p in parts]) for j, name in enumerate(names)}
+
+
+def dump_outputs(dirname, arrays):
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise SystemExit(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ EKF headline
 def ekf_main(args):
     rank, local_rank, world, torch, dist = dist_setup(args)
@@ -392,15 +457,14 @@ def ekf_main(args):
         eng.flush()
         eng.synchronize()
         cold_rate = args.steps / (time.perf_counter() - c0)
-        preheat_steps = n_cold
     if pre_cap:
-        t_end = time.perf_counter() + args.preheat_ms * 1e-3
-        while preheat_steps < pre_cap and time.perf_counter() < t_end:
-            for t in range(preheat_steps, min(pre_cap, preheat_steps + 100)):
+        # a number of steps fixed by the arguments, not a wall-clock time: the state the timed steps start from must be the
+        # same on every run (--dump-outputs).  --preheat-ms at the headline rate, scaled by the n^2 cost of a step
+        preheat_steps = min(pre_cap - n_cold, math.ceil(args.preheat_ms * PREHEAT_STEPS_PER_MS * (HEADLINE_N / n) ** 2))
+        for t0 in range(n_cold, n_cold + preheat_steps, 100):
+            for t in range(t0, min(n_cold + preheat_steps, t0 + 100)):
                 step(t)
-            preheat_steps = min(pre_cap, preheat_steps + 100)
             eng.synchronize()
-        preheat_steps -= n_cold
     for t in range(pre_cap, pre_cap + args.warmup):
         step(t)
     eng.flush()  # (the timed region starts from an applied state: the warm-up's pending P-GEMM is not billed to it,
@@ -423,6 +487,10 @@ def ekf_main(args):
     stages = eng.stage_times()
     eng.set_profiling(0)
     flags = eng.factor_status()
+    if args.dump_outputs and rank == 0:
+        X, P = eng.get_state()
+        dump_outputs(args.dump_outputs, filter_outputs(X, P, p_sample_index(n, P_SAMPLE_ENTRIES)))
+        del X, P
 
     if rank != 0:
         eng.close()
@@ -785,6 +853,8 @@ def mc_main(args):
     for e in engs:
         e.set_profiling(0)
     flags = [e.factor_status() for e in engs]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, filters_outputs([e.get_state for e in engs], n))
     if rank != 0:
         for e in engs:
             e.close()
@@ -894,6 +964,8 @@ def mc_batched(args, rank, local_rank, world, torch, dist, N, m, I, quirks):
         dd_ms, dd_cnt = dd_ms + ms_, dd_cnt + c_
         b.set_profiling(0)
         flags += b.factor_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, filters_outputs([lambda i=i: bs[i // per].get_state(i % per) for i in range(I)], n))
     if rank != 0:
         for b in bs:
             b.close()
@@ -1082,6 +1154,8 @@ def pf_main(args):
     elapsed = max_over_ranks(torch, dist, elapsed)
     if world == 1:
         n_resampled = sh.resample_stats()[1] - r0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, particle_outputs(sh))
     ws = sh.get_weights()
     if rank == 0:
         rec_bytes = (13 + 6 * Nf) * 4
