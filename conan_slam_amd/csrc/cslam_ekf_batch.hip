@@ -12,6 +12,11 @@
 // filter's (the same *_body functions), so an instance's results are BITWISE those of a solo engine running look-ahead
 // windows of the same pairs of updates (tests/test_batch_gpu.py).
 //
+// The reference's whole loop (predict + observeHeading per control step, update + augment per observation step) runs
+// through cslam_ekf_batch_predict / observe_heading / update / augment: a batched pose queue (ekf_pose_step_batch_kernel),
+// windows of one update, a batched augment (ekf_augment_batch_kernel) and a map that grows up to the handle's capacity
+// ("The reference's loop through the batch").
+//
 // State lives in slabs with a fixed stride per instance: X [I][ldp], Pv [I][3 ldp], P [I][ldp ldp] (block-lower), the
 // pending store W [2 regions][I][128][ldp] (P = Ps - Wp Wp^T, Wp = the previous window's panels), factor slots, the
 // look-ahead scratch and the wait counters (labatch:: layout in ekf_lookahead.hpp).
@@ -88,9 +93,20 @@ struct cslam_ekf_batch
     int           tab_gen = 0;
     hipEvent_t    ev_gen[2]   = {nullptr, nullptr}; // the last kernel that reads generation g has finished
     bool          gen_used[2] = {false, false};
-    int2*         dTiles  = nullptr;
-    int*          dTicket = nullptr;
-    int           n_tiles = 0, parity = 0;
+    // P-GEMM tile lists, one per row-tile count T (the map grows): list T is the union of the instances' lower-triangular
+    // tiles (ti, tj) with ti < T, instance-major, at dTiles + tile_off[T].  All are built at create time and never
+    // change, so a P-GEMM still in flight keeps reading the list it was launched with when n crosses a 128-row boundary.
+    int2*            dTiles  = nullptr;
+    int*             dTicket = nullptr;
+    std::vector<int> tile_off, tile_cnt;
+    int              parity = 0;
+    int              ncap   = 0; // n at max_landmarks
+    // the calls of the reference's loop (cslam_ekf_batch_predict / observe_heading / update / augment): as the single
+    // handle's queueing model (cslam_ekf.hip, "predict / heading"), one state for all instances
+    PredictArgs<float> pp{0, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0}; // the held predict
+    PoseSeq<float>     pseq{};                                          // queued control steps
+    float*             dHead     = nullptr; // [I][ldp]: the column of heading steps without a map (n = 3)
+    int*               dPoseDone = nullptr; // [I]: ticket counters of ekf_pose_step_batch_kernel
     int           wcur = 0, kp = 0; // pending region and its columns
     unsigned      target = 0, seq = 0;
     long long     windows = 0;
@@ -147,6 +163,8 @@ struct cslam_ekf_batch
         (void)hipFree(dZtab);
         (void)hipFree(dIdftab);
         (void)hipFree(dTiles);
+        (void)hipFree(dHead);
+        (void)hipFree(dPoseDone);
         (void)hipFree(dTicket);
         (void)hipFree(dStamps);
         for (auto& e : prof_ev)
@@ -225,6 +243,9 @@ struct cslam_ekf_batch
         CSLAM_HIP_TRY(hipMalloc(&dZtab, (size_t)2 * I * sizeof(float*)));
         CSLAM_HIP_TRY(hipMalloc(&dIdftab, (size_t)2 * I * sizeof(int*)));
         CSLAM_HIP_TRY(hipMalloc(&dTicket, 2 * sizeof(int)));
+        CSLAM_HIP_TRY(hipMalloc(&dHead, I * L * sizeof(float)));
+        CSLAM_HIP_TRY(hipMalloc(&dPoseDone, (size_t)I * sizeof(int)));
+        CSLAM_HIP_TRY(hipMemset(dPoseDone, 0, (size_t)I * sizeof(int)));
         CSLAM_HIP_TRY(hipMemset(dX, 0, I * L * sizeof(float)));
         CSLAM_HIP_TRY(hipMemset(dPv, 0, I * 3 * L * sizeof(float)));
         CSLAM_HIP_TRY(hipMemset(dP, 0, I * L * L * sizeof(float)));
@@ -235,24 +256,27 @@ struct cslam_ekf_batch
         CSLAM_HIP_TRY(hipMemset(dDone, 0, (size_t)I * labatch::kDoneBlock * sizeof(unsigned)));
         CSLAM_HIP_TRY(hipMemset(dFlags, 0, (size_t)I * 2 * sizeof(int)));
         CSLAM_HIP_TRY(hipMemset(dTicket, 0, 2 * sizeof(int)));
-        // the union of the instances' lower-triangular tiles, instance-major; x = row tile | instance << 16
+        // the union of the instances' lower-triangular tiles, instance-major; x = row tile | instance << 16.  Tiles of
+        // pure padding rows never change: list T holds the row tiles ti < T, for every T from today's n to capacity.
         const int         tiles = ldp / kTile;
         std::vector<int2> h;
-        h.reserve((size_t)I * tiles * (tiles + 1) / 2);
-        for (int i = 0; i < I; i++)
+        tile_off.assign((size_t)tiles + 1, 0);
+        tile_cnt.assign((size_t)tiles + 1, 0);
+        for (int T = std::max(1, row_tiles()); T <= tiles; T++)
         {
-            for (int tj = 0; tj < tiles; tj++)
+            tile_off[T] = (int)h.size();
+            for (int i = 0; i < I; i++)
             {
-                for (int ti = tj; ti < tiles; ti++)
+                for (int tj = 0; tj < tiles; tj++)
                 {
-                    if (ti * kTile < n) // (tiles of pure padding rows never change)
+                    for (int ti = tj; ti < T; ti++)
                     {
                         h.push_back(make_int2(ti | (i << 16), tj));
                     }
                 }
             }
+            tile_cnt[T] = (int)h.size() - tile_off[T];
         }
-        n_tiles = (int)h.size();
         CSLAM_HIP_TRY(hipMalloc(&dTiles, h.size() * sizeof(int2)));
         CSLAM_HIP_TRY(hipMemcpy(dTiles, h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_batch<32>),
@@ -261,6 +285,8 @@ struct cslam_ekf_batch
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds(64)));
         return CSLAM_OK;
     }
+
+    int row_tiles() const { return (n + kTile - 1) / kTile; }
 
     int sync()
     {
@@ -290,7 +316,10 @@ struct cslam_ekf_batch
             CSLAM_HIP_TRY(hipMemset2DAsync(W + (size_t)kp * ldp, sW() * sizeof(float), 0, (size_t)(cover - kp) * ldp * sizeof(float),
                                            (size_t)I, stream));
         }
-        const int      G      = std::min(n_tiles, 2 * (num_cus - I));
+        const int      T       = std::max(1, row_tiles());
+        const int2*    tl      = dTiles + tile_off[T];
+        const int      n_tiles = tile_cnt[T];
+        const int      G       = std::min(n_tiles, 2 * (num_cus - I));
         const unsigned sPb    = (unsigned)((size_t)ldp * ldp * 4);
         const unsigned sWb    = (unsigned)(sW() * 4);
         const unsigned p_span = (unsigned)((size_t)I * ldp * ldp * 4);
@@ -303,7 +332,7 @@ struct cslam_ekf_batch
         }
 #define CSLAM_LAUNCH_PSYM4B(NCH, KC)                                                                                  \
     hipLaunchKernelGGL((ekf_downdate_psym4_f32<0, NCH, KC, false, true>), dim3(G), dim3(256), 0, stream, dP, ldp, W, ldp, \
-                       kp, (const int2*)dTiles, n_tiles, dTicket + parity, dTicket + (parity ^ 1),                  \
+                       kp, tl, n_tiles, dTicket + parity, dTicket + (parity ^ 1),                  \
                        (unsigned long long*)nullptr, (const int*)nullptr, sPb, sWb, p_span, w_span,                   \
                        sig_add ? dDone : (unsigned*)nullptr, sig_add, I, (int)labatch::kDoneBlock)
         if (k8 <= 64)
@@ -328,6 +357,93 @@ struct cslam_ekf_batch
         kp = 0;
         return CSLAM_OK;
     }
+
+    // ---------------------------------------------------------------- predict / heading queue
+    // A held predict followed by an update rides inside that update's window (pp_a); observe_heading joins it into ONE
+    // step of the pose queue; up to kPoseSeqMax steps run as one ekf_pose_step_batch_kernel launch for all instances.
+    // Every heading step appends one pending column (the rank-1 downdate -p p^T / S of the map block) to the current
+    // region; rows 0..2 and [n, n_pad) of that column are written as zeros, which keeps the invariant every pending
+    // column has: its rows >= n are zero (the wide kernel's panels get theirs from the zero rows of Ps), so a feature
+    // appended by augment() starts with nothing pending.
+    int queue_step(const PredictArgs<float>& p, const HeadingArgs<float>& hd)
+    {
+        int rc = CSLAM_OK;
+        if (pseq.count == kPoseSeqMax && (rc = launch_pose_queue()))
+        {
+            return rc;
+        }
+        int col = -1;
+        if (hd.valid && n > 3)
+        {
+            if (kp + 1 > kWcols && ((rc = launch_pose_queue()) || (rc = flush())))
+            {
+                return rc;
+            }
+            col = kp;
+            kp += 1;
+        }
+        const int s = pseq.count++;
+        pseq.pp[s]  = p;
+        pseq.hd[s]  = hd;
+        pseq.col[s] = col;
+        return CSLAM_OK;
+    }
+
+    int launch_pose_queue()
+    {
+        if (pseq.count == 0)
+        {
+            return CSLAM_OK;
+        }
+        const int n_pad = round_up(n, kTile);
+        hipLaunchKernelGGL(ekf_pose_step_batch_kernel<float>, dim3((n_pad + 255) / 256, I), dim3(256), 0, stream, dX, dPv, ldp,
+                           n, n_pad, pseq, wregion(wcur), (long)sW(), dHead, dPoseDone, dFlags);
+        CSLAM_HIP_TRY(hipGetLastError());
+        pseq.count = 0;
+        return CSLAM_OK;
+    }
+
+    // everything the calls of the reference's loop left queued (a held predict becomes a predict-only step) is launched;
+    // nothing to do for a handle that never used them
+    int drain()
+    {
+        int rc = CSLAM_OK;
+        if (pp.valid)
+        {
+            if ((rc = queue_step(pp, HeadingArgs<float>{0, 0.f, 0.f})))
+            {
+                return rc;
+            }
+            pp.valid = 0;
+        }
+        return launch_pose_queue();
+    }
+
+    // The per-instance input pointers of a call go into the table generation the previous call does not use, with a
+    // BLOCKING copy: the chain kernels read them on stream F, which is not ordered behind copies on the main stream.  The
+    // generation was last used two calls ago: wait for that call's last kernel (the call in between stays in flight).
+    int stage_inputs(const float* const* dZ, const int* const* d_idf, int* gen)
+    {
+        tab_gen ^= 1;
+        const int g = tab_gen;
+        if (gen_used[g])
+        {
+            CSLAM_HIP_TRY(hipEventSynchronize(ev_gen[g]));
+        }
+        CSLAM_HIP_TRY(hipMemcpy(dZtab + (size_t)g * I, dZ, (size_t)I * sizeof(float*), hipMemcpyHostToDevice));
+        CSLAM_HIP_TRY(hipMemcpy(dIdftab + (size_t)g * I, d_idf, (size_t)I * sizeof(int*), hipMemcpyHostToDevice));
+        *gen = g;
+        return CSLAM_OK;
+    }
+
+    int inputs_done(int g)
+    {
+        CSLAM_HIP_TRY(hipEventRecord(ev_gen[g], stream)); // (the chains of a window finish before its wide kernel does)
+        gen_used[g] = true;
+        return CSLAM_OK;
+    }
+
+    int predict_width() const { return std::max((quirks & CSLAM_Q_PREDICT_NM4) ? (n - 4) : (n - 3), 0); }
 
     // one window: updates a (and b when nu == 2) of every instance, with their held predicts
     int window(const LaBatchWin& w0)
@@ -447,7 +563,14 @@ extern "C" {
 
 int cslam_ekf_batch_create(int instances, int n_landmarks, int device, int quirks, cslam_ekf_batch_t* out)
 {
-    if (!out || instances < 1 || instances > 255 || n_landmarks < 1 || (quirks & ~CSLAM_Q_REF_EXACT))
+    return cslam_ekf_batch_create_capacity(instances, n_landmarks, n_landmarks, device, quirks, out);
+}
+
+int cslam_ekf_batch_create_capacity(int instances, int max_landmarks, int n_landmarks, int device, int quirks,
+                                    cslam_ekf_batch_t* out)
+{
+    if (!out || instances < 1 || instances > 255 || max_landmarks < 1 || n_landmarks < 0 || n_landmarks > max_landmarks ||
+        (quirks & ~CSLAM_Q_REF_EXACT))
     {
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_create: bad arguments");
     }
@@ -465,14 +588,14 @@ int cslam_ekf_batch_create(int instances, int n_landmarks, int device, int quirk
     {
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_create: device %d of %d", device, c);
     }
-    const int    n   = 3 + 2 * n_landmarks;
-    const int    ldp = round_up(n, kTile);
-    const size_t pb  = (size_t)instances * ldp * ldp * 4;
+    const int    ncap = 3 + 2 * max_landmarks;
+    const int    ldp  = round_up(ncap, kTile);
+    const size_t pb   = (size_t)instances * ldp * ldp * 4;
     if (pb >= ((size_t)1 << 32))
     {
         // (the P-GEMM addresses the slab through one buffer resource with 32-bit offsets)
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_create: %d instances x %d landmarks exceed the 4 GiB covariance slab", instances,
-                    n_landmarks);
+                    max_landmarks);
     }
     cslam_ekf_batch* b = new (std::nothrow) cslam_ekf_batch();
     if (!b)
@@ -481,7 +604,8 @@ int cslam_ekf_batch_create(int instances, int n_landmarks, int device, int quirk
     }
     b->device = device;
     b->I      = instances;
-    b->n      = n;
+    b->n      = 3 + 2 * n_landmarks;
+    b->ncap   = ncap;
     b->ldp    = ldp;
     b->quirks = quirks;
     int rc    = b->init();
@@ -515,7 +639,7 @@ int cslam_ekf_batch_set_state(cslam_ekf_batch_t h, int instance, const float* X,
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_set_state: bad arguments (instance %d, n %d)", instance, n);
     }
     int rc = h->use_device();
-    if (rc || (rc = h->sync()))
+    if (rc || (rc = h->drain()) || (rc = h->sync()))
     {
         return rc;
     }
@@ -544,7 +668,11 @@ int cslam_ekf_batch_flush(cslam_ekf_batch_t h)
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_flush: null handle");
     }
     int rc = h->use_device();
-    return rc ? rc : h->flush();
+    if (rc || (rc = h->drain()))
+    {
+        return rc;
+    }
+    return h->flush();
 }
 
 int cslam_ekf_batch_synchronize(cslam_ekf_batch_t h)
@@ -554,7 +682,11 @@ int cslam_ekf_batch_synchronize(cslam_ekf_batch_t h)
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_synchronize: null handle");
     }
     int rc = h->use_device();
-    return rc ? rc : h->sync();
+    if (rc || (rc = h->drain()))
+    {
+        return rc;
+    }
+    return h->sync();
 }
 
 int cslam_ekf_batch_get_state(cslam_ekf_batch_t h, int instance, float* X, float* P, int ldp)
@@ -564,7 +696,7 @@ int cslam_ekf_batch_get_state(cslam_ekf_batch_t h, int instance, float* X, float
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_get_state: bad arguments (instance %d)", instance);
     }
     int rc = h->use_device();
-    if (rc || (P && (rc = h->flush())))
+    if (rc || (rc = h->drain()) || (P && (rc = h->flush())))
     {
         return rc;
     }
@@ -596,7 +728,7 @@ int cslam_ekf_batch_trace(cslam_ekf_batch_t h, double* traces)
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_trace: bad arguments");
     }
     int rc = h->use_device();
-    if (rc || (rc = h->flush()))
+    if (rc || (rc = h->drain()) || (rc = h->flush()))
     {
         return rc;
     }
@@ -627,7 +759,7 @@ int cslam_ekf_batch_factor_status(cslam_ekf_batch_t h, int* flags)
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_factor_status: bad arguments");
     }
     int rc = h->use_device();
-    if (rc || (rc = h->sync()))
+    if (rc || (rc = h->drain()) || (rc = h->sync()))
     {
         return rc;
     }
@@ -667,22 +799,16 @@ int cslam_ekf_batch_run(cslam_ekf_batch_t h, int steps, const double* v, const d
     {
         return rc;
     }
-    // The per-instance input pointers of this call go into the table generation the previous call does not use, with a
-    // BLOCKING copy: the chain kernels read them on stream F, which is not ordered behind copies on the main stream.  The
-    // generation was last used two calls ago: wait for that call's last kernel (the call in between stays in flight).
-    h->tab_gen ^= 1;
-    const int     g  = h->tab_gen;
+    int g = 0;
+    if ((rc = h->drain()) || (rc = h->stage_inputs(dZ, d_idf, &g)))
+    {
+        return rc;
+    }
     const float** zt = h->dZtab + (size_t)g * h->I;
     const int**   it = h->dIdftab + (size_t)g * h->I;
-    if (h->gen_used[g])
-    {
-        CSLAM_HIP_TRY(hipEventSynchronize(h->ev_gen[g]));
-    }
-    CSLAM_HIP_TRY(hipMemcpy(zt, dZ, (size_t)h->I * sizeof(float*), hipMemcpyHostToDevice));
-    CSLAM_HIP_TRY(hipMemcpy(it, d_idf, (size_t)h->I * sizeof(int*), hipMemcpyHostToDevice));
-    const int pw = (h->quirks & CSLAM_Q_PREDICT_NM4) ? (h->n - 4) : (h->n - 3);
-    auto      pp = [&](int t) {
-        return PredictArgs<float>{1, (float)v[t], (float)swa[t], Q[0], Q[1], Q[2], Q[3], (float)wb, (float)dt, std::max(pw, 0)};
+    const int     pw = h->predict_width();
+    auto          pp = [&](int t) {
+        return PredictArgs<float>{1, (float)v[t], (float)swa[t], Q[0], Q[1], Q[2], Q[3], (float)wb, (float)dt, pw};
     };
     for (int t = 0; t < steps; t += 2)
     {
@@ -708,9 +834,7 @@ int cslam_ekf_batch_run(cslam_ekf_batch_t h, int steps, const double* v, const d
             return rc;
         }
     }
-    CSLAM_HIP_TRY(hipEventRecord(h->ev_gen[g], h->stream)); // (the chains of a window finish before its wide kernel does)
-    h->gen_used[g] = true;
-    return CSLAM_OK;
+    return h->inputs_done(g);
 }
 
 int cslam_ekf_batch_set_profiling(cslam_ekf_batch_t h, int every)
@@ -777,6 +901,148 @@ int cslam_ekf_batch_info(cslam_ekf_batch_t h, int* instances, int* n, long long*
     if (windows)
     {
         *windows = h->windows;
+    }
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_predict(cslam_ekf_batch_t h, double v, double swa, const float* Q, double wb, double dt)
+{
+    if (!h || !Q)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_predict: bad arguments");
+    }
+    int rc = h->use_device();
+    if (rc)
+    {
+        return rc;
+    }
+    if (h->pp.valid && (rc = h->queue_step(h->pp, HeadingArgs<float>{0, 0.f, 0.f}))) // two predicts in a row
+    {
+        return rc;
+    }
+    h->pp = PredictArgs<float>{1, (float)v, (float)swa, Q[0], Q[1], Q[2], Q[3], (float)wb, (float)dt, h->predict_width()};
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_observe_heading(cslam_ekf_batch_t h, double phi, int use_heading)
+{
+    if (!h)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_observe_heading: null handle");
+    }
+    if (!use_heading)
+    {
+        return CSLAM_OK; // EKF.cpp:332-335 (a held predict stays held)
+    }
+    int rc = h->use_device();
+    if (rc)
+    {
+        return rc;
+    }
+    // float sigmaPhi = 0.01F * pi / 180.0F; R = pow(sigmaPhi, 2) -- as the single handle
+    const float              sigma = (float)(((double)0.01f * kPi) / 180.0);
+    const PredictArgs<float> p     = h->pp;
+    if ((rc = h->queue_step(p, HeadingArgs<float>{1, (float)phi, sigma * sigma})))
+    {
+        return rc;
+    }
+    h->pp.valid = 0;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_update(cslam_ekf_batch_t h, const float* const* dZ, const int* const* d_idf, int m, const float* R)
+{
+    if (!h || m < 0 || (m > 0 && (!dZ || !d_idf || !R)))
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update: bad arguments");
+    }
+    if (m == 0)
+    {
+        return CSLAM_OK;
+    }
+    if (2 * m <= 16 || m > kLaMaxObs)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update: m=%d outside the batched engine's 9..%d observations per update", m,
+                    kLaMaxObs);
+    }
+    if ((h->n - 3) / 2 < 1)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update: the map is empty");
+    }
+    for (int i = 0; i < h->I; i++)
+    {
+        if (!dZ[i] || !d_idf[i])
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update: instance %d has no inputs", i);
+        }
+    }
+    int rc = h->use_device();
+    int g  = 0;
+    if (rc || (rc = h->launch_pose_queue()) || (rc = h->stage_inputs(dZ, d_idf, &g)))
+    {
+        return rc;
+    }
+    // one window of ONE update at once (pairing updates across calls would hold the caller's buffers); the held predict,
+    // if any, rides inside it
+    LaBatchWin w;
+    memset(&w, 0, sizeof(w));
+    w.nu     = 1;
+    w.ma     = m;
+    w.mb     = m;
+    w.Ztab   = h->dZtab + (size_t)g * h->I;
+    w.idftab = h->dIdftab + (size_t)g * h->I;
+    w.pp_a   = h->pp;
+    w.pp_b   = h->pp;
+    for (int e = 0; e < 4; e++)
+    {
+        w.R[e] = R[e];
+    }
+    h->pp.valid = 0;
+    if ((rc = h->window(w)))
+    {
+        return rc;
+    }
+    return h->inputs_done(g);
+}
+
+int cslam_ekf_batch_augment(cslam_ekf_batch_t h, const float* const* dZn, int q, const float* R)
+{
+    if (!h || q < 0 || (q > 0 && (!dZn || !R)))
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_augment: bad arguments (q=%d)", q);
+    }
+    if (q == 0)
+    {
+        return CSLAM_OK;
+    }
+    if (h->n + 2 * q > h->ncap)
+    {
+        return fail(CSLAM_ERR_CAPACITY, "ekf_batch_augment: %d features would exceed max_landmarks=%d", (h->n - 3) / 2 + q,
+                    (h->ncap - 3) / 2);
+    }
+    AugBatchArgs za;
+    for (int i = 0; i < h->I; i++)
+    {
+        if (!dZn[i])
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_augment: instance %d has no inputs", i);
+        }
+        za.z[i] = dZn[i];
+    }
+    int rc = h->use_device();
+    if (rc || (rc = h->drain())) // (the new rows are built from the pose and the stripe: they must be current)
+    {
+        return rc;
+    }
+    // Everything is on the main stream: the P-GEMM that may sweep Ps has run by the time the new rows are written, and the
+    // pending panels have zero rows for the new features (see queue_step), so the kernel writes values of the true P.
+    for (int f = 0; f < q; f++)
+    {
+        za.f = f;
+        hipLaunchKernelGGL(ekf_augment_batch_kernel<float>, dim3((h->n + 255) / 256, h->I), dim3(256), 0, h->stream, h->dX, h->dP,
+                           h->dPv, h->ldp, h->n, za, R[0], R[1], R[2], R[3]);
+        CSLAM_HIP_TRY(hipGetLastError());
+        h->n += 2;
     }
     return CSLAM_OK;
 }

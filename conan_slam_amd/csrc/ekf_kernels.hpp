@@ -27,6 +27,7 @@ namespace cslam
 constexpr int kFlagLltFailed = 1; // device-side factor flags
 constexpr int kFlagZeroed    = 2;
 constexpr int kFlagBadIdf    = 8; // a feature index outside 1..(n-3)/2 reached the device (cslam_ekf_update_device)
+constexpr int kFlagHeadingSkipped = 32; // the batched engine skipped a heading step with S <= 0 (ekf_pose_step_body)
 
 // Feature indices that arrive through device memory cannot be checked by the host: every kernel clamps them into
 // 1..(n-3)/2 before it forms an address (no out-of-bounds access whatever the caller sends) and the gather kernel

@@ -54,11 +54,16 @@ struct PoseSeq
 // n_pad entries written per heading column, zeros in rows 0..2 and [n, n_pad)); scratch: a column for heading steps
 // without a map (col < 0).  sgn / neg_count: see below.  done: ticket counter (reset by the last workgroup, which is
 // also the one that rewrites the 3 x 3 pose block and the pose -- everybody else has consumed the old values by then).
-template <typename T>
-__global__ void __launch_bounds__(256) ekf_pose_step_kernel(T* __restrict__ X, T* __restrict__ Pv, int ldp, int n,
-                                                             int n_pad, PoseSeq<T> seq, T* __restrict__ wbase, int ldw,
-                                                             T* __restrict__ scratch, int* __restrict__ sgn,
-                                                             int* __restrict__ neg_count, int* __restrict__ done)
+//
+// SKIP (the batched engine, whose pending panels carry no sign words): a heading step with S = P22 + R <= 0 or
+// non-finite is skipped -- X, the stripe and the pose block stay as they are, its column is written as zeros -- and
+// kFlagHeadingSkipped is raised in *flags; sgn / neg_count are not used.  A predict in the same step still applies.
+template <typename T, bool SKIP>
+__device__ __forceinline__ void ekf_pose_step_body(T* __restrict__ X, T* __restrict__ Pv, int ldp, int n, int n_pad,
+                                                   PoseSeq<T> seq, T* __restrict__ wbase, int ldw,
+                                                   T* __restrict__ scratch, int* __restrict__ sgn,
+                                                   int* __restrict__ neg_count, int* __restrict__ done,
+                                                   int* __restrict__ flags)
 {
     // sgn / neg_count: the reference's Joseph form is finite for S = P22 + R < 0 too (an indefinite P, which
     // REF_EXACT's gain produces: SURVEY 2.1 #1/#3) and equals P - p p^T / S there as well, i.e. P + w w^T with
@@ -124,6 +129,19 @@ __global__ void __launch_bounds__(256) ekf_pose_step_kernel(T* __restrict__ X, T
             const T pcol[3] = {pvv[0 + 6], pvv[1 + 6], pvv[2 + 6]}; // P[r,2]
             const T prow[3] = {pvv[2 + 0], pvv[2 + 3], pvv[2 + 6]}; // P[2,c]
             const T S       = pcol[2] + hd.R;
+            if (SKIP && !(S > (T)0 && __builtin_isfinite(S)))
+            {
+                T* wcol = (seq.col[s] >= 0) ? wbase + (size_t)seq.col[s] * ldw : scratch;
+                if (i < n_pad)
+                {
+                    wcol[i] = (T)0; // (the column stays zero: nothing pending)
+                }
+                if (i == 0)
+                {
+                    atomicOr(flags, kFlagHeadingSkipped);
+                }
+                continue;
+            }
             const T si      = (T)1 / S;
             const T rs      = (T)1 / dsqrt(dabs(S));
             const T ros     = hd.R * si; // R/S = 1 - P22/S without the cancellation
@@ -179,7 +197,7 @@ __global__ void __launch_bounds__(256) ekf_pose_step_kernel(T* __restrict__ X, T
             {
                 pvv[e] = nv[e];
             }
-            if (seq.col[s] >= 0 && i == 0)
+            if (!SKIP && seq.col[s] >= 0 && i == 0)
             {
                 const int neg  = (S > (T)0) ? 0 : 1;
                 sgn[seq.col[s]] = neg; // (workgroup 0 only: nobody reads it before the kernel ends)
@@ -194,7 +212,7 @@ __global__ void __launch_bounds__(256) ekf_pose_step_kernel(T* __restrict__ X, T
         Pv[(size_t)2 * ldp + i] = a2;
         X[i]                    = xi;
     }
-    if (i == 0 && negs > 0)
+    if (!SKIP && i == 0 && negs > 0)
     {
         atomicAdd(neg_count, negs);
     }
@@ -217,6 +235,29 @@ __global__ void __launch_bounds__(256) ekf_pose_step_kernel(T* __restrict__ X, T
     X[0] = xo[0];
     X[1] = xo[1];
     X[2] = xo[2];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) ekf_pose_step_kernel(T* __restrict__ X, T* __restrict__ Pv, int ldp, int n,
+                                                             int n_pad, PoseSeq<T> seq, T* __restrict__ wbase, int ldw,
+                                                             T* __restrict__ scratch, int* __restrict__ sgn,
+                                                             int* __restrict__ neg_count, int* __restrict__ done)
+{
+    ekf_pose_step_body<T, false>(X, Pv, ldp, n, n_pad, seq, wbase, ldw, scratch, sgn, neg_count, done, nullptr);
+}
+
+// The batched engine's pose queue: grid = (ceil(n_pad/256), I), blockIdx.y the instance; slabs with a fixed stride per
+// instance (X [I][ldp], Pv [I][3 ldp], the pending region [I][sw], scratch [I][ldp], done [I], flags [I][2]).  The
+// steps (controls, heading, column indices) are common to the instances.
+template <typename T>
+__global__ void __launch_bounds__(256) ekf_pose_step_batch_kernel(T* __restrict__ X, T* __restrict__ Pv, int ldp, int n,
+                                                                   int n_pad, PoseSeq<T> seq, T* __restrict__ wbase,
+                                                                   long sw, T* __restrict__ scratch,
+                                                                   int* __restrict__ done, int* __restrict__ flags)
+{
+    const size_t i = blockIdx.y;
+    ekf_pose_step_body<T, true>(X + i * ldp, Pv + i * 3 * ldp, ldp, n, n_pad, seq, wbase + i * sw, ldp,
+                                scratch + i * ldp, nullptr, nullptr, done + i, flags + 2 * i);
 }
 
 // Pose-stripe downdate behind the gain kernel: Pv[:, c] -= sum_q W1[:, q] * W1[c, q], c = 0..2; then the LAST workgroup
@@ -370,9 +411,8 @@ __global__ void __launch_bounds__(256) ekf_negcol_fix_kernel(T* __restrict__ P, 
 // values written here are those of the true P.  grid = ceil(len/256) x 256 (nobody writes what another thread reads:
 // X[2] and rows < len of the stripe are only read, rows len, len+1 only written).
 template <typename T>
-__global__ void __launch_bounds__(256) ekf_augment_kernel(T* __restrict__ X, T* __restrict__ P, T* __restrict__ Pv,
-                                                           int ldp, int len, T r, T b, T r00, T r10, T r01, T r11,
-                                                           int lower)
+__device__ __forceinline__ void ekf_augment_body(T* __restrict__ X, T* __restrict__ P, T* __restrict__ Pv, int ldp,
+                                                 int len, T r, T b, T r00, T r10, T r01, T r11, int lower)
 {
     const T s = dsin(X[2] + b), c = dcos(X[2] + b);
     const T Gv[6] = {(T)1, (T)0, (T)0, (T)1, -r * s, r * c}; // 2x3 column-major
@@ -453,6 +493,34 @@ __global__ void __launch_bounds__(256) ekf_augment_kernel(T* __restrict__ X, T* 
             }
         }
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) ekf_augment_kernel(T* __restrict__ X, T* __restrict__ P, T* __restrict__ Pv,
+                                                           int ldp, int len, T r, T b, T r00, T r10, T r01, T r11,
+                                                           int lower)
+{
+    ekf_augment_body<T>(X, P, Pv, ldp, len, r, b, r00, r10, r01, r11, lower);
+}
+
+// The batched engine's augment of feature f of every instance: grid = (ceil(len/256), I), blockIdx.y the instance.
+// Instance i's observation (r, b) is read from ITS device array, z[i][2 f], [2 f + 1] (the inputs are read in stream
+// order); the slabs are block-lower with a fixed stride per instance.
+struct AugBatchArgs
+{
+    const float* z[256];
+    int          f;
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) ekf_augment_batch_kernel(T* __restrict__ X, T* __restrict__ P, T* __restrict__ Pv,
+                                                                 int ldp, int len, AugBatchArgs za, T r00, T r10, T r01,
+                                                                 T r11)
+{
+    const size_t i  = blockIdx.y;
+    const float* zi = za.z[i] + 2 * za.f;
+    ekf_augment_body<T>(X + i * ldp, P + i * ldp * ldp, Pv + i * 3 * ldp, ldp, len, (T)zi[0], (T)zi[1], r00, r10, r01, r11,
+                        1);
 }
 
 // rows / columns 0..2 of the P buffer <- Pv (before P is handed to the host); grid = ceil(n/256) x 256

@@ -222,15 +222,37 @@ class EKF:
 class EKFBatch:
     """`instances` independent f32 filters of `n_landmarks` landmarks each, advancing in lockstep (cslam_ekf_batch_*):
     the Monte-Carlo unit of BASELINE configs[4] (test/main.cpp:132-200 x I) with one launch per stage for all
-    instances."""
+    instances.
 
-    def __init__(self, instances: int, n_landmarks: int, device: int = -1, quirks: int = Q_REF_EXACT):
+    max_landmarks: capacity for augment_device (default: n_landmarks, a map of fixed size); n_landmarks defaults to
+    max_landmarks (0 = the reference driver's X = 0_3, P = 0_3x3).  The reference's loop runs through predict /
+    observe_heading / update_device / augment_device, one call per reference call for all instances."""
+
+    def __init__(self, instances: int, n_landmarks: int = None, device: int = -1, quirks: int = Q_REF_EXACT, *,
+                 max_landmarks: int = None):
+        if n_landmarks is None and max_landmarks is None:
+            raise ValueError("EKFBatch: give n_landmarks and / or max_landmarks")
+        if max_landmarks is None:
+            max_landmarks = n_landmarks
+        if n_landmarks is None:
+            n_landmarks = max_landmarks
         self._L = _capi.lib()
         self._h = C.c_void_p(None)
-        check(self._L.cslam_ekf_batch_create(C.c_int(instances), C.c_int(n_landmarks), C.c_int(device), C.c_int(quirks),
-                                             C.byref(self._h)))
-        self.instances, self.n_landmarks, self.n = instances, n_landmarks, 3 + 2 * n_landmarks
+        check(self._L.cslam_ekf_batch_create_capacity(C.c_int(instances), C.c_int(max_landmarks), C.c_int(n_landmarks),
+                                                      C.c_int(device), C.c_int(quirks), C.byref(self._h)))
+        self.instances, self.max_landmarks = instances, max_landmarks
         self.quirks = quirks
+
+    @property
+    def n(self) -> int:
+        """current state size 3 + 2 * landmarks (common to the instances; grows with augment_device)"""
+        n = C.c_int(0)
+        check(self._L.cslam_ekf_batch_info(self._h, None, C.byref(n), None))
+        return n.value
+
+    @property
+    def n_landmarks(self) -> int:
+        return (self.n - 3) // 2
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -276,6 +298,36 @@ class EKFBatch:
         check(self._L.cslam_ekf_batch_run(self._h, C.c_int(steps), v.ctypes.data_as(C.POINTER(C.c_double)),
                                           swa.ctypes.data_as(C.POINTER(C.c_double)), _vp(Q), C.c_double(wb), C.c_double(dt),
                                           zs, ids, C.c_int(m), _vp(R)))
+
+    def predict(self, v: float, swa: float, Q, wb: float, dt: float):
+        """Slam::predict on every instance (held until the next call that needs it, as a single handle's)."""
+        Q = np.asfortranarray(Q, dtype=np.float32)
+        check(self._L.cslam_ekf_batch_predict(self._h, C.c_double(v), C.c_double(swa), _vp(Q), C.c_double(wb),
+                                              C.c_double(dt)))
+
+    def observe_heading(self, phi: float, use: bool = True):
+        """Slam::observeHeading on every instance (phi common).  An instance with P22 + R <= 0 skips it and raises
+        FACTOR_HEADING_SKIPPED (see cslam_ekf_batch_observe_heading)."""
+        check(self._L.cslam_ekf_batch_observe_heading(self._h, C.c_double(phi), C.c_int(1 if use else 0)))
+
+    def update_device(self, dZ_ptrs, d_idf_ptrs, m: int, R):
+        """Slam::update(batch = true) on every instance: one device pointer per instance to its 2 x m float32
+        observations (column-major) and m int32 feature indices, read in stream order."""
+        if len(dZ_ptrs) != self.instances or len(d_idf_ptrs) != self.instances:
+            raise ValueError("update_device: not one input pointer per instance")
+        R = np.asfortranarray(R, dtype=np.float32)
+        zs = (C.c_void_p * self.instances)(*[int(p) for p in dZ_ptrs])
+        ids = (C.c_void_p * self.instances)(*[int(p) for p in d_idf_ptrs])
+        check(self._L.cslam_ekf_batch_update(self._h, zs, ids, C.c_int(m), _vp(R)))
+
+    def augment_device(self, dZn_ptrs, q: int, R):
+        """Slam::augment on every instance: one device pointer per instance to its 2 x q float32 new-feature
+        observations (column-major), read in stream order."""
+        if len(dZn_ptrs) != self.instances:
+            raise ValueError("augment_device: not one input pointer per instance")
+        R = np.asfortranarray(R, dtype=np.float32)
+        zs = (C.c_void_p * self.instances)(*[int(p) for p in dZn_ptrs])
+        check(self._L.cslam_ekf_batch_augment(self._h, zs, C.c_int(q), _vp(R)))
 
     def flush(self):
         check(self._L.cslam_ekf_batch_flush(self._h))

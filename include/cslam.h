@@ -48,6 +48,8 @@ extern "C" {
                                    that window are undefined) */
 #define CSLAM_FACTOR_BAD_IDF 8  /* cslam_ekf_update_device: a device-resident feature index was outside 1..N; the kernels
                                    clamped it (no out-of-bounds access), the update used the clamped index           */
+#define CSLAM_FACTOR_HEADING_SKIPPED 32 /* batched engine: a heading step met S = P22 + R <= 0 or non-finite (an
+                                          indefinite P) and was skipped for that instance (cslam_ekf_batch_observe_heading) */
 
 /* ---- precision ---- */
 #define CSLAM_F32 0 /* the reference's precision (Eigen::MatrixXf everywhere)                          */
@@ -164,7 +166,8 @@ int cslam_ekf_run_many(cslam_ekf_t* handles, int count, int steps, const double*
                        int batch);
 
 /* Batched Monte-Carlo engine (BASELINE configs[4], test/main.cpp:132-200 x I): `instances` INDEPENDENT f32 filters of the
- * same size (n = 3 + 2 * n_landmarks, fixed) advance in lockstep, every stage of the step ONE launch for all of them
+ * same size n = 3 + 2 * n_landmarks (common to the instances; it grows with cslam_ekf_batch_augment up to the capacity
+ * given at create time) advance in lockstep, every stage of the step ONE launch for all of them
  * (conan_slam_amd/csrc/cslam_ekf_batch.hip).  The arithmetic per instance is cslam_ekf_update's (batch form with the
  * predict held back and applied inside the update, look-ahead windows of two updates): an instance's results are bitwise
  * those of a single handle that runs the same pairs of updates as look-ahead windows.
@@ -192,6 +195,38 @@ int cslam_ekf_batch_info(cslam_ekf_batch_t h, int* instances, int* n, long long*
  * get: synchronises, sum of milliseconds and number of the launches timed since profiling was switched on. */
 int cslam_ekf_batch_set_profiling(cslam_ekf_batch_t h, int every);
 int cslam_ekf_batch_get_pgemm_time(cslam_ekf_batch_t h, double* ms_sum, int* launches);
+
+/* ---- the reference's filter loop through the batch (test/main.cpp:132-200: predict + observeHeading per control step,
+ *      update + augment per observation step), one call per reference call, every call one state for all instances.
+ * Calls are queued as in a single handle: predict is held; observe_heading joins it into one step of a pose queue (up to
+ * 8 steps per launch); update launches the queued steps, then one look-ahead window of ONE update with the held predict
+ * inside it; augment launches what is queued, then the new features.  run / flush / synchronize / get_state / trace /
+ * factor_status / set_state first launch whatever these calls left queued (a held predict becomes a predict-only step);
+ * for a handle that never used them that is nothing.  Device inputs are read in stream order: the arrays behind dZ /
+ * d_idf / dZn must stay unchanged until the work of the call has run (as for cslam_ekf_batch_run); the host arrays of
+ * pointers are consumed before the call returns.  Asynchronous: the calls return when the work has been enqueued. */
+/* Like cslam_ekf_batch_create, but sized for max_landmarks.  Every instance starts with n_landmarks landmarks
+ * (0 = the reference driver's X = 0_3, P = 0_3x3, test/main.cpp:107-108), and the map grows with
+ * cslam_ekf_batch_augment.  cslam_ekf_batch_create(I, N, ...) behaves exactly as create_capacity(I, N, N, ...).
+ * cslam_ekf_batch_info reports the current n; set_state requires n equal to it. */
+int cslam_ekf_batch_create_capacity(int instances, int max_landmarks, int n_landmarks, int device, int quirks,
+                                    cslam_ekf_batch_t* out);
+/* Slam::predict (slam.h:841-847, EKF.cpp:406-455) on every instance.  The controls are common to all instances, as in
+ * cslam_ekf_batch_run. */
+int cslam_ekf_batch_predict(cslam_ekf_batch_t h, double v, double swa, const float* Q, double wb, double dt);
+/* Slam::observeHeading (slam.h:788, EKF.cpp:328-352, josephUpdate slam.h:700-725) on every instance.  phi is common,
+ * as in the reference driver, which observes the true heading.  Deliberate difference from the single handle: an
+ * instance whose S = P22 + R is <= 0 or non-finite (an indefinite P; a healthy filter never has one) skips the heading
+ * half of the step -- a predict in the same step still applies, X and P are otherwise unchanged -- and raises
+ * CSLAM_FACTOR_HEADING_SKIPPED in its flag word (sticky).  The other instances are unaffected. */
+int cslam_ekf_batch_observe_heading(cslam_ekf_batch_t h, double phi, int use_heading);
+/* Slam::update(..., batch = true) (slam.h:938-943, EKF.cpp:93-129) on every instance.  dZ[i] / d_idf[i] are instance
+ * i's device-resident 2 x m observations and m feature indices; 9 <= m <= 32 (m = 0 is a no-op). */
+int cslam_ekf_batch_update(cslam_ekf_batch_t h, const float* const* dZ, const int* const* d_idf, int m, const float* R);
+/* Slam::augment (slam.h:190-191, EKF.cpp:9-91) on every instance.  dZn[i] holds instance i's 2 x q new-feature
+ * observations (device).  q is common to all instances, so n stays common.  CSLAM_ERR_CAPACITY beyond max_landmarks,
+ * with nothing changed. */
+int cslam_ekf_batch_augment(cslam_ekf_batch_t h, const float* const* dZn, int q, const float* R);
 
 /* Per-stage device times of update() measured with HIP events on the handle's streams.
  * on = 1 starts recording (events around every stage of every update), on = 2 brackets the covariance downdate
