@@ -95,6 +95,7 @@ struct EkfBase
     int         lookahead     = -1; // look-ahead windows (ekf_lookahead.hpp): -1 where they pay, env CSLAM_LOOKAHEAD=1 / 0 forces
     hipStream_t stream   = nullptr; // A: everything except the P-GEMM
     hipStream_t stream_b = nullptr; // B: the P-GEMM (== stream when not pipelined)
+    long long   la_windows = 0;     // look-ahead windows launched (cslam_ekf_lookahead_windows)
 
     virtual int init()                                                                        = 0;
     virtual int set_state(const void* X, int n, const void* P, int ldp)                        = 0;
@@ -711,8 +712,9 @@ struct Ekf : EkfBase
         return CSLAM_OK;
     }
 
-    // copies (Z, idf) of one call into a pinned slot and enqueues the H2D copy; returns device pointers
-    int stage_obs(const void* Z, const int* idf, int m, const T** dZ, const int** dIdf)
+    // copies (Z, idf) of one call into the next slot of the ring on the main stream; returns device pointers.  Host
+    // inputs go through the slot's pinned buffer (H2D copy); device inputs (on_device) are copied by one small kernel.
+    int stage_obs(const void* Z, const int* idf, int m, bool on_device, const T** dZ, const int** dIdf)
     {
         int rc = ensure_m(m);
         if (rc)
@@ -730,12 +732,21 @@ struct Ekf : EkfBase
             CSLAM_HIP_TRY(hipEventCreateWithFlags(&stage_ev[slot], hipEventDisableTiming));
             stage_ev_used[slot] = true;
         }
-        unsigned char* hs = static_cast<unsigned char*>(hStage) + slot_bytes(mcap) * slot;
         size_t         zb = (size_t)m * 2 * sizeof(T);
-        memcpy(hs, Z, zb);
-        memcpy(hs + zb, idf, (size_t)m * sizeof(int));
         unsigned char* ds = static_cast<unsigned char*>(dStage) + slot_bytes(mcap) * slot;
-        CSLAM_HIP_TRY(hipMemcpyAsync(ds, hs, zb + (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
+        if (on_device)
+        {
+            hipLaunchKernelGGL(ekf_stage_obs_kernel<T>, dim3((3 * m + 255) / 256), dim3(256), 0, stream,
+                               static_cast<const T*>(Z), idf, m, reinterpret_cast<T*>(ds), reinterpret_cast<int*>(ds + zb));
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        else
+        {
+            unsigned char* hs = static_cast<unsigned char*>(hStage) + slot_bytes(mcap) * slot;
+            memcpy(hs, Z, zb);
+            memcpy(hs + zb, idf, (size_t)m * sizeof(int));
+            CSLAM_HIP_TRY(hipMemcpyAsync(ds, hs, zb + (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
+        }
         CSLAM_HIP_TRY(hipEventRecord(stage_ev[slot], stream));
         *dZ   = reinterpret_cast<const T*>(ds);
         *dIdf = reinterpret_cast<const int*>(ds + zb);
@@ -991,7 +1002,7 @@ struct Ekf : EkfBase
         const T* dZ = nullptr;
         const int* dummy = nullptr;
         std::vector<int> zero_idf((size_t)m, 1);
-        if ((rc = stage_obs(Zv, zero_idf.data(), m, &dZ, &dummy)))
+        if ((rc = stage_obs(Zv, zero_idf.data(), m, false, &dZ, &dummy)))
         {
             return rc;
         }
@@ -1534,7 +1545,6 @@ struct Ekf : EkfBase
     T*          la_Y = nullptr;         // H_b * W1_a of the last window (for a fused wide kernel)
     LaModel<T>* la_model = nullptr;     // [2]: predict + observation model of update a / b
     int         la_kpad  = 0;
-    long long   la_windows = 0; // windows launched (diagnostics)
     int         la_cus = 0;        // compute units the persistent P-GEMM leaves to the chain kernel (0 until stream F exists)
     unsigned*   la_done   = nullptr; // device counter: workgroups of the blocks kernels that have finished
     unsigned    la_target = 0;       // its value once every blocks kernel launched so far has finished
@@ -1681,8 +1691,22 @@ struct Ekf : EkfBase
                kp_call_limit == 0;
     }
 
-    int la_enqueue(const T* dZ, const int* dIdf, int m, const T* R)
+    int la_enqueue(const T* dZ, const int* dIdf, int m, const T* R, bool on_device)
     {
+        // The first update of a window stays queued after this call returns, and the window reads its inputs when it
+        // launches, during a later call.  Device-resident inputs are therefore snapshotted now, on the main stream, into
+        // the staging ring: every read of a caller's dZ / d_idf is enqueued during that call (cslam.h).  The snapshot
+        // reaches the window's readers like a host-staged copy does: the rows and blocks kernels follow it on the main
+        // stream, and the chain kernel on stream F reads Z only after the blocks kernel has released it (or, with
+        // several engines, behind that kernel's event).  (On stream F with an event wait on the main stream instead,
+        // it measured no faster: DESIGN.md.)
+        if (on_device && la_n == 0)
+        {
+            if (int rc = stage_obs(dZ, dIdf, m, true, &dZ, &dIdf))
+            {
+                return rc;
+            }
+        }
         LaUpd u;
         u.dZ   = dZ;
         u.dIdf = dIdf;
@@ -2059,14 +2083,14 @@ struct Ekf : EkfBase
                     return fail(CSLAM_ERR_BAD_ARG, "update: idf[%d]=%d outside 1..%d", i, idf[i], nf);
                 }
             }
-            if ((rc = stage_obs(Zv, idf, m, &dZ, &dIdf)))
+            if ((rc = stage_obs(Zv, idf, m, false, &dZ, &dIdf)))
             {
                 return rc;
             }
         }
         if (batch && la_eligible(m))
         {
-            return la_enqueue(dZ, dIdf, m, R);
+            return la_enqueue(dZ, dIdf, m, R, on_device);
         }
         if ((rc = la_drain())) // (the held predict of THIS call survives the drain: la_launch_window keeps it)
         {
@@ -2829,6 +2853,17 @@ int cslam_ekf_set_pgemm_workgroups(cslam_ekf_t h, int workgroups)
         return fail(CSLAM_ERR_BAD_ARG, "set_pgemm_workgroups: negative");
     }
     B(h)->pgemm_wgs = workgroups;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_lookahead_windows(cslam_ekf_t h, long long* windows)
+{
+    CSLAM_NEED(h);
+    if (!windows)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "lookahead_windows: null");
+    }
+    *windows = B(h)->la_windows;
     return CSLAM_OK;
 }
 

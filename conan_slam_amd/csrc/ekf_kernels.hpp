@@ -726,6 +726,26 @@ __global__ void __launch_bounds__(64) ekf_assoc_scan_kernel(const T* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------
+// Snapshot of a device-resident update's inputs (Z: 2 x m, idf: m) into one slot of the staging ring, so that an
+// update that stays queued after its call (the first of a look-ahead window) no longer reads the caller's buffers.
+// One launch of one workgroup per 256 entries; the slot holds Z, then idf.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) ekf_stage_obs_kernel(const T* __restrict__ Z, const int* __restrict__ idf, int m,
+                                                             T* __restrict__ Zs, int* __restrict__ idfs)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 2 * m)
+    {
+        Zs[i] = Z[i];
+    }
+    else if (i < 3 * m)
+    {
+        idfs[i - 2 * m] = idf[i - 2 * m];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Deferred downdates.  The engine may hold the covariance as  P = Ps - Wp*Wp^T  with Ps the matrix stored
 // in HBM ("stale") and Wp (n x kp) the W1 panels of updates whose P-GEMM has not been applied yet; one
 // P-GEMM with k = kp then applies them all (slam.h:260 is linear in the panels).  Every reader of P adds the

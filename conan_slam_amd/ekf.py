@@ -119,6 +119,12 @@ class EKF:
     def synchronize(self):
         check(self._L.cslam_ekf_synchronize(self._h))
 
+    def lookahead_windows(self) -> int:
+        """look-ahead windows this handle has launched (cslam_ekf_lookahead_windows)"""
+        w = C.c_longlong(0)
+        check(self._L.cslam_ekf_lookahead_windows(self._h, C.byref(w)))
+        return w.value
+
     def factor_status(self, clear: bool = False) -> int:
         f = C.c_int(0)
         check(self._L.cslam_ekf_factor_status(self._h, C.byref(f), C.c_int(1 if clear else 0)))

@@ -111,7 +111,13 @@ int cslam_ekf_update(cslam_ekf_t h, const void* Z, int m, const void* R, const i
 
 /* Same, with Z and idf already resident in device memory (HBM); R stays a host pointer (4 scalars).  The host cannot
  * check device-resident indices: every kernel clamps them into 1..N before it forms an address and
- * CSLAM_FACTOR_BAD_IDF is raised (cslam_ekf_factor_status) when one was out of range. */
+ * CSLAM_FACTOR_BAD_IDF is raised (cslam_ekf_factor_status) when one was out of range.
+ * Lifetime: dZ / d_idf are read only by work that this call enqueues on the handle's streams (an update that a
+ * look-ahead window keeps queued past the call is read from a copy the call takes on the device).  The caller must
+ * keep both arrays unchanged until that work has run -- for example until cslam_ekf_synchronize returns, or until the
+ * handle's streams (cslam_ekf_get_streams) or the whole device have been synchronised, which keeps a queued look-ahead
+ * update queued; after that the buffers may be rewritten for the next call.  Writes the caller makes on another stream
+ * must be complete (or ordered before the handle's streams) when the call is made. */
 int cslam_ekf_update_device(cslam_ekf_t h, const void* dZ, int m, const void* R, const int* d_idf, int batch);
 
 /* Replaces Slam::augment(X, P, Z, R)  -- slam.h:190-191, EKF.cpp:9-26 / addOneNewFeature EKF.cpp:28-91.
@@ -141,7 +147,8 @@ int cslam_ekf_associate(cslam_ekf_t h, const void* Z, int m, const void* R, doub
  * results are the reference's up to rounding.  0 (default) applies each update's downdate at once.  The
  * sequential form update(batch = 0) always defers its m rank-2 downdates to one pass at the end of the call
  * (SURVEY.md 8f rank 2).  get_state / trace / associate / flush apply whatever is pending.
- * The shipped engine is single-stream and applies every batch update's P-GEMM at once unless a window is set here. */
+ * With 0 every batch update's P-GEMM is applied within its call; a window lets the P-GEMM of pending panels run
+ * later, under the next updates (and, in asynchronous mode, lets batch updates pair into look-ahead windows). */
 int cslam_ekf_set_deferred(cslam_ekf_t h, int max_pending_columns);
 int cslam_ekf_flush(cslam_ekf_t h);
 
@@ -149,6 +156,10 @@ int cslam_ekf_flush(cslam_ekf_t h);
  * the P-GEMM stream carries P -= W1*W1^T of the previous update (the same stream when the engine is not pipelined).
  * For callers that want to order their own work (event records, input copies) against the engine's. */
 int cslam_ekf_get_streams(cslam_ekf_t h, void** chain_stream, void** pgemm_stream);
+
+/* Look-ahead windows (pairs of asynchronous batch updates issued together, or a single update drained alone) that this
+ * handle has launched so far: lets a caller or a test confirm which schedule ran. */
+int cslam_ekf_lookahead_windows(cslam_ekf_t h, long long* windows);
 
 /* Cap on the workgroups of the persistent covariance-downdate kernel (0 = default: two per compute unit, i.e. the
  * whole chip).  For several filter instances that run side by side on one GPU (Monte-Carlo runs, one stream each): with
