@@ -32,6 +32,13 @@ class CslamError(RuntimeError):
 # per-instance controls and the pose read of every instance.
 BATCH_MC_SYMBOLS = ("cslam_ekf_batch_predict_each", "cslam_ekf_batch_get_poses")
 
+# The landmark reads (means and marginal covariance blocks without applying the pending downdate), with their prototypes.
+LANDMARK_SYMBOLS = ("cslam_ekf_get_landmarks", "cslam_ekf_batch_get_landmarks")
+_PROTOTYPES = {
+    "cslam_ekf_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cslam_ekf_batch_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
 
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
@@ -83,6 +90,9 @@ def lib() -> C.CDLL:
         _preload_shared_hip_runtime()
         _lib = C.CDLL(LIB_PATH)
         _lib.cslam_last_error.restype = C.c_char_p
+        for name, args in _PROTOTYPES.items():
+            fn = getattr(_lib, name)
+            fn.argtypes, fn.restype = args, C.c_int
     return _lib
 
 

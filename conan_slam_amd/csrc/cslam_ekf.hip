@@ -28,6 +28,7 @@
 #include "cslam_common.hpp"
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
+#include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_pgemm_limbs.hpp"
 #include "ekf_pose_kernels.hpp"
@@ -101,6 +102,7 @@ struct EkfBase
     virtual int set_state(const void* X, int n, const void* P, int ldp)                        = 0;
     virtual int get_state(void* X, void* P, int ldp)                                           = 0;
     virtual int get_x(void* X, int cap)                                                        = 0;
+    virtual int get_landmarks(int first, int count, void* x, void* pll, void* pvl)             = 0;
     virtual int trace(double* tr)                                                              = 0;
     virtual int predict(double v, double swa, const void* Q, double wb, double dt)             = 0;
     virtual int update(const void* Z, int m, const void* R, const int* idf, int batch, bool on_device) = 0;
@@ -128,6 +130,7 @@ struct Ekf : EkfBase
     T*   dWv = nullptr; // pose rows of the last update's W1 (3 x kcap), saved by the pose downdate before it zeroes them
     int* dPoseDone = nullptr; // ticket counters: [0] ekf_pose_step_kernel, [1] ekf_pose_downdate_kernel
     int* dSign     = nullptr; // per region: wcap column signs (heading columns with S < 0), then [2*wcap + r] their count
+    T*   dLm       = nullptr; // landmark read outputs: 12 scalars per landmark of capacity (allocated by the first read)
     int  hd_cols[2] = {0, 0}; // heading columns appended to each region since it became the pending store
     // the pending W1 store is two regions of wcap columns: `wcur` collects pending columns, the other one may still be
     // read by a P-GEMM in flight on stream B
@@ -248,6 +251,7 @@ struct Ekf : EkfBase
         (void)hipFree(dWv);
         (void)hipFree(dPoseDone);
         (void)hipFree(dSign);
+        (void)hipFree(dLm);
         free_workspace();
         (void)hipFree(dFlags);
         (void)hipFree(dHead);
@@ -827,6 +831,44 @@ struct Ekf : EkfBase
             return fail(CSLAM_ERR_BAD_ARG, "get_x: capacity %d < n=%d", cap, n);
         }
         return get_state(X, nullptr, 0);
+    }
+
+    // Landmarks first .. first + count - 1 (arguments checked by cslam_ekf_get_landmarks, queued work launched by
+    // resolve_predict): P = Ps - Wp diag(s) Wp^T is read as it stands (ekf_landmark_kernels.hpp), so the pending columns
+    // stay pending and every later result is the one the run would give without this read.  Two-stream mode: the read
+    // is ORDERED behind the P-GEMMs in flight on stream B (they write Ps), as get_state is; it does not correct for them.
+    int get_landmarks(int first, int count, void* x, void* pll, void* pvl) override
+    {
+        int rc = use_device();
+        if (rc || (rc = wait_pgemm()))
+        {
+            return rc;
+        }
+        if (dLm == nullptr)
+        {
+            CSLAM_HIP_TRY(hipMalloc(&dLm, (size_t)std::max(nmax, 1) * 12 * sizeof(T)));
+        }
+        const size_t c  = (size_t)count;
+        T*           ox = dLm, *opll = dLm + 2 * c, *opvl = dLm + 6 * c;
+        const int*   sg = (kp > 0 && hd_cols[wcur] > 0) ? dSign + (size_t)wcur * wcap : (const int*)nullptr;
+        hipLaunchKernelGGL(ekf_landmark_read_kernel<T>, dim3((count + 255) / 256), dim3(256), 0, stream, dX, dPv, dP, ldp,
+                           lower, (const T*)wbase(wcur), ldp, kp, sg, first, count, x ? ox : (T*)nullptr,
+                           pll ? opll : (T*)nullptr, pvl ? opvl : (T*)nullptr);
+        CSLAM_HIP_TRY(hipGetLastError());
+        if (x)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(x, ox, 2 * c * sizeof(T), hipMemcpyDeviceToHost, stream));
+        }
+        if (pll)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(pll, opll, 4 * c * sizeof(T), hipMemcpyDeviceToHost, stream));
+        }
+        if (pvl)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(pvl, opvl, 6 * c * sizeof(T), hipMemcpyDeviceToHost, stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
     }
 
     int trace(double* tr) override
@@ -2761,6 +2803,25 @@ int cslam_ekf_get_x(cslam_ekf_t h, void* X, int capacity)
         return rc;
     }
     return B(h)->get_x(X, capacity);
+}
+
+int cslam_ekf_get_landmarks(cslam_ekf_t h, int first, int count, void* x, void* pll, void* pvl)
+{
+    CSLAM_NEED(h);
+    const long long nl = (B(h)->n - 3) / 2;
+    if ((!x && !pll && !pvl) || first < 1 || count < 0 || (long long)first - 1 + count > nl)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "get_landmarks: bad arguments (first %d, count %d, %lld landmarks)", first, count, nl);
+    }
+    if (count == 0)
+    {
+        return CSLAM_OK;
+    }
+    if (int rc = B(h)->resolve_predict()) // (as get_x: the held predict, the pose queue, a queued look-ahead update)
+    {
+        return rc;
+    }
+    return B(h)->get_landmarks(first, count, x, pll, pvl);
 }
 
 int cslam_ekf_get_n(cslam_ekf_t h, int* n)

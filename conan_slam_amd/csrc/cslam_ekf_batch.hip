@@ -29,6 +29,7 @@
 #include "cslam_common.hpp"
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
+#include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_pose_kernels.hpp"
 
@@ -79,6 +80,26 @@ __global__ void __launch_bounds__(256) ekf_la_signal_batch(unsigned* signal, uns
         atomicAdd(signal + (size_t)threadIdx.x * stride, add);
     }
 }
+
+// batched engine (f32, block-lower): grid = (ceil(count / 256), I); instance i's slabs at the labatch strides (X ldp,
+// Pv 3 ldp, P ldp^2, pending region sW) and its outputs at i * count landmarks
+__global__ void __launch_bounds__(256) ekf_landmark_read_batch(const float* __restrict__ X, const float* __restrict__ Pv,
+                                                               const float* __restrict__ P, int ldp,
+                                                               const float* __restrict__ W, long sW, int kp, int first,
+                                                               int count, float* __restrict__ x, float* __restrict__ pll,
+                                                               float* __restrict__ pvl)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= count)
+    {
+        return;
+    }
+    const size_t i = blockIdx.y;
+    const size_t L = (size_t)ldp;
+    const size_t c = (size_t)count;
+    landmark_read_body<float>(X + i * L, Pv + i * 3 * L, P + i * L * L, ldp, 1, W + i * (size_t)sW, ldp, kp, nullptr, first,
+                              j, x ? x + i * 2 * c : nullptr, pll ? pll + i * 4 * c : nullptr, pvl ? pvl + i * 6 * c : nullptr);
+}
 } // namespace cslam
 
 struct cslam_ekf_batch
@@ -107,6 +128,7 @@ struct cslam_ekf_batch
     PoseSeq<float>     pseq{};                                          // queued control steps
     float*             dHead     = nullptr; // [I][ldp]: the column of heading steps without a map (n = 3)
     int*               dPoseDone = nullptr; // [I]: ticket counters of ekf_pose_step_batch_kernel
+    float*             dLm       = nullptr; // landmark read outputs: 12 floats per instance and landmark of capacity
     // per-instance controls (cslam_ekf_batch_predict_each): the held predict's (v, swa) per instance, and a ring of
     // kCtlSlots slots [kPoseSeqMax][I][2] -- one per pose-queue launch -- filled in pinned host memory, copied in on the
     // main stream and read by ekf_pose_step_batch_each_kernel.  A slot is refilled only after ev_ctl says the launch that
@@ -180,6 +202,7 @@ struct cslam_ekf_batch
         (void)hipFree(dTicket);
         (void)hipFree(dStamps);
         (void)hipFree(dCtl);
+        (void)hipFree(dLm);
         (void)hipHostFree(hCtl);
         for (hipEvent_t& e : ev_ctl)
         {
@@ -826,6 +849,51 @@ int cslam_ekf_batch_get_poses(cslam_ekf_batch_t h, float* x, float* pvv)
     {
         CSLAM_HIP_TRY(hipMemcpy2DAsync(pvv, 3 * sizeof(float), h->dPv, L * sizeof(float), 3 * sizeof(float), (size_t)3 * h->I,
                                        hipMemcpyDeviceToHost, h->stream));
+    }
+    CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, float* x, float* pll, float* pvl)
+{
+    if (!h || (!x && !pll && !pvl) || first < 1 || count < 0 || (long long)first - 1 + count > (h->n - 3) / 2)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_get_landmarks: bad arguments (first %d, count %d)", first, count);
+    }
+    if (count == 0)
+    {
+        return CSLAM_OK;
+    }
+    int rc = h->use_device();
+    if (rc || (rc = h->drain()))
+    {
+        return rc;
+    }
+    // P = Ps - Wp Wp^T over the kp columns of region wcur, read as it stands (ekf_landmark_kernels.hpp): no flush, so
+    // the pending columns stay pending and every later result is the one the run would give without this read.  Every
+    // writer of X, Pv, Ps and the pending store runs on the main stream (the chains on stream F hand over to the wide
+    // kernel there), so the read is ordered behind them.
+    if (h->dLm == nullptr)
+    {
+        CSLAM_HIP_TRY(hipMalloc(&h->dLm, (size_t)h->I * std::max((h->ncap - 3) / 2, 1) * 12 * sizeof(float)));
+    }
+    const size_t c  = (size_t)h->I * count;
+    float*       ox = h->dLm, *opll = h->dLm + 2 * c, *opvl = h->dLm + 6 * c;
+    hipLaunchKernelGGL(ekf_landmark_read_batch, dim3((count + 255) / 256, h->I), dim3(256), 0, h->stream, h->dX, h->dPv, h->dP,
+                       h->ldp, h->wregion(h->wcur), (long)h->sW(), h->kp, first, count, x ? ox : nullptr,
+                       pll ? opll : nullptr, pvl ? opvl : nullptr);
+    CSLAM_HIP_TRY(hipGetLastError());
+    if (x)
+    {
+        CSLAM_HIP_TRY(hipMemcpyAsync(x, ox, 2 * c * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (pll)
+    {
+        CSLAM_HIP_TRY(hipMemcpyAsync(pll, opll, 4 * c * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    }
+    if (pvl)
+    {
+        CSLAM_HIP_TRY(hipMemcpyAsync(pvl, opvl, 6 * c * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     }
     CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
     return CSLAM_OK;

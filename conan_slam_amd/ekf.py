@@ -125,6 +125,19 @@ class EKF:
         check(self._L.cslam_ekf_lookahead_windows(self._h, C.byref(w)))
         return w.value
 
+    def landmarks(self, first: int = 1, count: int = None):
+        """(x [c, 2], P [c, 2, 2], Pvl [c, 3, 2]) of landmarks first .. first + c - 1 (1-based; count None: to the
+        last): means, marginal 2 x 2 blocks and pose-landmark blocks P[0:3, fx:fx+2], read without applying the pending
+        covariance downdate (cslam_ekf_get_landmarks): the run continues bit for bit as without the read."""
+        if count is None:
+            count = max((self.n - 3) // 2 - first + 1, 0)
+        x = np.empty((count, 2), dtype=self.dtype)
+        pll = np.empty((count, 4), dtype=self.dtype)
+        pvl = np.empty((count, 6), dtype=self.dtype)
+        check(self._L.cslam_ekf_get_landmarks(self._h, int(first), int(count), _vp(x), _vp(pll), _vp(pvl)))
+        # (column-major blocks per landmark)
+        return x, pll.reshape(count, 2, 2).transpose(0, 2, 1).copy(), pvl.reshape(count, 2, 3).transpose(0, 2, 1).copy()
+
     def factor_status(self, clear: bool = False) -> int:
         f = C.c_int(0)
         check(self._L.cslam_ekf_factor_status(self._h, C.byref(f), C.c_int(1 if clear else 0)))
@@ -331,6 +344,19 @@ class EKFBatch:
         pv = np.empty((self.instances, 9), dtype=np.float32)
         check(self._L.cslam_ekf_batch_get_poses(self._h, _vp(x), _vp(pv)))
         return x, pv.reshape(self.instances, 3, 3).transpose(0, 2, 1).copy()  # (column-major per instance)
+
+    def landmarks(self, first: int = 1, count: int = None):
+        """EKF.landmarks for every instance: (x [I, c, 2], P [I, c, 2, 2], Pvl [I, c, 3, 2]) after launching what is
+        queued, without the covariance downdate or a copy of P (cslam_ekf_batch_get_landmarks)."""
+        if count is None:
+            count = max(self.n_landmarks - first + 1, 0)
+        I = self.instances
+        x = np.empty((I, count, 2), dtype=np.float32)
+        pll = np.empty((I, count, 4), dtype=np.float32)
+        pvl = np.empty((I, count, 6), dtype=np.float32)
+        check(self._L.cslam_ekf_batch_get_landmarks(self._h, int(first), int(count), _vp(x), _vp(pll), _vp(pvl)))
+        return (x, pll.reshape(I, count, 2, 2).transpose(0, 1, 3, 2).copy(),
+                pvl.reshape(I, count, 2, 3).transpose(0, 1, 3, 2).copy())
 
     def observe_heading(self, phi: float, use: bool = True):
         """Slam::observeHeading on every instance (phi common).  An instance with P22 + R <= 0 skips it and raises

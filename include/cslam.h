@@ -95,6 +95,21 @@ int cslam_ekf_set_state(cslam_ekf_t h, const void* X, int n, const void* P, int 
 int cslam_ekf_get_state(cslam_ekf_t h, void* X, void* P, int ldp); /* synchronises */
 int cslam_ekf_get_x(cslam_ekf_t h, void* X, int capacity);         /* synchronises; writes n scalars */
 int cslam_ekf_get_n(cslam_ekf_t h, int* n);
+/* The means and marginal covariances of landmarks first .. first+count-1 (1-based feature numbers, as idf;
+ * 1 <= first, first+count-1 <= N = (n-3)/2, count >= 0), in the handle's dtype:
+ *   x   [count][2]  X[fx], X[fx+1]                         (fx = 3 + 2*(f-1), 0-based)
+ *   pll [count][4]  P[fx:fx+2, fx:fx+2], 2 x 2 column-major, exactly symmetric
+ *   pvl [count][6]  P[0:3, fx:fx+2], 3 x 2 column-major
+ * This replaces the caller reading X and P directly, which the reference allows because the driver owns them and
+ * passes them by reference (test/main.cpp:107-108); the reference's data association reads exactly these blocks
+ * through H*P*H^T (computeAssociation, EKF.cpp:131-144).  Unlike get_state / trace it NEVER applies the pending
+ * covariance downdate, mirrors P or copies P: the 2 x 2 blocks are read from the deferred form (P = Ps - Wp Wp^T over
+ * the pending columns), so a run that reads its landmarks ends bit for bit where the same run without the reads ends.
+ * Queued work is launched first, exactly as get_x does: a held predict, the pose queue, and a queued look-ahead
+ * update (as a window of one -- that update alone then rounds as a window of one would).  Two-stream mode
+ * (CSLAM_PIPELINE=1): the read waits for the P-GEMMs in flight.  Any output may be NULL, not all three; count = 0
+ * returns CSLAM_OK at once; a bad range returns CSLAM_ERR_BAD_ARG and changes nothing.  Synchronises. */
+int cslam_ekf_get_landmarks(cslam_ekf_t h, int first, int count, void* x, void* pll, void* pvl);
 int cslam_ekf_trace(cslam_ekf_t h, double* trace);                 /* synchronises */
 int cslam_ekf_synchronize(cslam_ekf_t h);
 int cslam_ekf_factor_status(cslam_ekf_t h, int* flags, int clear); /* synchronises */
@@ -241,6 +256,12 @@ int cslam_ekf_batch_predict_each(cslam_ekf_batch_t h, const double* v, const dou
  * queued (as the other reads do): 48 bytes per instance, no covariance downdate and no copy of P.  Synchronises.
  * x: [instances][3], pvv: [instances][9]; either may be NULL. */
 int cslam_ekf_batch_get_poses(cslam_ekf_batch_t h, float* x, float* pvv);
+/* cslam_ekf_get_landmarks for every instance (same arguments, blocks and guarantees): x [instances][count][2],
+ * pll [instances][count][4], pvl [instances][count][6].  Launches what is queued (as get_poses), then reads the pending
+ * region as it stands: no covariance downdate, no mirror and no copy of P -- 12 floats per instance and landmark -- and
+ * the run continues bit for bit as without the read.  For Monte-Carlo scoring of the map (landmark error and NEES,
+ * e^T P_jj^-1 e) in place of get_state (test/main.cpp:107-108; the blocks EKF.cpp:131-144 reads).  Synchronises. */
+int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, float* x, float* pll, float* pvl);
 /* Slam::observeHeading (slam.h:788, EKF.cpp:328-352, josephUpdate slam.h:700-725) on every instance.  phi is common,
  * as in the reference driver, which observes the true heading.  Deliberate difference from the single handle: an
  * instance whose S = P22 + R is <= 0 or non-finite (an indefinite P; a healthy filter never has one) skips the heading

@@ -10,7 +10,10 @@ the sensor and the association table are test-side helpers, not product code), t
            augment_device, one launch per stage for all instances;
   handles  I EKF handles, one host thread each (as tools/mc_loop.py).
 Prints one JSON line: control steps per second of each driver (a step advances every instance by one control step),
-and per instance the pose RMSE and mean NEES against the truth at the observation steps, from EKFBatch.poses().
+and per instance the pose RMSE and mean NEES against the truth at the observation steps, from EKFBatch.poses(), and the
+map RMSE and mean landmark NEES (e^T P_jj^-1 e per landmark, averaged over landmarks and steps) from
+EKFBatch.landmarks(), which reads without applying the pending covariance downdate: scoring does not perturb the runs.
+The true landmark of each state feature is the demo map's landmark the association table gave it.
 
     python tools/mc_demo.py [--instances 8] [--steps 2400] [--seed 1000] [--quirks textbook|ref_exact]
 """
@@ -83,6 +86,53 @@ def truth_poses(LM, WP, steps):
         sim.vehicle_model(XTrue, cfg.velocity, swa, cfg.wheel_base, f(cfg.dt_controls))
         out.append(XTrue.astype(np.float64).copy())
     return out
+
+
+class _MapTable:
+    """run_demo back-end without a filter, noise off: the demo map landmark behind every state feature, in augment
+    order (the table association appends new features in the order data_associate_table returns them)."""
+
+    def __init__(self, LM, truth):
+        self.LM, self.truth, self.step, self.nf, self.lm = LM, truth, 0, 0, []
+
+    @property
+    def n(self):
+        return 3 + 2 * self.nf
+
+    def predict(self, *a):
+        self.step += 1
+
+    def observe_heading(self, *a):
+        pass
+
+    def update(self, *a):
+        return 0
+
+    def augment(self, Z, R):
+        x = self.truth[self.step - 1]
+        for c in range(Z.shape[1] if Z.size else 0):
+            r, b = float(Z[0, c]), float(Z[1, c])
+            p = np.array([x[0] + r * np.cos(b + x[2]), x[1] + r * np.sin(b + x[2])])
+            d = np.hypot(self.LM[0] - p[0], self.LM[1] - p[1])
+            assert d.min() < 1e-2 * r + 1e-3, "a noise-free observation must land on its landmark"
+            self.lm.append(int(np.argmin(d)))
+            self.nf += 1
+
+    def get_x(self):
+        return np.zeros(self.n, np.float32)
+
+    def get_p(self):
+        return np.zeros((self.n, self.n), np.float32)
+
+
+def map_truth(steps):
+    """[N, 2]: the true position of state feature j + 1, from a noise-free run of the same demo."""
+    from sim_driver import load_demo_map, run_demo
+
+    LM, WP = load_demo_map()
+    t = _MapTable(LM.astype(np.float64), truth_poses(LM, WP, steps))
+    run_demo(t, LM, WP, noise_seed=None, max_steps=steps)
+    return LM.astype(np.float64)[:, t.lm].T
 
 
 def record(I, seed, steps, quirks):
@@ -188,8 +238,11 @@ def main():
         for h in hs:
             h.close()
 
-    # accuracy: pose error and NEES at every observation step, from poses()
+    # accuracy: pose error and NEES at every observation step, from poses(); map error and landmark NEES from
+    # landmarks() (the features seen so far, truth through the association table)
     err2, nees = [[] for _ in range(I)], [[] for _ in range(I)]
+    lm_true = map_truth(args.steps)
+    merr2, mnees = [[] for _ in range(I)], [[] for _ in range(I)]
 
     def score(step, b):
         x, pvv = b.poses()
@@ -202,6 +255,15 @@ def main():
                 nees[i].append(float(e @ np.linalg.solve(pvv[i].astype(np.float64), e)))
             except np.linalg.LinAlgError:
                 nees[i].append(float("nan"))
+        xl, pll, _ = b.landmarks()
+        e = xl.astype(np.float64) - lm_true[None, : xl.shape[1]]
+        for i in range(I):
+            merr2[i].extend((e[i] ** 2).sum(axis=1).tolist())
+            try:
+                mnees[i].append(float(np.mean(np.einsum("ja,ja->j", e[i], np.linalg.solve(pll[i].astype(np.float64),
+                                                                                            e[i][:, :, None])[:, :, 0]))))
+            except np.linalg.LinAlgError:
+                mnees[i].append(float("nan"))
 
     b = EKFBatch(I, n_landmarks=0, max_landmarks=64, quirks=quirks)
     drive_batch(b, recs, dz, di, score)
@@ -215,6 +277,8 @@ def main():
         "speedup": round(t_handles / t_batch, 3),
         "pose_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in err2],
         "mean_nees": [round(float(np.nanmean(v)), 3) for v in nees],
+        "map_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in merr2],
+        "mean_landmark_nees": [round(float(np.nanmean(v)), 3) for v in mnees],
         "factor_status": flags,
     }))
 
