@@ -9,6 +9,6 @@ from . import _capi  # noqa: F401
 from ._capi import (CslamError, F32, F64, Q_LOWER_CHOL_GAIN, Q_PREDICT_NM4, Q_REF_EXACT, Q_TEXTBOOK,  # noqa: F401
                     device_count)
 from .ekf import EKF, EKFBatch  # noqa: F401
-from .sim import Simulator  # noqa: F401
+from .sim import BatchSimulator, Simulator  # noqa: F401
 
-__all__ = ["EKF", "EKFBatch", "Simulator", "CslamError", "F32", "F64", "Q_REF_EXACT", "Q_TEXTBOOK", "device_count"]
+__all__ = ["EKF", "EKFBatch", "Simulator", "BatchSimulator", "CslamError", "F32", "F64", "Q_REF_EXACT", "Q_TEXTBOOK", "device_count"]

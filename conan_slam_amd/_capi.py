@@ -37,7 +37,18 @@ LANDMARK_SYMBOLS = ("cslam_ekf_get_landmarks", "cslam_ekf_batch_get_landmarks")
 _PROTOTYPES = {
     "cslam_ekf_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cslam_ekf_batch_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    # the batched scan generator and the two batch calls that consume its scans
+    "cslam_sim_batch_create": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_void_p)],
+    "cslam_sim_batch_destroy": [C.c_void_p],
+    "cslam_sim_batch_scan": [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_longlong, C.POINTER(C.c_int),
+                             C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "cslam_sim_batch_get_scan": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cslam_sim_batch_get_table": [C.c_void_p, C.c_void_p],
+    "cslam_sim_batch_set_table": [C.c_void_p, C.c_void_p],
+    "cslam_ekf_batch_update_scan": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "cslam_ekf_batch_augment_scan": [C.c_void_p, C.c_void_p, C.c_void_p],
 }
+SIM_BATCH_SYMBOLS = tuple(k for k in _PROTOTYPES if "sim_batch" in k or k.endswith("_scan"))
 
 
 def declared_symbols(header_path: str = HEADER_PATH):

@@ -32,6 +32,7 @@
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_pose_kernels.hpp"
+#include "sim_scan_view.hpp"
 
 using namespace cslam;
 
@@ -541,6 +542,52 @@ struct cslam_ekf_batch
     {
         CSLAM_HIP_TRY(hipEventRecord(ev_gen[g], stream)); // (the chains of a window finish before its wide kernel does)
         gen_used[g] = true;
+        return CSLAM_OK;
+    }
+
+    // what cslam_ekf_batch_update launches ahead of its window: a held predict_each never rides inside the window (its
+    // rows, chain and wide kernels take the predict by value), it is launched first as a predict-only pose step
+    int launch_before_update() { return (pp.valid && pp_each) ? drain() : launch_pose_queue(); }
+
+    // one window of ONE update at once (pairing updates across calls would hold the caller's buffers); the held predict,
+    // if any, rides inside it.  Ztab / idftab: device tables of one pointer per instance.
+    int update_window(const float* const* Ztab, const int* const* idftab, int m, const float* R)
+    {
+        LaBatchWin w;
+        memset(&w, 0, sizeof(w));
+        w.nu     = 1;
+        w.ma     = m;
+        w.mb     = m;
+        w.Ztab   = Ztab;
+        w.idftab = idftab;
+        w.pp_a   = pp;
+        w.pp_b   = pp;
+        for (int e = 0; e < 4; e++)
+        {
+            w.R[e] = R[e];
+        }
+        pp.valid = 0;
+        return window(w);
+    }
+
+    // q new features per instance from za.z[i] (device).  Everything is on the main stream: the P-GEMM that may sweep Ps
+    // has run by the time the new rows are written, and the pending panels have zero rows for the new features (see
+    // queue_step), so the kernel writes values of the true P.
+    int augment_features(AugBatchArgs& za, int q, const float* R)
+    {
+        int rc = drain(); // (the new rows are built from the pose and the stripe: they must be current)
+        if (rc)
+        {
+            return rc;
+        }
+        for (int f = 0; f < q; f++)
+        {
+            za.f = f;
+            hipLaunchKernelGGL(ekf_augment_batch_kernel<float>, dim3((n + 255) / 256, I), dim3(256), 0, stream, dX, dP, dPv, ldp,
+                               n, za, R[0], R[1], R[2], R[3]);
+            CSLAM_HIP_TRY(hipGetLastError());
+            n += 2;
+        }
         return CSLAM_OK;
     }
 
@@ -1187,29 +1234,11 @@ int cslam_ekf_batch_update(cslam_ekf_batch_t h, const float* const* dZ, const in
     }
     int rc = h->use_device();
     int g  = 0;
-    // a held predict_each never rides inside the window (its rows, chain and wide kernels take the predict by value):
-    // it is launched first as a predict-only pose step
-    if (rc || (rc = (h->pp.valid && h->pp_each) ? h->drain() : h->launch_pose_queue()) || (rc = h->stage_inputs(dZ, d_idf, &g)))
+    if (rc || (rc = h->launch_before_update()) || (rc = h->stage_inputs(dZ, d_idf, &g)))
     {
         return rc;
     }
-    // one window of ONE update at once (pairing updates across calls would hold the caller's buffers); the held predict,
-    // if any, rides inside it
-    LaBatchWin w;
-    memset(&w, 0, sizeof(w));
-    w.nu     = 1;
-    w.ma     = m;
-    w.mb     = m;
-    w.Ztab   = h->dZtab + (size_t)g * h->I;
-    w.idftab = h->dIdftab + (size_t)g * h->I;
-    w.pp_a   = h->pp;
-    w.pp_b   = h->pp;
-    for (int e = 0; e < 4; e++)
-    {
-        w.R[e] = R[e];
-    }
-    h->pp.valid = 0;
-    if ((rc = h->window(w)))
+    if ((rc = h->update_window(h->dZtab + (size_t)g * h->I, h->dIdftab + (size_t)g * h->I, m, R)))
     {
         return rc;
     }
@@ -1241,21 +1270,109 @@ int cslam_ekf_batch_augment(cslam_ekf_batch_t h, const float* const* dZn, int q,
         za.z[i] = dZn[i];
     }
     int rc = h->use_device();
-    if (rc || (rc = h->drain())) // (the new rows are built from the pose and the stripe: they must be current)
+    if (rc)
     {
         return rc;
     }
-    // Everything is on the main stream: the P-GEMM that may sweep Ps has run by the time the new rows are written, and the
-    // pending panels have zero rows for the new features (see queue_step), so the kernel writes values of the true P.
-    for (int f = 0; f < q; f++)
+    return h->augment_features(za, q, R);
+}
+
+// The two calls of an observation step (test/main.cpp:188-189) fed from the batched scan generator's current scan
+// (cslam_sim_batch.hip): the pointer tables are resident in the scan slot, so nothing is staged; the slot's event is
+// recorded behind the last kernel that reads it (the chains of a window finish before its wide kernel does).
+static int scan_view_for(const char* who, cslam_ekf_batch_t b, cslam_sim_batch_t s, SimScanView* v)
+{
+    if (!b || !s)
     {
-        za.f = f;
-        hipLaunchKernelGGL(ekf_augment_batch_kernel<float>, dim3((h->n + 255) / 256, h->I), dim3(256), 0, h->stream, h->dX, h->dP,
-                           h->dPv, h->ldp, h->n, za, R[0], R[1], R[2], R[3]);
-        CSLAM_HIP_TRY(hipGetLastError());
-        h->n += 2;
+        return fail(CSLAM_ERR_BAD_ARG, "%s: null handle", who);
+    }
+    int rc = sim_batch_current(s, v);
+    if (rc)
+    {
+        return rc;
+    }
+    if (v->instances != b->I || v->device != b->device)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "%s: the scan is for %d instances on device %d, the batch has %d on device %d", who,
+                    v->instances, v->device, b->I, b->device);
     }
     return CSLAM_OK;
+}
+
+int cslam_ekf_batch_update_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* R)
+{
+    SimScanView v;
+    int         rc = scan_view_for("ekf_batch_update_scan", b, s, &v);
+    if (rc)
+    {
+        return rc;
+    }
+    if (v.updated)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update_scan: this scan has been consumed by an update already");
+    }
+    if (v.mf == 0)
+    {
+        return sim_batch_mark(s, kScanUpdated, false);
+    }
+    if (v.augmented)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update_scan: the update of a scan comes before its augment");
+    }
+    if (!R || (b->n - 3) / 2 != v.nf)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_update_scan: the batch holds %d features, the scan was split against %d (or R is null)",
+                    (b->n - 3) / 2, v.nf);
+    }
+    if ((rc = b->use_device()) || (rc = b->launch_before_update()) || (rc = b->update_window(v.Ztab, v.idftab, v.mf, R)))
+    {
+        return rc;
+    }
+    CSLAM_HIP_TRY(hipEventRecord(v.consumed, b->stream));
+    return sim_batch_mark(s, kScanUpdated, true);
+}
+
+int cslam_ekf_batch_augment_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* R)
+{
+    SimScanView v;
+    int         rc = scan_view_for("ekf_batch_augment_scan", b, s, &v);
+    if (rc)
+    {
+        return rc;
+    }
+    if (v.augmented)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_augment_scan: this scan has been consumed by an augment already");
+    }
+    if (v.mf > 0 && !v.updated)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_augment_scan: the update of a scan comes before its augment");
+    }
+    if (v.mn == 0)
+    {
+        return sim_batch_mark(s, kScanAugmented, false);
+    }
+    if (!R || (b->n - 3) / 2 != v.nf)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_augment_scan: the batch holds %d features, the scan was split against %d (or R is null)",
+                    (b->n - 3) / 2, v.nf);
+    }
+    if (b->n + 2 * v.mn > b->ncap)
+    {
+        return fail(CSLAM_ERR_CAPACITY, "ekf_batch_augment_scan: %d features would exceed max_landmarks=%d", (b->n - 3) / 2 + v.mn,
+                    (b->ncap - 3) / 2);
+    }
+    AugBatchArgs za;
+    for (int i = 0; i < b->I; i++)
+    {
+        za.z[i] = v.ZN + (size_t)i * kScanStride;
+    }
+    if ((rc = b->use_device()) || (rc = b->augment_features(za, v.mn, R)))
+    {
+        return rc;
+    }
+    CSLAM_HIP_TRY(hipEventRecord(v.consumed, b->stream));
+    return sim_batch_mark(s, kScanAugmented, true);
 }
 
 } // extern "C"

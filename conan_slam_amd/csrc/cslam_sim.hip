@@ -9,9 +9,9 @@
 // Here the map, the table, the scan and its split stay in HBM; the filter is fed with cslam_ekf_update_device and the
 // only thing that returns to the host per step is three counters.
 //
-// Kernels: one workgroup of 1024 threads walks the landmarks / the scan in order and compacts with a block-wide
-// exclusive scan, so that the outputs come out in ascending tag order exactly as the reference's sequential loops
-// produce them (integer outputs are bit-exact against the oracle).
+// Kernels (bodies in sim_kernels.hpp, shared with the batched generator): one workgroup of 1024 threads walks the
+// landmarks / the scan in order and compacts with a block-wide exclusive scan, so that the outputs come out in ascending
+// tag order exactly as the reference's sequential loops produce them (integer outputs are bit-exact against the oracle).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,6 +22,7 @@
 
 #include "cslam_common.hpp"
 #include "device_math.hpp"
+#include "sim_kernels.hpp"
 #include "../../include/cslam.h"
 
 namespace cslam
@@ -29,64 +30,14 @@ namespace cslam
 namespace
 {
 
-constexpr int kSimThreads = 1024;
-
-// exclusive prefix sum of one flag per thread over the workgroup; returns the thread's offset, *total = block sum
-__device__ inline int block_exclusive_scan(int flag, int* s_wave, int* total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag != 0);
-    const int                in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0)
-    {
-        s_wave[wave] = __popcll(bal);
-    }
-    __syncthreads();
-    int base = 0, sum = 0;
-    for (int w = 0; w < kSimThreads / 64; w++)
-    {
-        const int c = s_wave[w];
-        base += (w < wave) ? c : 0;
-        sum += c;
-    }
-    __syncthreads();
-    *total = sum;
-    return base + in_wave;
-}
-
-// slam.h:575-683 getVisibleLandmarks + slam.h:339-368 computeRangeBearing.  The visibility test is evaluated in
-// double on the float differences, as the reference does (slam.h:627-628 stores float subtractions in doubles).
+// slam.h:575-683 getVisibleLandmarks + slam.h:339-368 computeRangeBearing (body: sim_kernels.hpp)
 template <typename T>
 __global__ void __launch_bounds__(kSimThreads) sim_get_observations_kernel(const T* __restrict__ LM, int nlm, T x, T y,
                                                                              T phi, T rmax, T* __restrict__ Z,
                                                                              int* __restrict__ tags, int* __restrict__ count)
 {
     __shared__ int s_wave[kSimThreads / 64];
-    const double   cphi = cos((double)phi), sphi = sin((double)phi), rm = (double)rmax;
-    int            done = 0;
-    for (int base = 0; base < nlm; base += kSimThreads)
-    {
-        const int i   = base + threadIdx.x;
-        bool      vis = false;
-        T         fx = (T)0, fy = (T)0;
-        if (i < nlm)
-        {
-            fx = LM[2 * i] - x;
-            fy = LM[2 * i + 1] - y;
-            const double dx = (double)fx, dy = (double)fy;
-            vis = (fabs(dx) < rm && fabs(dy) < rm) && ((dx * cphi + dy * sphi) > 0.0) && ((dx * dx + dy * dy) < rm * rm);
-        }
-        int       total;
-        const int off = block_exclusive_scan(vis ? 1 : 0, s_wave, &total);
-        if (vis)
-        {
-            const int o  = done + off;
-            Z[2 * o]     = dsqrt(fx * fx + fy * fy);
-            Z[2 * o + 1] = datan2(fy, fx) - phi;
-            tags[o]      = i + 1;
-        }
-        done += total;
-    }
+    const int      done = sim_get_observations_body<T>(LM, nlm, x, y, phi, rmax, Z, tags, nlm, s_wave);
     if (threadIdx.x == 0)
     {
         *count = done;
@@ -105,8 +56,7 @@ __global__ void sim_add_noise_kernel(T* __restrict__ Z, const T* __restrict__ no
     }
 }
 
-// EKF.cpp:146-233.  The scan is split by the table as it stands before this scan (EKF.cpp:169-182); then the new
-// tags receive the state positions nf+1, nf+2, ... in scan order (EKF.cpp:213-226).
+// EKF.cpp:146-233 (body: sim_kernels.hpp)
 template <typename T>
 __global__ void __launch_bounds__(kSimThreads) sim_associate_table_kernel(const T* __restrict__ Z, const int* __restrict__ tags,
                                                                             const int* __restrict__ count, int* __restrict__ table,
@@ -114,34 +64,8 @@ __global__ void __launch_bounds__(kSimThreads) sim_associate_table_kernel(const 
                                                                             T* __restrict__ ZN, int* __restrict__ out_counts)
 {
     __shared__ int s_wave[kSimThreads / 64];
-    const int      m = *count;
-    int            nknown = 0, nnew = 0;
-    for (int base = 0; base < m; base += kSimThreads)
-    {
-        const int i  = base + threadIdx.x;
-        const int id = (i < m) ? tags[i] : 0;
-        const int pos = (i < m) ? table[id - 1] : 0;
-        const bool known = (i < m) && pos != 0, fresh = (i < m) && pos == 0;
-        int        tk, tn;
-        const int  ok = block_exclusive_scan(known ? 1 : 0, s_wave, &tk);
-        const int  on = block_exclusive_scan(fresh ? 1 : 0, s_wave, &tn);
-        if (known)
-        {
-            const int o = nknown + ok;
-            ZF[2 * o]     = Z[2 * i];
-            ZF[2 * o + 1] = Z[2 * i + 1];
-            idf[o]        = pos;
-        }
-        if (fresh)
-        {
-            const int o = nnew + on;
-            ZN[2 * o]     = Z[2 * i];
-            ZN[2 * o + 1] = Z[2 * i + 1];
-            table[id - 1] = nf + o + 1; // (read above by the same thread only: tags within a scan are distinct)
-        }
-        nknown += tk;
-        nnew += tn;
-    }
+    int            nknown, nnew;
+    sim_associate_table_body<T>(Z, tags, *count, table, nf, ZF, idf, ZN, nullptr, s_wave, &nknown, &nnew);
     if (threadIdx.x == 0)
     {
         out_counts[0] = nknown;

@@ -1,0 +1,446 @@
+// cslam_sim_batch.hip -- the batched scan generator: the sensor side of the reference's demo loop (test/main.cpp:139-165)
+// for I Monte-Carlo runs that share the true trajectory and the map, feeding cslam_ekf_batch_update_scan / _augment_scan.
+//
+// All instances see the same landmarks, so the visibility filter (slam.h:575-683), range / bearing (slam.h:339-368) and
+// the known-association table (EKF.cpp:146-233) run ONCE per scan; only the sensor noise (slam.h:168-178) is per
+// instance, drawn on the device from the counter-based generator of conan_slam_amd/synth.py.  A scan is two launches on
+// the generator's own stream:
+//   sim_batch_scan_kernel   one workgroup: visible landmarks -> Z0 / tags (at most 32 are kept), then, in the same
+//                           workgroup and behind a barrier, the table split -> idf / route / counts and the table's new
+//                           entries.  The table is read and written by this launch alone, each entry by one thread.
+//   sim_batch_noise_kernel  one wave per instance, one lane per (scan position, component): the draw, the f32 noise
+//                           arithmetic, and the store into the instance's ZF or ZN column.  Reads Z0 / route / counts only.
+// Scans live in a ring of kSlots slots; a slot is rewritten only after the event recorded behind its last consumer (a
+// window or an augment of the batched engine) has completed.  The host learns the three counts through pinned memory.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "cslam_common.hpp"
+#include "device_math.hpp"
+#include "sim_kernels.hpp"
+#include "sim_scan_view.hpp"
+
+namespace cslam
+{
+namespace
+{
+
+constexpr int kSlots = 4;
+
+// per-slot device scratch common to the instances (ints and floats apart)
+struct SlotCommon
+{
+    float* Z0;    // [2 x 32] the noise-free scan
+    float* ZF0;   // [2 x 32] its known part (noise-free; written by the table split)
+    float* ZN0;   // [2 x 32] its new part
+    int*   tags;  // [32]
+    int*   idf;   // [32]
+    int*   route; // [32] scan position -> ZF column o (>= 0) or ZN column ~o (< 0)
+    int*   count; // [4]  m (all visible landmarks, may exceed 32), mf, mn
+};
+
+__global__ void __launch_bounds__(kSimThreads) sim_batch_scan_kernel(const float* __restrict__ LM, int nlm, float x, float y,
+                                                                       float phi, float rmax, int* __restrict__ table, int nf,
+                                                                       SlotCommon s)
+{
+    __shared__ int s_wave[kSimThreads / 64];
+    const int      m = sim_get_observations_body<float>(LM, nlm, x, y, phi, rmax, s.Z0, s.tags, kScanMaxObs, s_wave);
+    __syncthreads(); // (Z0 / tags are read back below by other threads of this workgroup)
+    int mf = 0, mn = 0;
+    if (m <= kScanMaxObs) // a scan beyond the cap leaves the table alone
+    {
+        sim_associate_table_body<float>(s.Z0, s.tags, m, table, nf, s.ZF0, s.idf, s.ZN0, s.route, s_wave, &mf, &mn);
+    }
+    if (threadIdx.x == 0)
+    {
+        s.count[0] = m;
+        s.count[1] = mf;
+        s.count[2] = mn;
+    }
+}
+
+// the counter-based standard normal of synth.py: splitmix64(seed, idx) -> 53-bit uniforms -> Box-Muller, in f64
+__device__ inline unsigned long long splitmix64(unsigned long long seed, unsigned long long idx)
+{
+    unsigned long long z = seed * 0x9E3779B97F4A7C15ull + idx + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ inline double uniform01(unsigned long long seed, unsigned long long idx)
+{
+    return (double)(splitmix64(seed, idx) >> 11) * (1.0 / 9007199254740992.0);
+}
+__device__ inline double counter_normal(unsigned long long seed, unsigned long long idx)
+{
+    const double u1 = uniform01(seed, 2ull * idx), u2 = uniform01(seed, 2ull * idx + 1ull);
+    return sqrt(-2.0 * log(1.0 - u1)) * cos((2.0 * kPi) * u2);
+}
+
+// slam.h:168-178: z0 + g * s with the product and the sum rounded separately, as the reference's f32 code rounds them
+// (the compiler's default contraction would fuse them into one multiply-add with a single rounding)
+__device__ inline float add_noise_f32(float z0, float g, float s)
+{
+#pragma clang fp contract(off)
+    const float t = g * s;
+    return z0 + t;
+}
+
+// slam.h:168-178 per instance.  grid = I workgroups of 64 lanes: lane = 2 c + r.  s0 / s1 = float(sqrt(R_rr)); noisy = 0
+// copies Z0.
+__global__ void __launch_bounds__(64) sim_batch_noise_kernel(SlotCommon s, const long long* __restrict__ seeds,
+                                                              unsigned long long key, int noisy, float s0, float s1,
+                                                              float* __restrict__ ZF, float* __restrict__ ZN)
+{
+    const int m = s.count[0];
+    const int i = blockIdx.x, e = threadIdx.x, c = e >> 1, r = e & 1;
+    if (m > kScanMaxObs || c >= m)
+    {
+        return;
+    }
+    float z = s.Z0[e];
+    if (noisy)
+    {
+        const double g = counter_normal((unsigned long long)seeds[i] + 1ull, key + (unsigned long long)e);
+        z              = add_noise_f32(z, (float)g, r ? s1 : s0);
+    }
+    const int rt = s.route[c]; // (|columns| < 32: m <= 32)
+    float*    d  = (rt >= 0) ? ZF + (size_t)i * kScanStride + 2 * rt : ZN + (size_t)i * kScanStride + 2 * (~rt);
+    d[r]         = z;
+}
+
+} // namespace
+} // namespace cslam
+
+using namespace cslam;
+
+struct cslam_sim_batch
+{
+    struct Slot
+    {
+        int        m = 0, mf = 0, mn = 0, nf = 0;
+        bool       updated = false, augmented = false, ev_used = false;
+        hipEvent_t ev = nullptr;
+    };
+
+    int         device = 0, nlm = 0, I = 0;
+    hipStream_t stream = nullptr;
+    float *     dLM = nullptr, *dF = nullptr; // dF: per slot 3 x 64 common floats, then ZF [I][64], ZN [I][64]
+    int *       dTable = nullptr, *dI = nullptr; // dI: per slot tags, idf, route (32 each), count (4)
+    long long*  dSeeds = nullptr;
+    const float** dZtab   = nullptr; // [kSlots][I], written once
+    const int**   dIdftab = nullptr;
+    int*        hCount = nullptr; // pinned, 4 ints
+    Slot        slot[kSlots];
+    int         cur = -1; // the current scan's slot, -1: none yet
+    int         nf  = 0;  // table entries assigned
+
+    size_t f_stride() const { return (size_t)3 * kScanStride + 2 * (size_t)I * kScanStride; }
+    static constexpr size_t i_stride() { return 3 * kScanMaxObs + 4; }
+
+    SlotCommon common(int k) const
+    {
+        float* f = dF + (size_t)k * f_stride();
+        int*   q = dI + (size_t)k * i_stride();
+        return SlotCommon{f, f + kScanStride, f + 2 * kScanStride, q, q + kScanMaxObs, q + 2 * kScanMaxObs, q + 3 * kScanMaxObs};
+    }
+    float* zf(int k) const { return dF + (size_t)k * f_stride() + 3 * kScanStride; }
+    float* zn(int k) const { return zf(k) + (size_t)I * kScanStride; }
+
+    ~cslam_sim_batch()
+    {
+        (void)hipSetDevice(device);
+        if (stream)
+        {
+            (void)hipStreamSynchronize(stream);
+        }
+        for (Slot& s : slot)
+        {
+            if (s.ev)
+            {
+                (void)hipEventSynchronize(s.ev); // (a consumer may still be reading the slot)
+                (void)hipEventDestroy(s.ev);
+            }
+        }
+        (void)hipFree(dLM);
+        (void)hipFree(dF);
+        (void)hipFree(dTable);
+        (void)hipFree(dI);
+        (void)hipFree(dSeeds);
+        (void)hipFree(dZtab);
+        (void)hipFree(dIdftab);
+        (void)hipHostFree(hCount);
+        if (stream)
+        {
+            (void)hipStreamDestroy(stream);
+        }
+    }
+
+    int init(const float* LM, const long long* seeds)
+    {
+        CSLAM_HIP_TRY(hipSetDevice(device));
+        CSLAM_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        const size_t cap = (size_t)std::max(nlm, 1);
+        CSLAM_HIP_TRY(hipMalloc(&dLM, 2 * cap * sizeof(float)));
+        CSLAM_HIP_TRY(hipMalloc(&dTable, cap * sizeof(int)));
+        CSLAM_HIP_TRY(hipMalloc(&dF, kSlots * f_stride() * sizeof(float)));
+        CSLAM_HIP_TRY(hipMalloc(&dI, kSlots * i_stride() * sizeof(int)));
+        CSLAM_HIP_TRY(hipMalloc(&dSeeds, (size_t)I * sizeof(long long)));
+        CSLAM_HIP_TRY(hipMalloc(&dZtab, (size_t)kSlots * I * sizeof(float*)));
+        CSLAM_HIP_TRY(hipMalloc(&dIdftab, (size_t)kSlots * I * sizeof(int*)));
+        CSLAM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hCount), 4 * sizeof(int), hipHostMallocDefault));
+        CSLAM_HIP_TRY(hipMemsetAsync(dTable, 0, cap * sizeof(int), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(dF, 0, kSlots * f_stride() * sizeof(float), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(dI, 0, kSlots * i_stride() * sizeof(int), stream));
+        if (nlm > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(dLM, LM, 2 * (size_t)nlm * sizeof(float), hipMemcpyHostToDevice, stream));
+        }
+        CSLAM_HIP_TRY(hipMemcpyAsync(dSeeds, seeds, (size_t)I * sizeof(long long), hipMemcpyHostToDevice, stream));
+        // the pointer tables of every slot, once: instance i's ZF column block and the common idf
+        std::vector<const float*> zt((size_t)kSlots * I);
+        std::vector<const int*>   it((size_t)kSlots * I);
+        for (int k = 0; k < kSlots; k++)
+        {
+            for (int i = 0; i < I; i++)
+            {
+                zt[(size_t)k * I + i] = zf(k) + (size_t)i * kScanStride;
+                it[(size_t)k * I + i] = common(k).idf;
+            }
+        }
+        CSLAM_HIP_TRY(hipMemcpyAsync(dZtab, zt.data(), zt.size() * sizeof(float*), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dIdftab, it.data(), it.size() * sizeof(int*), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        for (Slot& s : slot)
+        {
+            CSLAM_HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+        }
+        return CSLAM_OK;
+    }
+
+    int scan(const float* xv, double rmax, const float* R, long long step, int* m, int* mf, int* mn)
+    {
+        CSLAM_HIP_TRY(hipSetDevice(device));
+        const int k = (cur + 1) % kSlots;
+        Slot&     s = slot[k];
+        if (s.ev_used) // the last kernel that read this slot, kSlots - 1 scans ago
+        {
+            CSLAM_HIP_TRY(hipEventSynchronize(s.ev));
+            s.ev_used = false;
+        }
+        const SlotCommon c = common(k);
+        hipLaunchKernelGGL(sim_batch_scan_kernel, dim3(1), dim3(kSimThreads), 0, stream, dLM, nlm, xv[0], xv[1], xv[2], (float)rmax,
+                           dTable, nf, c);
+        CSLAM_HIP_TRY(hipGetLastError());
+        const float              s0 = R ? std::sqrt(R[0]) : 0.f, s1 = R ? std::sqrt(R[3]) : 0.f;
+        const unsigned long long key = (unsigned long long)(10000000ll + step) * 64ull;
+        hipLaunchKernelGGL(sim_batch_noise_kernel, dim3(I), dim3(64), 0, stream, c, dSeeds, key, R ? 1 : 0, s0, s1, zf(k), zn(k));
+        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_HIP_TRY(hipMemcpyAsync(hCount, c.count, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        if (hCount[0] > kScanMaxObs)
+        {
+            return fail(CSLAM_ERR_CAPACITY, "sim_batch_scan: %d visible landmarks exceed the %d observations of a batched update",
+                        hCount[0], kScanMaxObs);
+        }
+        s.m       = hCount[0];
+        s.mf      = hCount[1];
+        s.mn      = hCount[2];
+        s.nf      = nf;
+        s.updated = s.augmented = false;
+        nf += s.mn;
+        cur = k;
+        if (m) *m = s.m;
+        if (mf) *mf = s.mf;
+        if (mn) *mn = s.mn;
+        return CSLAM_OK;
+    }
+
+    int get_scan(int i, float* ZF, int* idf, float* ZN, int* tags)
+    {
+        CSLAM_HIP_TRY(hipSetDevice(device));
+        const Slot&      s = slot[cur];
+        const SlotCommon c = common(cur);
+        if (ZF && s.mf > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(ZF, zf(cur) + (size_t)i * kScanStride, 2 * (size_t)s.mf * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        if (idf && s.mf > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(idf, c.idf, (size_t)s.mf * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (ZN && s.mn > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(ZN, zn(cur) + (size_t)i * kScanStride, 2 * (size_t)s.mn * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        if (tags && s.m > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(tags, c.tags, (size_t)s.m * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+};
+
+namespace cslam
+{
+
+int sim_batch_current(cslam_sim_batch_t s, SimScanView* v)
+{
+    if (!s || s->cur < 0)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch: no current scan");
+    }
+    const cslam_sim_batch::Slot& k = s->slot[s->cur];
+    v->device    = s->device;
+    v->instances = s->I;
+    v->m         = k.m;
+    v->mf        = k.mf;
+    v->mn        = k.mn;
+    v->nf        = k.nf;
+    v->updated   = k.updated ? 1 : 0;
+    v->augmented = k.augmented ? 1 : 0;
+    v->Ztab      = s->dZtab + (size_t)s->cur * s->I;
+    v->idftab    = s->dIdftab + (size_t)s->cur * s->I;
+    v->ZN        = s->zn(s->cur);
+    v->consumed  = k.ev;
+    return CSLAM_OK;
+}
+
+int sim_batch_mark(cslam_sim_batch_t s, int what, bool recorded)
+{
+    if (!s || s->cur < 0)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch: no current scan");
+    }
+    cslam_sim_batch::Slot& k = s->slot[s->cur];
+    k.updated   = k.updated || (what & kScanUpdated);
+    k.augmented = k.augmented || (what & kScanAugmented);
+    k.ev_used   = k.ev_used || recorded;
+    return CSLAM_OK;
+}
+
+} // namespace cslam
+
+#define CSLAM_NEED_SIMB(h)                                           \
+    if (!(h))                                                        \
+    {                                                                \
+        return fail(CSLAM_ERR_BAD_ARG, "%s: null handle", __func__); \
+    }
+
+extern "C" {
+
+int cslam_sim_batch_create(const float* LM, int n_landmarks, int instances, const long long* seeds, int device,
+                           cslam_sim_batch_t* out)
+{
+    if (!out || n_landmarks < 0 || (n_landmarks > 0 && !LM) || instances < 1 || instances > 255 || !seeds)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch_create: bad arguments");
+    }
+    *out  = nullptr;
+    int c = 0;
+    if (hipGetDeviceCount(&c) != hipSuccess || c == 0)
+    {
+        return fail(CSLAM_ERR_NO_DEVICE, "sim_batch_create: no HIP device (this engine has no CPU fallback)");
+    }
+    if (device < 0 && hipGetDevice(&device) != hipSuccess)
+    {
+        device = 0;
+    }
+    if (device >= c)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch_create: device %d of %d", device, c);
+    }
+    cslam_sim_batch* b = new (std::nothrow) cslam_sim_batch();
+    if (!b)
+    {
+        return fail(CSLAM_ERR_ALLOC, "sim_batch_create: out of host memory");
+    }
+    b->device = device;
+    b->nlm    = n_landmarks;
+    b->I      = instances;
+    int rc    = b->init(LM, seeds);
+    if (rc)
+    {
+        delete b;
+        return rc;
+    }
+    *out = b;
+    return CSLAM_OK;
+}
+
+int cslam_sim_batch_destroy(cslam_sim_batch_t h)
+{
+    delete h;
+    return CSLAM_OK;
+}
+
+int cslam_sim_batch_scan(cslam_sim_batch_t h, const float* xv_true, double rmax, const float* R, long long step, int* m,
+                         int* mf, int* mn)
+{
+    CSLAM_NEED_SIMB(h);
+    if (!xv_true || step < 0)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch_scan: bad arguments");
+    }
+    return h->scan(xv_true, rmax, R, step, m, mf, mn);
+}
+
+int cslam_sim_batch_get_scan(cslam_sim_batch_t h, int instance, float* ZF, int* idf, float* ZN, int* tags)
+{
+    CSLAM_NEED_SIMB(h);
+    if (instance < 0 || instance >= h->I || h->cur < 0)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch_get_scan: instance %d of %d, or no scan yet", instance, h->I);
+    }
+    return h->get_scan(instance, ZF, idf, ZN, tags);
+}
+
+int cslam_sim_batch_get_table(cslam_sim_batch_t h, int* table)
+{
+    CSLAM_NEED_SIMB(h);
+    if (!table)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch_get_table: null");
+    }
+    CSLAM_HIP_TRY(hipSetDevice(h->device));
+    if (h->nlm > 0)
+    {
+        CSLAM_HIP_TRY(hipMemcpyAsync(table, h->dTable, (size_t)h->nlm * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    return CSLAM_OK;
+}
+
+int cslam_sim_batch_set_table(cslam_sim_batch_t h, const int* table)
+{
+    CSLAM_NEED_SIMB(h);
+    if (!table)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "sim_batch_set_table: null");
+    }
+    int top = 0;
+    for (int i = 0; i < h->nlm; i++)
+    {
+        if (table[i] < 0)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "sim_batch_set_table: entry %d is negative", i);
+        }
+        top = std::max(top, table[i]);
+    }
+    CSLAM_HIP_TRY(hipSetDevice(h->device));
+    if (h->nlm > 0)
+    {
+        CSLAM_HIP_TRY(hipMemcpyAsync(h->dTable, table, (size_t)h->nlm * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    }
+    h->nf = top;
+    return CSLAM_OK;
+}
+
+} // extern "C"

@@ -382,6 +382,18 @@ class EKFBatch:
         zs = (C.c_void_p * self.instances)(*[int(p) for p in dZn_ptrs])
         check(self._L.cslam_ekf_batch_augment(self._h, zs, C.c_int(q), _vp(R)))
 
+    def update_scan(self, sim, R):
+        """Slam::update(batch = true) on every instance with the current scan of a BatchSimulator: update_device with
+        that scan's ZF / idf, without a pointer table passing through the host.  mf = 0: nothing."""
+        R = np.asfortranarray(R, dtype=np.float32)
+        check(self._L.cslam_ekf_batch_update_scan(self._h, sim._h, _vp(R)))
+
+    def augment_scan(self, sim, R):
+        """Slam::augment on every instance with the new-feature part of a BatchSimulator's current scan (after
+        update_scan when the scan has known features).  mn = 0: nothing."""
+        R = np.asfortranarray(R, dtype=np.float32)
+        check(self._L.cslam_ekf_batch_augment_scan(self._h, sim._h, _vp(R)))
+
     def flush(self):
         check(self._L.cslam_ekf_batch_flush(self._h))
 

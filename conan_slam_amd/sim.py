@@ -4,6 +4,10 @@
     add_observation_noise   the driver's sensor noise     slam.h:168-178 (the N(0,1) draws are an input)
     data_associate_table    EKF::dataAssociateTable       EKF.cpp:146-233
 The map, the table, the scan and its split live in HBM; `device_ptrs()` feeds `EKF.update_device` without a host copy.
+
+`BatchSimulator` (cslam_sim_batch_*) is the generator for Monte-Carlo studies through `EKFBatch`: one scan per observation
+step for all instances, the sensor noise drawn on the device per instance, consumed by `EKFBatch.update_scan` /
+`augment_scan` without a device pointer passing through the caller.
 """
 import ctypes as C
 
@@ -91,3 +95,77 @@ class Simulator:
         if t.size != self.n_landmarks:
             raise ValueError("table size")
         check(self._L.cslam_sim_set_table(self._h, t.ctypes.data_as(C.POINTER(C.c_int))))
+
+
+class BatchSimulator:
+    """The sensor side of the reference's demo loop (test/main.cpp:139-165) for `instances` Monte-Carlo runs that share
+    the true trajectory and the map: visibility, range / bearing and the table association once per scan, the noise of
+    slam.h:168-178 per instance from the counter-based generator of synth.py, keyed
+    normal(seeds[i] + 1, (10_000_000 + step) * 64 + 2 c + r) for scan position c and component r.  f32."""
+
+    MAX_OBS = 32  # observations per scan: the batched update's limit
+
+    def __init__(self, LM, instances: int, seeds, device: int = -1):
+        self._L = _capi.lib()
+        self._h = C.c_void_p()
+        LM = np.asarray(LM, dtype=np.float32, order="F").reshape(2, -1, order="F")
+        seeds = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1)
+        if seeds.size != instances:
+            raise ValueError(f"BatchSimulator: {seeds.size} seeds for {instances} instances")
+        self.n_landmarks, self.instances = LM.shape[1], int(instances)
+        check(self._L.cslam_sim_batch_create(LM.ctypes.data_as(C.c_void_p), C.c_int(self.n_landmarks), C.c_int(self.instances),
+                                             seeds.ctypes.data_as(C.POINTER(C.c_longlong)), C.c_int(device),
+                                             C.byref(self._h)))
+        self.m = self.mf = self.mn = 0
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.cslam_sim_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def scan(self, xv_true, rmax, R, step: int):
+        """One observation step for all instances -> (m, mf, mn), common to the instances.  R = None: noise off.
+        More than 32 visible landmarks: CslamError(ERR_CAPACITY), the table and the current scan stay as they are."""
+        xv = np.ascontiguousarray(xv_true, dtype=np.float32).reshape(3)
+        Rp = None
+        if R is not None:
+            R = np.asfortranarray(R, dtype=np.float32)
+            Rp = R.ctypes.data_as(C.c_void_p)
+        m, mf, mn = C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._L.cslam_sim_batch_scan(self._h, xv.ctypes.data_as(C.c_void_p), C.c_double(float(rmax)), Rp,
+                                           C.c_longlong(int(step)), C.byref(m), C.byref(mf), C.byref(mn)))
+        self.m, self.mf, self.mn = m.value, mf.value, mn.value
+        return self.m, self.mf, self.mn
+
+    def get_scan(self, instance: int):
+        """-> (ZF 2 x mf, idf mf, ZN 2 x mn, tags m): host copies of the current scan as `instance` sees it."""
+        cap = self.MAX_OBS
+        ZF = np.zeros((2, cap), dtype=np.float32, order="F")
+        ZN = np.zeros((2, cap), dtype=np.float32, order="F")
+        idf = np.zeros(cap, dtype=np.int32)
+        tags = np.zeros(cap, dtype=np.int32)
+        check(self._L.cslam_sim_batch_get_scan(self._h, C.c_int(int(instance)), ZF.ctypes.data_as(C.c_void_p),
+                                               idf.ctypes.data_as(C.c_void_p), ZN.ctypes.data_as(C.c_void_p),
+                                               tags.ctypes.data_as(C.c_void_p)))
+        return (np.asfortranarray(ZF[:, :self.mf]), idf[:self.mf].copy(), np.asfortranarray(ZN[:, :self.mn]),
+                tags[:self.m].copy())
+
+    @property
+    def table(self):
+        t = np.zeros(max(self.n_landmarks, 1), dtype=np.int32)
+        check(self._L.cslam_sim_batch_get_table(self._h, t.ctypes.data_as(C.c_void_p)))
+        return t[:self.n_landmarks]
+
+    @table.setter
+    def table(self, value):
+        t = np.ascontiguousarray(value, dtype=np.int32)
+        if t.size != self.n_landmarks:
+            raise ValueError("table size")
+        t = np.concatenate([t, np.zeros(1, np.int32)])  # (never an empty buffer)
+        check(self._L.cslam_sim_batch_set_table(self._h, t.ctypes.data_as(C.c_void_p)))

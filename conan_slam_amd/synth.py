@@ -52,6 +52,27 @@ def noise_matrices(dtype=np.float32):
     return Q, R, (2 * Q).astype(dtype, order="F"), (8 * R).astype(dtype, order="F")
 
 
+def control_noise(seeds, step, v, swa, Q):
+    """The reference's noisy controls (slam.h:149-159) for Monte-Carlo instances, vectorised: instance i at control step
+    `step` (counted from 1) gets  vn = f32(v + f32(normal(seeds[i], 2 step)) * f32(sqrt(Q[0,0])))  and
+    swan = f32(swa + f32(normal(seeds[i], 2 step + 1)) * f32(sqrt(Q[1,1]))), every operation in f32 -- what
+    EKFBatch.predict_each wants.  step, v and swa may be scalars (-> vn[I], swan[I]) or arrays of S steps
+    (-> vn[S, I], swan[S, I])."""
+    f = np.float32
+    seeds = np.asarray(seeds, dtype=np.int64).reshape(-1)
+    scalar = np.ndim(step) == 0
+    st = np.atleast_1d(np.asarray(step, dtype=np.uint64))
+    vv = np.broadcast_to(np.asarray(v, dtype=f), st.shape)[:, None]
+    ss = np.broadcast_to(np.asarray(swa, dtype=f), st.shape)[:, None]
+    Q = np.asarray(Q, dtype=f)
+    s0, s1 = np.sqrt(Q[0, 0]), np.sqrt(Q[1, 1])  # (f32 square roots)
+    g0 = np.stack([normal(int(s), st * np.uint64(2)) for s in seeds], axis=1).astype(f)
+    g1 = np.stack([normal(int(s), st * np.uint64(2) + np.uint64(1)) for s in seeds], axis=1).astype(f)
+    vn = (vv + (g0 * s0).astype(f)).astype(f)
+    swan = (ss + (g1 * s1).astype(f)).astype(f)
+    return (vn[0], swan[0]) if scalar else (vn, swan)
+
+
 class Workload:
     """A synthetic map + initial filter state + a stream of (controls, observations) per step."""
 

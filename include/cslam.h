@@ -433,6 +433,48 @@ int cslam_sim_device_ptrs(cslam_sim_t h, const void** dZF, const int** dIdf, con
 int cslam_sim_get_table(cslam_sim_t h, int* table);
 int cslam_sim_set_table(cslam_sim_t h, const int* table);
 
+/* ------------------------------------------------------------------------------------------------
+ * Batched scan generator for Monte-Carlo studies through cslam_ekf_batch_* (f32): the sensor side of the reference's
+ * demo loop (test/main.cpp:139-165, 188-189) for `instances` runs that share the true trajectory and the map, hence the
+ * visible tags, the table association, idf, mf and mn; only the sensor noise differs.  One scan = one observation step
+ * for all instances, in two launches on a stream of the generator's own:
+ *   1. Slam::getObservations (slam.h:575-683, computeRangeBearing slam.h:339-368) and EKF::dataAssociateTable
+ *      (EKF.cpp:146-233) ONCE, with the arithmetic and ordering of cslam_sim_get_observations / _associate_table;
+ *   2. the sensor noise of slam.h:168-178 per instance i, scan position c (before the split) and component r (0 range,
+ *      1 bearing), every operation in f32:  Z_i[r][c] = Z0[r][c] + float(g) * float(sqrt(R[r][r])),  g = the counter-based
+ *      standard normal of conan_slam_amd/synth.py normal(seed, idx), evaluated in f64 on the device, with
+ *      seed = seeds[i] + 1 and idx = (10000000 + step) * 64 + 2 c + r; the value goes to instance i's ZF or ZN column
+ *      by the common split.  R == NULL: noise off (mSwitchSensorNoise = false), every instance gets Z0.
+ * A scan holds at most 32 observations (the batched update's limit; the stride 64 of the noise key holds exactly their
+ * draws): a pose that sees more returns CSLAM_ERR_CAPACITY and leaves the table and the current scan unchanged.
+ * The generator keeps nf, the number of state features its table has assigned, and a small ring of scan slots in HBM;
+ * a slot is rewritten only after the last kernel that consumed it has finished.  scan() waits only for its own two
+ * kernels (the three counts come back through pinned memory), never for filter work in flight, and may be called as soon
+ * as the previous scan has been consumed (there is one current scan: a new one replaces it, consumed or not, and the
+ * table has then advanced past it).  `step` is the control-step number, counted from 1.
+ *   create     LM: 2 x n_landmarks floats (host, column-major); seeds: one per instance; 1 <= instances <= 255.
+ *   get_scan   host copies of the current scan (tests): ZF 2 x mf, idf mf, ZN 2 x mn of `instance`, tags m; any may be NULL.
+ *   get_table / set_table  as cslam_sim_get_table / _set_table; set_table also sets nf to the highest position in it. */
+typedef struct cslam_sim_batch* cslam_sim_batch_t;
+int cslam_sim_batch_create(const float* LM, int n_landmarks, int instances, const long long* seeds, int device,
+                           cslam_sim_batch_t* out);
+int cslam_sim_batch_destroy(cslam_sim_batch_t h);
+int cslam_sim_batch_scan(cslam_sim_batch_t h, const float* xv_true, double rmax, const float* R, long long step, int* m,
+                         int* mf, int* mn);
+int cslam_sim_batch_get_scan(cslam_sim_batch_t h, int instance, float* ZF, int* idf, float* ZN, int* tags);
+int cslam_sim_batch_get_table(cslam_sim_batch_t h, int* table);
+int cslam_sim_batch_set_table(cslam_sim_batch_t h, const int* table);
+/* Slam::update(..., batch = true) (slam.h:938-943, EKF.cpp:93-129, test/main.cpp:188) on every instance with the
+ * generator's CURRENT scan: the queueing rules, kernels and rounding of cslam_ekf_batch_update with that scan's ZF / idf,
+ * without copying pointer tables (they are resident in the scan slot).  mf == 0 is a no-op.
+ * Slam::augment (slam.h:190-191, EKF.cpp:9-91, test/main.cpp:189) likewise, as cslam_ekf_batch_augment with the scan's
+ * ZN; mn == 0 is a no-op; CSLAM_ERR_CAPACITY beyond max_landmarks, with nothing changed.
+ * Each may be called at most once per scan, and when mf > 0 the update comes before the augment.  CSLAM_ERR_BAD_ARG, with
+ * nothing changed (state, queue, table, scan): different instance counts or devices, a batch whose feature count
+ * (n - 3) / 2 is not the nf the scan was split against, a scan consumed twice, the wrong order, no current scan. */
+int cslam_ekf_batch_update_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* R);
+int cslam_ekf_batch_augment_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* R);
+
 #ifdef __cplusplus
 }
 #endif

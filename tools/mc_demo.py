@@ -15,7 +15,14 @@ map RMSE and mean landmark NEES (e^T P_jj^-1 e per landmark, averaged over landm
 EKFBatch.landmarks(), which reads without applying the pending covariance downdate: scoring does not perturb the runs.
 The true landmark of each state feature is the demo map's landmark the association table gave it.
 
+--generator device needs none of the recorded filter runs for its inputs: the truth (poses, steering, observation
+steps) still comes from the harness helpers, the noisy controls from synth.control_noise, the scans from one
+BatchSimulator for all instances, consumed with EKFBatch.update_scan / augment_scan.  --placement says when the scan of
+an observation step is made: `late` right before it is consumed, `early` right after the previous scan was consumed
+(the table depends only on the sequence of scans), while that window is still running.
+
     python tools/mc_demo.py [--instances 8] [--steps 2400] [--seed 1000] [--quirks textbook|ref_exact]
+                            [--generator tape|device] [--placement late|early|both]
 """
 import argparse
 import json
@@ -182,6 +189,58 @@ def drive_batch(b, recs, dz, di, score=None):
     b.synchronize()
 
 
+def truth_script(LM, WP, steps):
+    """Per control step (true pose f32, steering angle, observes?): run_demo's truth side through the harness helpers."""
+    from pyoracle import Oracle
+    from sim_driver import SlamConfig
+
+    cfg = SlamConfig()
+    sim = Oracle(np.float32)
+    f = np.float32
+    XTrue = np.zeros(3, dtype=np.float32)
+    WPd = WP.astype(np.float32, order="F")
+    dt = cfg.dt_controls
+    iwp, swa, loops, dtsum, out = 1, f(0.0), float(cfg.number_loops), 0.0, []
+    while 0 < iwp <= WP.shape[1] and len(out) < steps:
+        iwp, swa = sim.compute_swa(XTrue, WPd, iwp, cfg.at_waypoint, swa, cfg.rate_swa, cfg.max_swa, f(dt), True)
+        if iwp == 0 and loops > 1:
+            iwp, loops = 1, loops - 1
+        sim.vehicle_model(XTrue, cfg.velocity, swa, cfg.wheel_base, f(dt))
+        dtsum += dt
+        observe = dtsum >= cfg.dt_observe
+        if observe:
+            dtsum = 0.0
+        out.append((XTrue.copy(), f(swa), observe))
+    return cfg, out
+
+
+def drive_device(b, gen, cfg, script, vn, swan, QE, R, RE, early=False, score=None):
+    """The demo loop with device-generated scans: predict_each / observe_heading per control step, scan -> update_scan ->
+    augment_scan per observation step.  early: the scan of the NEXT observation step is made right after this one's was
+    consumed.  Returns (observation steps, updates, largest scan)."""
+    wb, dt, rmax = float(cfg.wheel_base), float(np.float32(cfg.dt_controls)), float(cfg.max_range)
+    obs = [k for k, s in enumerate(script) if s[2]]
+    nxt = {a: c for a, c in zip(obs, obs[1:])}
+    made = None
+    n_obs = updates = max_m = 0
+    for k, (xv, swa, observe) in enumerate(script):
+        b.predict_each(vn[k], swan[k], QE, wb, dt)
+        b.observe_heading(float(xv[2]), True)
+        if not observe:
+            continue
+        m, mf, mn = made if made is not None else gen.scan(xv, rmax, R, k + 1)
+        made = None
+        b.update_scan(gen, RE)
+        b.augment_scan(gen, RE)
+        n_obs, updates, max_m = n_obs + 1, updates + (mf > 0), max(max_m, mf)
+        if score is not None and mn:
+            score(k + 1, b)
+        if early and k in nxt:
+            made = gen.scan(script[nxt[k]][0], rmax, R, nxt[k] + 1)
+    b.synchronize()
+    return n_obs, updates, max_m
+
+
 def drive_handles(hs, recs, dz, di):
     """Instance i's calls through handle i, one host thread per handle (the calls release the GIL)."""
 
@@ -215,9 +274,13 @@ def main():
     ap.add_argument("--steps", type=int, default=2400)
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--quirks", choices=["textbook", "ref_exact"], default="textbook")
+    ap.add_argument("--generator", choices=["tape", "device"], default="tape")
+    ap.add_argument("--placement", choices=["late", "early", "both"], default="both")
     args = ap.parse_args()
     quirks = Q_TEXTBOOK if args.quirks == "textbook" else Q_REF_EXACT
     I = args.instances
+    if args.generator == "device":
+        return main_device(args, quirks)
     recs, truth = record(I, args.seed, args.steps, quirks)
     steps = sum(1 for c in recs[0] if c[0] == "P")
     dz, di = pack(recs)
@@ -269,12 +332,87 @@ def main():
     drive_batch(b, recs, dz, di, score)
     b.close()
     print(json.dumps({
-        "workload": "mc_demo", "instances": I, "steps": steps, "quirks": args.quirks,
+        "workload": "mc_demo", "generator": "tape", "instances": I, "steps": steps, "quirks": args.quirks,
         "updates": sum(1 for c in recs[0] if c[0] == "U"),
         "max_m": max((c[1].shape[1] for c in recs[0] if c[0] == "U"), default=0),
         "batch_steps_per_s": round(steps / t_batch, 1),
         "handles_steps_per_s": round(steps / t_handles, 1),
         "speedup": round(t_handles / t_batch, 3),
+        "pose_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in err2],
+        "mean_nees": [round(float(np.nanmean(v)), 3) for v in nees],
+        "map_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in merr2],
+        "mean_landmark_nees": [round(float(np.nanmean(v)), 3) for v in mnees],
+        "factor_status": flags,
+    }))
+
+
+def main_device(args, quirks):
+    from sim_driver import load_demo_map
+
+    from conan_slam_amd import BatchSimulator
+    from conan_slam_amd.synth import control_noise, noise_matrices
+
+    I = args.instances
+    seeds = [args.seed + i for i in range(I)]
+    LM, WP = load_demo_map()
+    cfg, script = truth_script(LM, WP, args.steps)
+    steps = len(script)
+    Q, R, QE, RE = noise_matrices(np.float32)
+    vn, swan = control_noise(seeds, np.arange(1, steps + 1), cfg.velocity, np.array([s[1] for s in script], np.float32), Q)
+    vn, swan = vn.astype(np.float64), swan.astype(np.float64)
+
+    def run(early, score=None):
+        gen = BatchSimulator(LM, I, seeds)
+        b = EKFBatch(I, n_landmarks=0, max_landmarks=64, quirks=quirks)
+        t0 = time.perf_counter()
+        counts = drive_device(b, gen, cfg, script, vn, swan, QE, R, RE, early, score)
+        t = time.perf_counter() - t0
+        flags = b.factor_status()
+        b.close()
+        gen.close()
+        return t, counts, flags
+
+    # one untimed pass (code objects, allocations), then the timed passes, alternated
+    run(False)
+    times = {"late": [], "early": []}
+    for _ in range(3):
+        for p in (("late", "early") if args.placement == "both" else (args.placement,)):
+            t, counts, flags = run(p == "early")
+            times[p].append(t)
+    best = {p: min(v) for p, v in times.items() if v}
+    place = min(best, key=best.get)
+
+    truth = [s[0].astype(np.float64) for s in script]
+    lm_true = map_truth(args.steps)
+    err2, nees = [[] for _ in range(I)], [[] for _ in range(I)]
+    merr2, mnees = [[] for _ in range(I)], [[] for _ in range(I)]
+
+    def score(step, b):
+        x, pvv = b.poses()
+        for i in range(I):
+            e = x[i].astype(np.float64) - truth[step - 1]
+            e[2] = (e[2] + np.pi) % (2 * np.pi) - np.pi
+            err2[i].append(float(e[0] ** 2 + e[1] ** 2))
+            try:
+                nees[i].append(float(e @ np.linalg.solve(pvv[i].astype(np.float64), e)))
+            except np.linalg.LinAlgError:
+                nees[i].append(float("nan"))
+        xl, pll, _ = b.landmarks()
+        e = xl.astype(np.float64) - lm_true[None, : xl.shape[1]]
+        for i in range(I):
+            merr2[i].extend((e[i] ** 2).sum(axis=1).tolist())
+            try:
+                mnees[i].append(float(np.mean(np.einsum("ja,ja->j", e[i], np.linalg.solve(pll[i].astype(np.float64),
+                                                                                            e[i][:, :, None])[:, :, 0]))))
+            except np.linalg.LinAlgError:
+                mnees[i].append(float("nan"))
+
+    _, counts, flags = run(place == "early", score)
+    print(json.dumps({
+        "workload": "mc_demo", "generator": "device", "instances": I, "steps": steps, "quirks": args.quirks,
+        "updates": int(counts[1]), "max_m": int(counts[2]), "scans": int(counts[0]),
+        "batch_steps_per_s": round(steps / best[place], 1), "placement": place,
+        "steps_per_s_by_placement": {p: round(steps / t, 1) for p, t in best.items()},
         "pose_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in err2],
         "mean_nees": [round(float(np.nanmean(v)), 3) for v in nees],
         "map_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in merr2],
