@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "cslam_common.hpp"
+#include "device_owners.hpp"
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
 #include "ekf_landmark_kernels.hpp"
@@ -94,8 +95,10 @@ struct EkfBase
     int         gather_corr_wide = 1; // a pending batch panel (<= 64 columns) corrected for inside the gather kernel (env CSLAM_GATHER_WIDE)
     int         pgemm_wgs     = 0;  // > 0: cap on the persistent P-GEMM grid (cslam_ekf_set_pgemm_workgroups: co-running instances)
     int         lookahead     = -1; // look-ahead windows (ekf_lookahead.hpp): -1 where they pay, env CSLAM_LOOKAHEAD=1 / 0 forces
-    hipStream_t stream   = nullptr; // A: everything except the P-GEMM
-    hipStream_t stream_b = nullptr; // B: the P-GEMM (== stream when not pipelined)
+    // (the owners live in the base, so they are destroyed after every buffer and event of Ekf<T>)
+    Stream      stream_own, stream_b_own, stream_f_own;
+    hipStream_t stream   = nullptr; // A: everything except the P-GEMM (= stream_own.get())
+    hipStream_t stream_b = nullptr; // B: the P-GEMM (== stream when not pipelined, else stream_b_own.get())
     long long   la_windows = 0;     // look-ahead windows launched (cslam_ekf_lookahead_windows)
 
     virtual int init()                                                                        = 0;
@@ -124,54 +127,64 @@ struct EkfBase
 template <typename T>
 struct Ekf : EkfBase
 {
-    T*   dX = nullptr;
-    T*   dP = nullptr;
-    T*   dPv = nullptr; // pose stripe: columns 0..2 of P (always current; see p_get in ekf_kernels.hpp)
-    T*   dWv = nullptr; // pose rows of the last update's W1 (3 x kcap), saved by the pose downdate before it zeroes them
-    int* dPoseDone = nullptr; // ticket counters: [0] ekf_pose_step_kernel, [1] ekf_pose_downdate_kernel
-    int* dSign     = nullptr; // per region: wcap column signs (heading columns with S < 0), then [2*wcap + r] their count
-    T*   dLm       = nullptr; // landmark read outputs: 12 scalars per landmark of capacity (allocated by the first read)
+    DevBuf<T>   dX, dP;
+    DevBuf<T>   dPv;       // pose stripe: columns 0..2 of P (always current; see p_get in ekf_kernels.hpp)
+    DevBuf<int> dPoseDone; // ticket counters: [0] ekf_pose_step_kernel, [1] ekf_pose_downdate_kernel
+    DevBuf<int> dSign;     // per region: wcap column signs (heading columns with S < 0), then [2*wcap + r] their count
+    DevBuf<T>   dLm;       // landmark read outputs: 12 scalars per landmark of capacity (allocated by the first read)
     int  hd_cols[2] = {0, 0}; // heading columns appended to each region since it became the pending store
     // the pending W1 store is two regions of wcap columns: `wcur` collects pending columns, the other one may still be
     // read by a P-GEMM in flight on stream B
     int        wcur = 0;
     unsigned   inflight_mask = 0; // regions an unfinished P-GEMM reads (cleared when stream A has waited for it)
-    hipEvent_t ev_a2b = nullptr, ev_pgemm = nullptr;
+    Event      ev_a2b, ev_pgemm;
     T*         last_slot = nullptr; // W1 of the last update
-    // update workspace
-    int  kcap  = 0;
-    T*   dPHT  = nullptr;
-    T*   dW1   = nullptr; // pending W1 panels, two regions of ldp x wcap
-    T*   dY    = nullptr; // Y = H*Wp (kcap x wcap), correction of PHT under pending panels
-    int  wcap  = 0;       // columns per region of dW1
-    int  kp    = 0;       // pending columns (downdates not applied to P yet)
-    int  defer_max = 0;   // > 0: keep up to this many pending columns across calls (cslam_ekf_set_deferred)
-    T*   dS    = nullptr;
-    T*   dG    = nullptr;
-    T*   dSub  = nullptr; // (3 + 64) x 64 compact block of PHT (see ekf_gather_kernel)
-    T*   dM    = nullptr; // 3 x 64: M = G G^T PHT[0:3,:]^T from ekf_factor_mfma_f32 (pose-stripe downdate in the gain kernel)
+    // update workspace for batches of up to kcap rows of H: one set, replaced as a whole by ensure_k
+    struct Workspace
+    {
+        DevBuf<T> dPHT, dS, dG, dGt, dV, dt_, dScrS, dScrG;
+        DevBuf<T> dSub; // (3 + 64) x 64 compact block of PHT (see ekf_gather_kernel)
+        DevBuf<T> dM;   // 3 x 64: M = G G^T PHT[0:3,:]^T from ekf_factor_mfma_f32 (pose-stripe downdate in the gain kernel)
+        DevBuf<T> dU;   // u = G*(G^T V), the gain kernel's X update vector
+        DevBuf<T> dWv;  // pose rows of the last update's W1 (3 x kcap), saved by the pose downdate before it zeroes them
+        DevBuf<T> dY;   // Y = H*Wp (kcap x wcap), correction of PHT under pending panels (ensure_w replaces it alone)
+
+        int alloc(int ldp, int newk, int wcap, hipStream_t st)
+        {
+            const size_t kk = (size_t)newk * (newk + 1);
+            int          rc = dPHT.alloc_zeroed((size_t)ldp * newk, st);
+            if (rc || (rc = dS.alloc(kk)) || (rc = dG.alloc(kk)) || (rc = dSub.alloc((size_t)(3 + 64) * 64)) ||
+                (rc = dM.alloc((size_t)3 * 128)) || (rc = dGt.alloc(kk)) || (rc = dScrS.alloc(kk)) ||
+                (rc = dScrG.alloc(kk)) || (rc = dV.alloc((size_t)newk)) || (rc = dt_.alloc((size_t)newk)) ||
+                (rc = dU.alloc((size_t)newk)) || (rc = dWv.alloc_zeroed((size_t)3 * newk, st)) || (wcap > 0 &&
+                (rc = dY.alloc((size_t)newk * wcap))))
+            {
+                return rc;
+            }
+            return CSLAM_OK;
+        }
+    };
+    Workspace ws;
+    int       kcap = 0;
+    DevBuf<T> dW1;      // pending W1 panels, two regions of ldp x wcap
+    int       wcap = 0; // columns per region of dW1
+    int       kp   = 0; // pending columns (downdates not applied to P yet)
+    int       defer_max = 0; // > 0: keep up to this many pending columns across calls (cslam_ekf_set_deferred)
     bool m_valid = false; // the last factor launch produced dM
     bool g_from_gt  = false; // the last factor launch wrote only G^T (ekf_factor_mfma_f32): debug transposes it
     bool sub_valid = false;
-    T*   dGt   = nullptr;
-    T*   dV    = nullptr;
-    T*   dt_   = nullptr;
-    T*   dU    = nullptr; // u = G*(G^T V), the gain kernel's X update vector
-    T*   dScrS = nullptr;
-    T*   dScrG = nullptr;
-    int* dFlags = nullptr; // [0] sticky, [1] last
-    int* hFlags = nullptr; // pinned mirror
+    DevBuf<int>    dFlags; // [0] sticky, [1] last
+    PinnedBuf<int> hFlags; // pinned mirror
     // heading scratch: w, cp2, rrow (ldp each) + 2 scalars
-    T* dHead = nullptr;
+    DevBuf<T> dHead;
     // observation staging: pinned host ring + one device buffer
     int         mcap   = 0;
-    void*       hStage = nullptr;
-    void*       dStage = nullptr;
-    hipEvent_t  stage_ev[kStagingSlots];
-    bool        stage_ev_used[kStagingSlots];
+    PinnedBuf<unsigned char> hStage;
+    DevBuf<unsigned char>    dStage;
+    Event                    stage_ev[kStagingSlots]; // created by the first call that takes the slot, recorded by every one
     int         stage_next = 0;
     // tile list of the persistent symmetric downdate
-    int*       dTicket     = nullptr; // two tile-ticket counters used alternately by successive P-GEMM launches
+    DevBuf<int> dTicket; // two tile-ticket counters used alternately by successive P-GEMM launches
     // f32 P-GEMM on the bf16 matrix cores (ekf_pgemm_limbs.hpp): limb pairs per product (9 exact, 6, 0 = the f32 MFMA
     // kernel; env CSLAM_PGEMM_LIMBS), from how many columns on (env CSLAM_LIMBS_KMIN), the limb store and its size.
     // Off by default: correct and as accurate as the f32 MFMA kernel (tests), but measured no faster -- 120 - 132 us
@@ -183,16 +196,16 @@ struct Ekf : EkfBase
     // 0 - 4 % slower (profiles/r02_pmc_xcd_queues.txt)
     int        xcd_queues  = 0;
     int        limbs_kmin  = 65;
-    uint4*     dWb         = nullptr;
-    size_t     wb_bytes    = 0;
-    int2*      dTilesM     = nullptr; // the tile list in Morton order, cut into eight segments (one per XCD) ...
-    int*       dSegOff     = nullptr; // ... at these offsets (9), and two sets of eight ticket counters
-    int*       dTicketX    = nullptr;
+    DevBuf<uint4> dWb;
+    size_t        wb_bytes = 0;
+    DevBuf<int2>  dTilesM;  // the tile list in Morton order, cut into eight segments (one per XCD) ...
+    DevBuf<int>   dSegOff;  // ... at these offsets (9), and two sets of eight ticket counters
+    DevBuf<int>   dTicketX;
     int        tilesM_built = 0;
     int        limb_parity = 0;
     unsigned   launch_parity = 0;
     int        psym_nt = -1; // CSLAM_PSYM_NT=0|1: non-temporal P accesses in the P-GEMM (-1: by footprint)
-    int2* dTiles      = nullptr;
+    DevBuf<int2> dTiles;
     int   tiles_built = 0;
     int   n_sym_tiles = 0;
     int   num_cus     = 256;
@@ -204,12 +217,13 @@ struct Ekf : EkfBase
     int                     profiling = 0;
     unsigned                prof_count = 0;
     bool                    prof_sampled = false;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event>      ev_pool;
     std::vector<int>        ev_stage; // stage id of interval [2i, 2i+1]
     size_t                  ev_used = 0;
 
     ~Ekf() override
     {
+        (void)hipSetDevice(device);
         if (stream)
         {
             (void)hipStreamSynchronize(stream);
@@ -221,97 +235,15 @@ struct Ekf : EkfBase
         if (stream_f)
         {
             (void)hipStreamSynchronize(stream_f);
-            (void)hipEventDestroy(ev_fb);
-            (void)hipEventDestroy(ev_raw);
-            (void)hipStreamDestroy(stream_f);
-        }
-        la_free();
-        if (ev_a2b)
-        {
-            (void)hipEventDestroy(ev_a2b);
-        }
-        if (ev_pgemm)
-        {
-            (void)hipEventDestroy(ev_pgemm);
-        }
-        for (hipEvent_t e : ev_pool)
-        {
-            (void)hipEventDestroy(e);
-        }
-        for (int i = 0; i < kStagingSlots; i++)
-        {
-            if (stage_ev_used[i])
-            {
-                (void)hipEventDestroy(stage_ev[i]);
-            }
-        }
-        (void)hipFree(dX);
-        (void)hipFree(dP);
-        (void)hipFree(dPv);
-        (void)hipFree(dWv);
-        (void)hipFree(dPoseDone);
-        (void)hipFree(dSign);
-        (void)hipFree(dLm);
-        free_workspace();
-        (void)hipFree(dFlags);
-        (void)hipFree(dHead);
-        (void)hipFree(dTicket);
-        (void)hipFree(dWb);
-        (void)hipFree(dTilesM);
-        (void)hipFree(dSegOff);
-        (void)hipFree(dTicketX);
-        (void)hipFree(dPred);
-        (void)hipFree(dAssoc);
-        (void)hipFree(dAssocOut);
-        (void)hipFree(dW1);
-        (void)hipFree(dY);
-        (void)hipFree(dTiles);
-        (void)hipFree(dStage);
-        if (hStage)
-        {
-            (void)hipHostFree(hStage);
-        }
-        if (hFlags)
-        {
-            (void)hipHostFree(hFlags);
-        }
-        if (stream_b && stream_b != stream)
-        {
-            (void)hipStreamDestroy(stream_b);
-        }
-        if (stream)
-        {
-            (void)hipStreamDestroy(stream);
         }
     }
 
-    T* wbase(int region) const { return dW1 + (size_t)region * wcap * ldp; }
-
-    void free_workspace()
-    {
-        (void)hipFree(dPHT);
-        (void)hipFree(dS);
-        (void)hipFree(dG);
-        (void)hipFree(dSub);
-        (void)hipFree(dM);
-        dM = nullptr;
-        (void)hipFree(dGt);
-        (void)hipFree(dV);
-        (void)hipFree(dt_);
-        (void)hipFree(dU);
-        (void)hipFree(dScrS);
-        (void)hipFree(dScrG);
-        dPHT = dS = dG = dSub = dGt = dV = dt_ = dU = dScrS = dScrG = nullptr;
-    }
+    T* wbase(int region) const { return dW1.get() + (size_t)region * wcap * ldp; }
 
     int use_device() { CSLAM_HIP_TRY(hipSetDevice(device)); return CSLAM_OK; }
 
     int init() override
     {
-        for (int i = 0; i < kStagingSlots; i++)
-        {
-            stage_ev_used[i] = false;
-        }
         int rc = use_device();
         if (rc)
         {
@@ -334,35 +266,35 @@ struct Ekf : EkfBase
             // the chain (A) outranks the P-GEMM (B): its small kernels must get in while the P-GEMM fills the chip
             int lo = 0, hi = 0;
             CSLAM_HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            CSLAM_HIP_TRY(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, hi));
-            CSLAM_HIP_TRY(hipStreamCreateWithPriority(&stream_b, hipStreamNonBlocking, lo));
+            if ((rc = stream_own.create_with_priority(hipStreamNonBlocking, hi)) ||
+                (rc = stream_b_own.create_with_priority(hipStreamNonBlocking, lo)))
+            {
+                return rc;
+            }
+            stream   = stream_own.get();
+            stream_b = stream_b_own.get();
         }
         else
         {
-            CSLAM_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            stream_b = stream;
+            CSLAM_TRY(stream_own.create(hipStreamNonBlocking));
+            stream = stream_b = stream_own.get();
         }
-        CSLAM_HIP_TRY(hipEventCreateWithFlags(&ev_a2b, hipEventDisableTiming));
-        CSLAM_HIP_TRY(hipEventCreateWithFlags(&ev_pgemm, hipEventDisableTiming));
+        if ((rc = ev_a2b.create(hipEventDisableTiming)) || (rc = ev_pgemm.create(hipEventDisableTiming)))
+        {
+            return rc;
+        }
         {
             hipDeviceProp_t prop;
             CSLAM_HIP_TRY(hipGetDeviceProperties(&prop, device));
             num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
         }
-        size_t pbytes = (size_t)ldp * ldp * sizeof(T);
-        CSLAM_HIP_TRY(hipMalloc(&dX, (size_t)ldp * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dP, pbytes));
-        CSLAM_HIP_TRY(hipMemsetAsync(dX, 0, (size_t)ldp * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dP, 0, pbytes, stream));
-        CSLAM_HIP_TRY(hipMalloc(&dPv, (size_t)3 * ldp * sizeof(T)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPv, 0, (size_t)3 * ldp * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMalloc(&dPoseDone, 4 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPoseDone, 0, 4 * sizeof(int), stream));
-        CSLAM_HIP_TRY(hipMalloc(&dFlags, 2 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dFlags, 0, 2 * sizeof(int), stream));
-        CSLAM_HIP_TRY(hipHostMalloc(&hFlags, 2 * sizeof(int), hipHostMallocDefault));
-        CSLAM_HIP_TRY(hipMalloc(&dHead, ((size_t)3 * ldp + 2) * sizeof(T)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dHead, 0, ((size_t)3 * ldp + 2) * sizeof(T), stream));
+        if ((rc = dX.alloc_zeroed((size_t)ldp, stream)) || (rc = dP.alloc_zeroed((size_t)ldp * ldp, stream)) ||
+            (rc = dPv.alloc_zeroed((size_t)3 * ldp, stream)) || (rc = dPoseDone.alloc_zeroed(4, stream)) ||
+            (rc = dFlags.alloc_zeroed(2, stream)) || (rc = hFlags.alloc(2)) ||
+            (rc = dHead.alloc_zeroed((size_t)3 * ldp + 2, stream)))
+        {
+            return rc;
+        }
         // allow the factor kernel its large dynamic LDS
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_kernel<T>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -382,8 +314,7 @@ struct Ekf : EkfBase
             CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_downdate_f64<2>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
-        CSLAM_HIP_TRY(hipMalloc(&dTicket, 2 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dTicket, 0, 2 * sizeof(int), stream));
+        CSLAM_TRY(dTicket.alloc_zeroed(2, stream));
         if (const char* sv = getenv("CSLAM_LA_K64"))
         {
             la_k64 = atoi(sv) ? 1 : 0;
@@ -424,38 +355,10 @@ struct Ekf : EkfBase
         }
         int newk = round_up(std::max(k, 2 * kcap), 8);
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        free_workspace();
-        size_t pan = (size_t)ldp * newk * sizeof(T);
-        size_t kk  = (size_t)newk * (newk + 1) * sizeof(T);
-        CSLAM_HIP_TRY(hipMalloc(&dPHT, pan));
-        CSLAM_HIP_TRY(hipMalloc(&dS, kk));
-        CSLAM_HIP_TRY(hipMalloc(&dG, kk));
-        if (dSub == nullptr)
-        {
-            CSLAM_HIP_TRY(hipMalloc(&dSub, (size_t)(3 + 64) * 64 * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dM, (size_t)3 * 128 * sizeof(T)));
-        }
-        CSLAM_HIP_TRY(hipMalloc(&dGt, kk));
-        CSLAM_HIP_TRY(hipMalloc(&dScrS, kk));
-        CSLAM_HIP_TRY(hipMalloc(&dScrG, kk));
-        CSLAM_HIP_TRY(hipMalloc(&dV, (size_t)newk * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dt_, (size_t)newk * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dU, (size_t)newk * sizeof(T)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPHT, 0, pan, stream));
-        (void)hipFree(dWv);
-        dWv = nullptr;
-        CSLAM_HIP_TRY(hipMalloc(&dWv, (size_t)3 * newk * sizeof(T)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dWv, 0, (size_t)3 * newk * sizeof(T), stream));
+        Workspace nw;
+        CSLAM_TRY(nw.alloc(ldp, newk, wcap, stream));
+        ws   = std::move(nw);
         kcap = newk;
-        if (dY)
-        {
-            (void)hipFree(dY);
-            dY = nullptr;
-        }
-        if (wcap > 0)
-        {
-            CSLAM_HIP_TRY(hipMalloc(&dY, (size_t)kcap * wcap * sizeof(T)));
-        }
         return CSLAM_OK;
     }
 
@@ -473,17 +376,16 @@ struct Ekf : EkfBase
             return rc;
         }
         int neww = round_up(std::max(cols, 2 * wcap), 8);
-        (void)hipFree(dW1);
-        (void)hipFree(dY);
-        dW1 = nullptr;
-        dY  = nullptr;
-        CSLAM_HIP_TRY(hipMalloc(&dW1, (size_t)2 * ldp * neww * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dY, (size_t)std::max(kcap, 8) * neww * sizeof(T)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dW1, 0, (size_t)2 * ldp * neww * sizeof(T), stream));
-        (void)hipFree(dSign);
-        dSign = nullptr;
-        CSLAM_HIP_TRY(hipMalloc(&dSign, ((size_t)2 * neww + 2) * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dSign, 0, ((size_t)2 * neww + 2) * sizeof(int), stream));
+        DevBuf<T>   w1, y;
+        DevBuf<int> sign;
+        if ((rc = w1.alloc_zeroed((size_t)2 * ldp * neww, stream)) || (rc = y.alloc((size_t)std::max(kcap, 8) * neww)) ||
+            (rc = sign.alloc_zeroed((size_t)2 * neww + 2, stream)))
+        {
+            return rc;
+        }
+        dW1   = std::move(w1);
+        ws.dY = std::move(y);
+        dSign = std::move(sign);
         hd_cols[0] = hd_cols[1] = 0;
         wcap      = neww;
         wcur      = 0;
@@ -517,7 +419,7 @@ struct Ekf : EkfBase
     {
         if (inflight_mask != 0 && stream_b != stream)
         {
-            CSLAM_HIP_TRY(hipStreamWaitEvent(stream, ev_pgemm, 0));
+            CSLAM_HIP_TRY(hipStreamWaitEvent(stream, ev_pgemm.get(), 0));
         }
         inflight_mask = 0;
         return CSLAM_OK;
@@ -557,8 +459,8 @@ struct Ekf : EkfBase
         }
         if (stream_b != stream)
         {
-            CSLAM_HIP_TRY(hipEventRecord(ev_a2b, stream));
-            CSLAM_HIP_TRY(hipStreamWaitEvent(stream_b, ev_a2b, 0));
+            CSLAM_HIP_TRY(hipEventRecord(ev_a2b.get(), stream));
+            CSLAM_HIP_TRY(hipStreamWaitEvent(stream_b, ev_a2b.get(), 0));
         }
         if (hd_cols[wcur] > 0) // exceptional heading columns (S < 0) enter with the opposite sign: exits at once otherwise
         {
@@ -574,7 +476,7 @@ struct Ekf : EkfBase
         }
         if (stream_b != stream)
         {
-            CSLAM_HIP_TRY(hipEventRecord(ev_pgemm, stream_b));
+            CSLAM_HIP_TRY(hipEventRecord(ev_pgemm.get(), stream_b));
             inflight_mask |= 1u << wcur;
         }
         wcur ^= 1;
@@ -588,8 +490,8 @@ struct Ekf : EkfBase
         {
             if (stream_b != stream) // (single stream: ekf_negcol_fix_kernel clears them itself when it had work)
             {
-                CSLAM_HIP_TRY(hipMemsetAsync(dSign + (size_t)wcur * wcap, 0, (size_t)wcap * sizeof(int), stream));
-                CSLAM_HIP_TRY(hipMemsetAsync(dSign + (size_t)2 * wcap + wcur, 0, sizeof(int), stream));
+                CSLAM_HIP_TRY(hipMemsetAsync(dSign.get() + (size_t)wcur * wcap, 0, (size_t)wcap * sizeof(int), stream));
+                CSLAM_HIP_TRY(hipMemsetAsync(dSign.get() + (size_t)2 * wcap + wcur, 0, sizeof(int), stream));
             }
             hd_cols[wcur] = 0;
         }
@@ -634,17 +536,21 @@ struct Ekf : EkfBase
             off[sgi] = (int)((size_t)hl.size() * sgi / 8);
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(dTilesM);
-        dTilesM = nullptr;
-        CSLAM_HIP_TRY(hipMalloc(&dTilesM, hl.size() * sizeof(int2)));
-        CSLAM_HIP_TRY(hipMemcpy(dTilesM, hl.data(), hl.size() * sizeof(int2), hipMemcpyHostToDevice));
-        if (dSegOff == nullptr)
+        DevBuf<int2> list;
+        DevBuf<int>  seg, ticket;
+        int          rc = list.alloc(hl.size());
+        if (rc || (!dSegOff.get() && ((rc = seg.alloc(9)) || (rc = ticket.alloc_zeroed_blocking(16)))))
         {
-            CSLAM_HIP_TRY(hipMalloc(&dSegOff, 9 * sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dTicketX, 16 * sizeof(int)));
-            CSLAM_HIP_TRY(hipMemset(dTicketX, 0, 16 * sizeof(int)));
+            return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpy(dSegOff, off, sizeof(off), hipMemcpyHostToDevice));
+        dTilesM = std::move(list);
+        if (!dSegOff.get())
+        {
+            dSegOff  = std::move(seg);
+            dTicketX = std::move(ticket);
+        }
+        CSLAM_HIP_TRY(hipMemcpy(dTilesM.get(), hl.data(), hl.size() * sizeof(int2), hipMemcpyHostToDevice));
+        CSLAM_HIP_TRY(hipMemcpy(dSegOff.get(), off, sizeof(off), hipMemcpyHostToDevice));
         tilesM_built = tiles;
         return CSLAM_OK;
     }
@@ -669,9 +575,10 @@ struct Ekf : EkfBase
             return rc;
         }
         const int nt = lower ? n_sym_tiles : tiles * tiles;
-        hipLaunchKernelGGL(ekf_negcol_fix_kernel<T>, dim3(std::min(nt, 2 * num_cus)), dim3(256), 0, st, dP, ldp, n, W, ldp,
-                           kcols, dSign + (size_t)wcur * wcap, dSign + (size_t)2 * wcap + wcur,
-                           lower ? dTiles : (const int2*)nullptr, nt, tiles, dPoseDone + 2, (stream_b == stream) ? 1 : 0);
+        hipLaunchKernelGGL(ekf_negcol_fix_kernel<T>, dim3(std::min(nt, 2 * num_cus)), dim3(256), 0, st, dP.get(), ldp,
+                           n, W, ldp, kcols, dSign.get() + (size_t)wcur * wcap, dSign.get() + (size_t)2 * wcap + wcur,
+                           lower ? dTiles.get() : (const int2*)nullptr, nt, tiles, dPoseDone.get() + 2,
+                           (stream_b == stream) ? 1 : 0);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -701,17 +608,17 @@ struct Ekf : EkfBase
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream_f));
         }
-        if (hStage)
-        {
-            (void)hipHostFree(hStage);
-            hStage = nullptr;
-        }
-        (void)hipFree(dStage);
-        dStage = nullptr;
-        CSLAM_HIP_TRY(hipHostMalloc(&hStage, slot_bytes(newm) * kStagingSlots, hipHostMallocDefault));
         // (a device slot per host slot: queued look-ahead updates read their inputs up to two calls later; a slot comes round
         // again kStagingSlots calls later, stream-ordered behind every kernel that read it)
-        CSLAM_HIP_TRY(hipMalloc(&dStage, slot_bytes(newm) * kStagingSlots));
+        PinnedBuf<unsigned char> hs;
+        DevBuf<unsigned char>    ds;
+        int                      rc = hs.alloc(slot_bytes(newm) * kStagingSlots);
+        if (rc || (rc = ds.alloc(slot_bytes(newm) * kStagingSlots)))
+        {
+            return rc;
+        }
+        hStage = std::move(hs);
+        dStage = std::move(ds);
         mcap = newm;
         return CSLAM_OK;
     }
@@ -727,17 +634,16 @@ struct Ekf : EkfBase
         }
         int slot = stage_next;
         stage_next = (stage_next + 1) % kStagingSlots;
-        if (stage_ev_used[slot])
+        if (stage_ev[slot])
         {
-            CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[slot]));
+            CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[slot].get()));
         }
-        else
+        else if ((rc = stage_ev[slot].create(hipEventDisableTiming)))
         {
-            CSLAM_HIP_TRY(hipEventCreateWithFlags(&stage_ev[slot], hipEventDisableTiming));
-            stage_ev_used[slot] = true;
+            return rc;
         }
         size_t         zb = (size_t)m * 2 * sizeof(T);
-        unsigned char* ds = static_cast<unsigned char*>(dStage) + slot_bytes(mcap) * slot;
+        unsigned char* ds = dStage.get() + slot_bytes(mcap) * slot;
         if (on_device)
         {
             hipLaunchKernelGGL(ekf_stage_obs_kernel<T>, dim3((3 * m + 255) / 256), dim3(256), 0, stream,
@@ -746,12 +652,12 @@ struct Ekf : EkfBase
         }
         else
         {
-            unsigned char* hs = static_cast<unsigned char*>(hStage) + slot_bytes(mcap) * slot;
+            unsigned char* hs = hStage.get() + slot_bytes(mcap) * slot;
             memcpy(hs, Z, zb);
             memcpy(hs + zb, idf, (size_t)m * sizeof(int));
             CSLAM_HIP_TRY(hipMemcpyAsync(ds, hs, zb + (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
         }
-        CSLAM_HIP_TRY(hipEventRecord(stage_ev[slot], stream));
+        CSLAM_HIP_TRY(hipEventRecord(stage_ev[slot].get(), stream));
         *dZ   = reinterpret_cast<const T*>(ds);
         *dIdf = reinterpret_cast<const int*>(ds + zb);
         return CSLAM_OK;
@@ -769,19 +675,20 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dX, X, (size_t)nn * sizeof(T), hipMemcpyHostToDevice, stream));
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(dP, (size_t)ldp * sizeof(T), P, (size_t)ldph * sizeof(T), (size_t)nn * sizeof(T),
-                                       (size_t)nn, hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dX.get(), X, (size_t)nn * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(dP.get(), (size_t)ldp * sizeof(T), P, (size_t)ldph * sizeof(T),
+                                       (size_t)nn * sizeof(T), (size_t)nn, hipMemcpyHostToDevice, stream));
         // the pose stripe = columns 0..2 of P (contiguous in the column-major buffer)
-        CSLAM_HIP_TRY(hipMemcpyAsync(dPv, dP, (size_t)3 * ldp * sizeof(T), hipMemcpyDeviceToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dPv.get(), dP.get(), (size_t)3 * ldp * sizeof(T), hipMemcpyDeviceToDevice,
+                                     stream));
         // panels: rows beyond the new n must read as zero (the tuned gain kernel relies on it)
         kp        = 0; // a new state discards updates that were never applied
         wcur      = 0;
         last_slot = nullptr;
         hd_cols[0] = hd_cols[1] = 0;
-        CSLAM_HIP_TRY(hipMemsetAsync(dSign, 0, ((size_t)2 * wcap + 2) * sizeof(int), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPHT, 0, (size_t)ldp * kcap * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dW1, 0, (size_t)2 * ldp * wcap * sizeof(T), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(dSign.get(), 0, ((size_t)2 * wcap + 2) * sizeof(int), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(ws.dPHT.get(), 0, (size_t)ldp * kcap * sizeof(T), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(dW1.get(), 0, (size_t)2 * ldp * wcap * sizeof(T), stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         n = nn;
         return CSLAM_OK;
@@ -804,20 +711,21 @@ struct Ekf : EkfBase
         }
         if (X)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(X, dX, (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(X, dX.get(), (size_t)n * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         if (P)
         {
             if (lower)
             {
                 const int g = (n + 31) / 32;
-                hipLaunchKernelGGL(ekf_mirror_upper_kernel<T>, dim3(g, g), dim3(256), 0, stream, dP, ldp, n);
+                hipLaunchKernelGGL(ekf_mirror_upper_kernel<T>, dim3(g, g), dim3(256), 0, stream, dP.get(), ldp, n);
                 CSLAM_HIP_TRY(hipGetLastError());
             }
             // rows / columns 0..2 of the buffer come from the pose stripe
-            hipLaunchKernelGGL(ekf_patch_pose_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, dP, dPv, ldp, n);
+            hipLaunchKernelGGL(ekf_patch_pose_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, dP.get(),
+                               dPv.get(), ldp, n);
             CSLAM_HIP_TRY(hipGetLastError());
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(P, (size_t)ldph * sizeof(T), dP, (size_t)ldp * sizeof(T),
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(P, (size_t)ldph * sizeof(T), dP.get(), (size_t)ldp * sizeof(T),
                                            (size_t)n * sizeof(T), (size_t)n, hipMemcpyDeviceToHost, stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
@@ -844,16 +752,16 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        if (dLm == nullptr)
+        if (!dLm.get() && (rc = dLm.alloc((size_t)std::max(nmax, 1) * 12)))
         {
-            CSLAM_HIP_TRY(hipMalloc(&dLm, (size_t)std::max(nmax, 1) * 12 * sizeof(T)));
+            return rc;
         }
         const size_t c  = (size_t)count;
-        T*           ox = dLm, *opll = dLm + 2 * c, *opvl = dLm + 6 * c;
-        const int*   sg = (kp > 0 && hd_cols[wcur] > 0) ? dSign + (size_t)wcur * wcap : (const int*)nullptr;
-        hipLaunchKernelGGL(ekf_landmark_read_kernel<T>, dim3((count + 255) / 256), dim3(256), 0, stream, dX, dPv, dP, ldp,
-                           lower, (const T*)wbase(wcur), ldp, kp, sg, first, count, x ? ox : (T*)nullptr,
-                           pll ? opll : (T*)nullptr, pvl ? opvl : (T*)nullptr);
+        T*           ox = dLm.get(), *opll = dLm.get() + 2 * c, *opvl = dLm.get() + 6 * c;
+        const int*   sg = (kp > 0 && hd_cols[wcur] > 0) ? dSign.get() + (size_t)wcur * wcap : (const int*)nullptr;
+        hipLaunchKernelGGL(ekf_landmark_read_kernel<T>, dim3((count + 255) / 256), dim3(256), 0, stream, dX.get(),
+                           dPv.get(), dP.get(), ldp, lower, (const T*)wbase(wcur), ldp, kp, sg, first, count,
+                           x ? ox : (T*)nullptr, pll ? opll : (T*)nullptr, pvl ? opvl : (T*)nullptr);
         CSLAM_HIP_TRY(hipGetLastError());
         if (x)
         {
@@ -887,11 +795,11 @@ struct Ekf : EkfBase
             return rc;
         }
         std::vector<T> diag((size_t)n);
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(T), dP, ((size_t)ldp + 1) * sizeof(T), sizeof(T), (size_t)n,
-                                       hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(T), dP.get(), ((size_t)ldp + 1) * sizeof(T), sizeof(T),
+                                       (size_t)n, hipMemcpyDeviceToHost, stream));
         // the pose block lives in the stripe
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(T), dPv, ((size_t)ldp + 1) * sizeof(T), sizeof(T), (size_t)3,
-                                       hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(T), dPv.get(), ((size_t)ldp + 1) * sizeof(T), sizeof(T),
+                                       (size_t)3, hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         double s = 0.0;
         for (T d : diag)
@@ -937,14 +845,14 @@ struct Ekf : EkfBase
         {
             for (int i = 0; i < 2; i++)
             {
-                hipEvent_t e;
-                CSLAM_HIP_TRY(hipEventCreate(&e));
-                ev_pool.push_back(e);
+                Event e;
+                CSLAM_TRY(e.create(hipEventDefault));
+                ev_pool.push_back(std::move(e));
             }
         }
         ev_stage.resize(ev_pool.size() / 2);
         ev_stage[ev_used / 2] = stage;
-        CSLAM_HIP_TRY(hipEventRecord(ev_pool[ev_used], st));
+        CSLAM_HIP_TRY(hipEventRecord(ev_pool[ev_used].get(), st));
         return CSLAM_OK;
     }
     int prof_end(int stage, hipStream_t st = nullptr)
@@ -954,7 +862,7 @@ struct Ekf : EkfBase
         {
             return CSLAM_OK;
         }
-        CSLAM_HIP_TRY(hipEventRecord(ev_pool[ev_used + 1], st));
+        CSLAM_HIP_TRY(hipEventRecord(ev_pool[ev_used + 1].get(), st));
         ev_used += 2;
         return CSLAM_OK;
     }
@@ -995,7 +903,7 @@ struct Ekf : EkfBase
         for (size_t i = 0; i + 1 < ev_used; i += 2)
         {
             float t = 0.f;
-            CSLAM_HIP_TRY(hipEventElapsedTime(&t, ev_pool[i], ev_pool[i + 1]));
+            CSLAM_HIP_TRY(hipEventElapsedTime(&t, ev_pool[i].get(), ev_pool[i + 1].get()));
             int s = ev_stage[i / 2];
             ms[s] += (double)t;
             launches[s] += 1;
@@ -1004,10 +912,10 @@ struct Ekf : EkfBase
     }
 
     // ---------------------------------------------------------------- data association (EKF.cpp:131-144, 235-326)
-    T*   dAssoc    = nullptr; // 8 scalars per feature
-    int  assoc_cap = 0;
-    int* dAssocOut = nullptr; // idf[m], kind[m]
-    int  assoc_mcap = 0;
+    DevBuf<T>   dAssoc; // 8 scalars per feature
+    int         assoc_cap = 0;
+    DevBuf<int> dAssocOut; // idf[m], kind[m]
+    int         assoc_mcap = 0;
     int associate(const void* Zv, int m, const void* Rv, double g1, double g2, int* idf_out, int* kind_out) override
     {
         if (m < 0 || !Rv || (m > 0 && (!Zv || !idf_out || !kind_out)))
@@ -1027,17 +935,17 @@ struct Ekf : EkfBase
         if (nf > assoc_cap)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(dAssoc);
-            dAssoc = nullptr;
-            CSLAM_HIP_TRY(hipMalloc(&dAssoc, (size_t)std::max(nf, 1) * 8 * sizeof(T)));
+            DevBuf<T> grown;
+            CSLAM_TRY(grown.alloc((size_t)std::max(nf, 1) * 8));
+            dAssoc    = std::move(grown);
             assoc_cap = nf;
         }
         if (m > assoc_mcap)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(dAssocOut);
-            dAssocOut = nullptr;
-            CSLAM_HIP_TRY(hipMalloc(&dAssocOut, (size_t)2 * m * sizeof(int)));
+            DevBuf<int> grown;
+            CSLAM_TRY(grown.alloc((size_t)2 * m));
+            dAssocOut  = std::move(grown);
             assoc_mcap = m;
         }
         const T* R  = static_cast<const T*>(Rv);
@@ -1050,15 +958,16 @@ struct Ekf : EkfBase
         }
         if (nf > 0)
         {
-            hipLaunchKernelGGL(ekf_assoc_feature_kernel<T>, dim3((nf + 255) / 256), dim3(256), 0, stream, dX, dP, dPv, ldp, n,
-                               R[0], R[1], R[2], R[3], lower, dAssoc);
+            hipLaunchKernelGGL(ekf_assoc_feature_kernel<T>, dim3((nf + 255) / 256), dim3(256), 0, stream, dX.get(),
+                               dP.get(), dPv.get(), ldp, n, R[0], R[1], R[2], R[3], lower, dAssoc.get());
             CSLAM_HIP_TRY(hipGetLastError());
         }
-        hipLaunchKernelGGL(ekf_assoc_scan_kernel<T>, dim3(m), dim3(64), 0, stream, dAssoc, nf, dZ, m, (T)g1, (T)g2,
-                           dAssocOut, dAssocOut + m);
+        hipLaunchKernelGGL(ekf_assoc_scan_kernel<T>, dim3(m), dim3(64), 0, stream, dAssoc.get(), nf, dZ, m, (T)g1,
+                           (T)g2, dAssocOut.get(), dAssocOut.get() + m);
         CSLAM_HIP_TRY(hipGetLastError());
-        CSLAM_HIP_TRY(hipMemcpyAsync(idf_out, dAssocOut, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, stream));
-        CSLAM_HIP_TRY(hipMemcpyAsync(kind_out, dAssocOut + m, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(idf_out, dAssocOut.get(), (size_t)m * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(kind_out, dAssocOut.get() + m, (size_t)m * sizeof(int), hipMemcpyDeviceToHost,
+                                     stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
@@ -1076,7 +985,7 @@ struct Ekf : EkfBase
     // CSLAM_FUSE_PREDICT=0 launches every predict / heading at once.
     PredictArgs<T> pp{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
     PoseSeq<T>     seq{};
-    T*             dPred = nullptr; // 16 scalars: factor kernel -> gain kernel (see FactorArgs::pred_out)
+    DevBuf<T>      dPred; // 16 scalars: factor kernel -> gain kernel (see FactorArgs::pred_out)
     bool           fuse_now = false; // the batch in flight consumes pp
     int            fuse_predict = 1;
 
@@ -1161,9 +1070,9 @@ struct Ekf : EkfBase
             return rc;
         }
         const int n_pad = round_up(n, kTile);
-        hipLaunchKernelGGL(ekf_pose_step_kernel<T>, dim3((n_pad + 255) / 256), dim3(256), 0, stream, dX, dPv, ldp, n, n_pad,
-                           seq, wbase(wcur), ldp, dHead, dSign + (size_t)wcur * wcap, dSign + (size_t)2 * wcap + wcur,
-                           dPoseDone);
+        hipLaunchKernelGGL(ekf_pose_step_kernel<T>, dim3((n_pad + 255) / 256), dim3(256), 0, stream, dX.get(),
+                           dPv.get(), ldp, n, n_pad, seq, wbase(wcur), ldp, dHead.get(),
+                           dSign.get() + (size_t)wcur * wcap, dSign.get() + (size_t)2 * wcap + wcur, dPoseDone.get());
         CSLAM_HIP_TRY(hipGetLastError());
         seq.count = 0;
         return CSLAM_OK;
@@ -1188,7 +1097,7 @@ struct Ekf : EkfBase
     int launch_factor(const T* dZ, const int* dIdf, int m, const T* R)
     {
         FactorArgs<T> a;
-        a.X   = dX;
+        a.X   = dX.get();
         a.n   = n;
         a.Z   = dZ;
         a.idf = dIdf;
@@ -1197,29 +1106,29 @@ struct Ekf : EkfBase
         {
             a.R[i] = R[i];
         }
-        a.PHT      = dPHT;
+        a.PHT      = ws.dPHT.get();
         a.ldw      = ldp;
-        a.dS       = dS;
-        a.dG       = dG;
-        a.dGt      = dGt;
-        a.dV       = dV;
-        a.dt       = dt_;
-        a.flags    = dFlags;
-        a.scratchS = dScrS;
-        a.scratchG = dScrG;
+        a.dS       = ws.dS.get();
+        a.dG       = ws.dG.get();
+        a.dGt      = ws.dGt.get();
+        a.dV       = ws.dV.get();
+        a.dt       = ws.dt_.get();
+        a.flags    = dFlags.get();
+        a.scratchS = ws.dScrS.get();
+        a.scratchG = ws.dScrG.get();
         a.textbook = (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1;
         a.stamps   = nullptr;
-        a.sub      = sub_valid ? dSub : nullptr;
+        a.sub      = sub_valid ? ws.dSub.get() : nullptr;
         a.dM       = nullptr;
         m_valid    = false;
         g_from_gt  = false;
         a.pp       = fuse_now ? pp : PredictArgs<T>{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
-        a.P3       = dPv; // the pose block lives in the stripe
+        a.P3       = dPv.get(); // the pose block lives in the stripe
         a.ldp3     = ldp;
-        a.pred_out = dPred;
+        a.pred_out = dPred.get();
         a.lds_S    = 1;
         a.lds_G    = 1;
-        return launch_factor_args(a, dU, stream);
+        return launch_factor_args(a, ws.dU.get(), stream);
     }
 
     // dispatch on k (a.m); du: the X-update vector u = G (G^T V)
@@ -1235,19 +1144,19 @@ struct Ekf : EkfBase
         //   beyond             ekf_factor_kernel: the general LDS / global-scratch form
         if (k <= 4)
         {
-            a.dM    = own ? dM : a.dM;
+            a.dM    = own ? ws.dM.get() : a.dM;
             m_valid = own ? true : m_valid;
             hipLaunchKernelGGL((ekf_factor_small_kernel<T, 4>), dim3(1), dim3(256), 0, st, a, du);
         }
         else if (k <= 16)
         {
-            a.dM    = own ? dM : a.dM;
+            a.dM    = own ? ws.dM.get() : a.dM;
             m_valid = own ? true : m_valid;
             hipLaunchKernelGGL((ekf_factor_small_kernel<T, 16>), dim3(1), dim3(256), 0, st, a, du);
         }
         else if (k <= 64)
         {
-            a.dM      = own ? dM : a.dM;
+            a.dM      = own ? ws.dM.get() : a.dM;
             m_valid   = own ? true : m_valid;
             g_from_gt = own ? true : g_from_gt;
             if constexpr (std::is_same<T, float>::value)
@@ -1284,7 +1193,7 @@ struct Ekf : EkfBase
                 constexpr int K   = 128;
                 const size_t  lds = (size_t)(K * (K + 1) + (3 + K) * (K + 1) + (K / 2) * 10 + 6 * K) * sizeof(float) +
                                    (size_t)(K / 2 + 4) * sizeof(int) + 16;
-                a.dM      = own ? dM : a.dM;
+                a.dM      = own ? ws.dM.get() : a.dM;
                 m_valid   = own ? true : m_valid;
                 g_from_gt = own ? true : g_from_gt;
                 hipLaunchKernelGGL((ekf_factor_mfma_big_f32<128>), dim3(1), dim3(256), lds, st, a, du);
@@ -1312,15 +1221,15 @@ struct Ekf : EkfBase
         pose_fused_in_gain = false;
         if (Gt == nullptr)
         {
-            Gt = dGt;
-            U  = dU;
-            M  = m_valid ? dM : nullptr;
+            Gt = ws.dGt.get();
+            U  = ws.dU.get();
+            M  = m_valid ? ws.dM.get() : nullptr;
         }
         if (!launch_gain_fast(k, n_pad, slot, Gt, U, M))
         {
             // the general vector-unit form (f32 beyond k = 128, f64 beyond k = 64): no X vector u, no fused pose downdate
-            hipLaunchKernelGGL(ekf_gain_kernel<T>, dim3(n_pad / 64), dim3(256), 0, stream, dPHT, ldp, n, n_pad, k, dGt, dt_,
-                               slot, dX);
+            hipLaunchKernelGGL(ekf_gain_kernel<T>, dim3(n_pad / 64), dim3(256), 0, stream, ws.dPHT.get(), ldp, n, n_pad,
+                               k, ws.dGt.get(), ws.dt_.get(), slot, dX.get());
         }
         CSLAM_HIP_TRY(hipGetLastError());
         if (pose_fused_in_gain)
@@ -1328,7 +1237,7 @@ struct Ekf : EkfBase
             return CSLAM_OK; // ekf_panel_mfma_f32 applied the pose-stripe downdate and zeroed the panel's pose rows itself
         }
         hipLaunchKernelGGL(ekf_pose_downdate_kernel<T>, dim3((n + 63) / 64), dim3(256), 0, stream, slot, ldp, k,
-                           round_up(k, 8), n, dPv, ldp, dWv, dPoseDone + 1);
+                           round_up(k, 8), n, dPv.get(), ldp, ws.dWv.get(), dPoseDone.get() + 1);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -1359,9 +1268,9 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        if (fuse_now && dPred == nullptr)
+        if (fuse_now && !dPred.get() && (rc = dPred.alloc(16)))
         {
-            CSLAM_HIP_TRY(hipMalloc(&dPred, 16 * sizeof(T)));
+            return rc;
         }
         // the general gain kernels and ekf_pose_downdate_kernel write whole blocks of 8 columns of the slot: the slot starts
         // at column kp (heading columns make kp any number), so kp + round_up(k, 8) must stay inside the region
@@ -1396,28 +1305,29 @@ struct Ekf : EkfBase
         }
         const dim3 ggrid((n + 255) / 256, (m + kGatherObs - 1) / kGatherObs);
         // the compact H-rows block for the MFMA factor kernel (f32, 16 < k <= 64, no pending panels to correct)
-        sub_valid = (k > 16 && k <= 64 && (kp == 0 || small_corr) && dSub != nullptr);
+        sub_valid = (k > 16 && k <= 64 && (kp == 0 || small_corr) && ws.dSub.get() != nullptr);
         PredictArgs<T> pnone{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
         {
-            T*             sub  = sub_valid ? dSub : nullptr;
+            T*             sub  = sub_valid ? ws.dSub.get() : nullptr;
             PredictArgs<T> pa   = fuse_now ? pp : pnone;
-            T*             pred = fuse_now ? dPred : (T*)nullptr;
+            T*             pred = fuse_now ? dPred.get() : (T*)nullptr;
             const T*       Wg   = (kp > 0 && !pipeline) ? (const T*)wbase(wcur) : (const T*)nullptr;
             const int      kg   = pipeline ? 0 : kp;
             const int*     sg =
-                (kp > 0 && !pipeline && hd_cols[wcur] > 0) ? dSign + (size_t)wcur * wcap : (const int*)nullptr;
-            T* yout = (kp > 0 && !small_corr && !pipeline) ? dY : (T*)nullptr;
+                (kp > 0 && !pipeline && hd_cols[wcur] > 0) ? dSign.get() + (size_t)wcur * wcap : (const int*)nullptr;
+            T* yout = (kp > 0 && !small_corr && !pipeline) ? ws.dY.get() : (T*)nullptr;
             if (wide_corr)
             {
                 const dim3 wgrid((n + 255) / 256, (m + kGatherObsWide - 1) / kGatherObsWide);
-                hipLaunchKernelGGL((ekf_gather_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream, dX,
-                                   dP, dPv, ldp, n, dZ, dIdf, m, dPHT, ldp, lower, sub, pa, pred, Wg, ldp, kg, sg, dFlags,
-                                   yout);
+                hipLaunchKernelGGL((ekf_gather_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream,
+                                   dX.get(), dP.get(), dPv.get(), ldp, n, dZ, dIdf, m, ws.dPHT.get(), ldp, lower, sub,
+                                   pa, pred, Wg, ldp, kg, sg, dFlags.get(), yout);
             }
             else
             {
-                hipLaunchKernelGGL(ekf_gather_kernel<T>, ggrid, dim3(256), 0, stream, dX, dP, dPv, ldp, n, dZ, dIdf, m, dPHT,
-                                   ldp, lower, sub, pa, pred, Wg, ldp, kg, sg, dFlags, yout);
+                hipLaunchKernelGGL(ekf_gather_kernel<T>, ggrid, dim3(256), 0, stream, dX.get(), dP.get(), dPv.get(),
+                                   ldp, n, dZ, dIdf, m, ws.dPHT.get(), ldp, lower, sub, pa, pred, Wg, ldp, kg, sg,
+                                   dFlags.get(), yout);
             }
         }
         CSLAM_HIP_TRY(hipGetLastError());
@@ -1441,15 +1351,15 @@ struct Ekf : EkfBase
         {
             if (pipeline) // (single stream: the gather kernel has published Y = H*Wp already)
             {
-                hipLaunchKernelGGL(ekf_pending_y_kernel<T>, dim3(m, (kc + 255) / 256), dim3(256), 0, stream, dX, n, dZ, dIdf,
-                                   m, Wc, ldp, kc, dY,
-                                   hd_cols[rc_region] > 0 ? dSign + (size_t)rc_region * wcap : (const int*)nullptr);
+                hipLaunchKernelGGL(ekf_pending_y_kernel<T>, dim3(m, (kc + 255) / 256), dim3(256), 0, stream, dX.get(), n, dZ, dIdf,
+                                   m, Wc, ldp, kc, ws.dY.get(),
+                                   hd_cols[rc_region] > 0 ? dSign.get() + (size_t)rc_region * wcap : (const int*)nullptr);
                 CSLAM_HIP_TRY(hipGetLastError());
             }
             if (!launch_corr_fast(k, Wc, kc))
             {
-                hipLaunchKernelGGL(ekf_pending_corr_kernel<T>, ggrid, dim3(256), 0, stream, n, m, Wc, ldp, kc, dY, dPHT,
-                                   ldp);
+                hipLaunchKernelGGL(ekf_pending_corr_kernel<T>, ggrid, dim3(256), 0, stream, n, m, Wc, ldp, kc,
+                                   ws.dY.get(), ws.dPHT.get(), ldp);
             }
             CSLAM_HIP_TRY(hipGetLastError());
         }
@@ -1473,7 +1383,7 @@ struct Ekf : EkfBase
         }
         if (sync_mode)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(hFlags, dFlags, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(hFlags.get(), dFlags.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
             if (hFlags[1] & kFlagLltFailed)
             {
@@ -1494,8 +1404,8 @@ struct Ekf : EkfBase
     {
         sticky_host |= CSLAM_FACTOR_FALLBACK;
         std::vector<T> S((size_t)k * k), V((size_t)k), G;
-        CSLAM_HIP_TRY(hipMemcpyAsync(S.data(), dS, S.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
-        CSLAM_HIP_TRY(hipMemcpyAsync(V.data(), dV, V.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(S.data(), ws.dS.get(), S.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(V.data(), ws.dV.get(), V.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         bool textbook = !(quirks & CSLAM_Q_LOWER_CHOL_GAIN);
         if (!host_eigen_fallback_gain(S.data(), k, textbook, G))
@@ -1512,11 +1422,11 @@ struct Ekf : EkfBase
                 t[c] += G[(size_t)c * k + r] * V[r];
             }
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dG, G.data(), G.size() * sizeof(T), hipMemcpyHostToDevice, stream));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dGt, Gt.data(), Gt.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(ws.dG.get(), G.data(), G.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(ws.dGt.get(), Gt.data(), Gt.size() * sizeof(T), hipMemcpyHostToDevice, stream));
         g_from_gt  = false; // (the fallback gain is a general matrix, uploaded as G and G^T)
         m_valid    = false; // (M belonged to the zeroed G: the separate pose downdate kernel runs)
-        CSLAM_HIP_TRY(hipMemcpyAsync(dt_, t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(ws.dt_.get(), t.data(), t.size() * sizeof(T), hipMemcpyHostToDevice, stream));
         std::vector<T> u((size_t)k, (T)0);
         for (int q = 0; q < k; q++)
         {
@@ -1525,7 +1435,7 @@ struct Ekf : EkfBase
                 u[q] += G[(size_t)c * k + q] * t[c];
             }
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dU, u.data(), u.size() * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(ws.dU.get(), u.data(), u.size() * sizeof(T), hipMemcpyHostToDevice, stream));
         int rc;
         if ((rc = own_region(wcur)))
         {
@@ -1573,22 +1483,29 @@ struct Ekf : EkfBase
     };
     struct FactorOut
     {
-        T *  S = nullptr, *G = nullptr, *Gt = nullptr, *V = nullptr, *t = nullptr, *U = nullptr, *M = nullptr;
-        T *  sub = nullptr, *xloc = nullptr;
-        int* idloc = nullptr;
+        DevBuf<T>   S, G, Gt, V, t, U, M, sub, xloc;
+        DevBuf<int> idloc;
+    };
+    // what the first window sets up, as a whole (la_ensure)
+    struct LaSet
+    {
+        Event          ev_fb;  // the chain kernel of the last window has finished
+        Event          ev_raw; // the blocks kernel of the last window has finished (several engines alive only)
+        FactorOut      fo[2];
+        DevBuf<T>      XL, PvL, PH, PvLb, Dbb;
+        DevBuf<T>      Y;      // H_b * W1_a of the last window (for a fused wide kernel)
+        DevBuf<LaModel<T>> model; // [2]: predict + observation model of update a / b
+        DevBuf<unsigned>   done;  // device counter: workgroups of the blocks kernels that have finished
+        DevBuf<long long>  stamps; // CSLAM_LA_STAMPS=1: phase stamps of factor(a) underneath the P-GEMM (diagnostics)
     };
     LaUpd       la_q[2];
     int         la_n = 0;
-    FactorOut   fo[2];
-    hipStream_t stream_f = nullptr;
-    hipEvent_t  ev_fb = nullptr;  // the chain kernel of the last window has finished
-    hipEvent_t  ev_raw = nullptr; // the blocks kernel of the last window has finished (several engines alive only)
-    T *         la_XL = nullptr, *la_PvL = nullptr, *la_WR = nullptr, *la_PH = nullptr, *la_PvLb = nullptr, *la_Dbb = nullptr;
-    T*          la_Y = nullptr;         // H_b * W1_a of the last window (for a fused wide kernel)
-    LaModel<T>* la_model = nullptr;     // [2]: predict + observation model of update a / b
+    LaSet       la;
+    bool        la_ready = false;   // la_ensure has set `la` and stream F up
+    hipStream_t stream_f = nullptr; // = stream_f_own.get() from then on
+    DevBuf<T>   la_WR;
     int         la_kpad  = 0;
     int         la_cus = 0;        // compute units the persistent P-GEMM leaves to the chain kernel (0 until stream F exists)
-    unsigned*   la_done   = nullptr; // device counter: workgroups of the blocks kernels that have finished
     unsigned    la_target = 0;       // its value once every blocks kernel launched so far has finished
     unsigned    la_seq    = 0;       // windows whose chain kernel has been launched
     // != 0: the next P-GEMM launch (ekf_downdate_psym4_f32) adds this to la_done[0] -- the chain's go-ahead, in place of a
@@ -1597,123 +1514,71 @@ struct Ekf : EkfBase
     int         la_k64 = 1;       // CSLAM_LA_K64=0: the general wide kernel for m = 32 too (A/B)
     int         la_wg_signal = 0; // CSLAM_LA_WG_SIGNAL=1: always the blocks kernel's own release (A/B: the first form)
 
-    // Dynamic LDS of the chain kernel <T, K>: the carry step's arrays (in f64 the factor body's arrays live in the same
-    // space), padded so that the workgroup's total LDS is ~99 KB: more than 96 KB keeps the persistent P-GEMM's 64 KB
-    // workgroups off its compute unit, less than 106 KB lets it start beside ONE workgroup of the wide kernel (54 KB) --
-    // a chain kernel that found no unit before the P-GEMM filled the chip must still be able to start while the wide
-    // kernel's workgroups wait for it.
-    static size_t la_chain_lds(int K)
-    {
-        size_t need = la_carry_lds<T>();
-        if (sizeof(T) == 8)
-        {
-            need = std::max(need, (size_t)(K * (K + 1) + (3 + K) * (K + 1) + (K / 2) * 10 + 6 * K) * sizeof(double) +
-                                      (size_t)(K / 2 + 4) * sizeof(int) + 16);
-            return need;
-        }
-        const size_t fixed = (K == 64) ? 53984 : 15008; // static LDS of ekf_la_chain_kernel<float, K> (tools/kernel_resources.py)
-        return std::max(need, (size_t)101 * 1024 - fixed);
-    }
     int         la_fused   = 1; // env CSLAM_LA_FUSED=0: gather + gain per update instead of the one wide launch (A/B)
-    long long*  la_stamps  = nullptr; // CSLAM_LA_STAMPS=1: phase stamps of factor(a) underneath the P-GEMM (diagnostics)
     // what debug_last_update reads (the handle's workspace, or the factor slot of a window's last update)
     const T *dbgS = nullptr, *dbgGt = nullptr, *dbgV = nullptr;
-
-    void la_free()
-    {
-        for (FactorOut& f : fo)
-        {
-            (void)hipFree(f.S);
-            (void)hipFree(f.G);
-            (void)hipFree(f.Gt);
-            (void)hipFree(f.V);
-            (void)hipFree(f.t);
-            (void)hipFree(f.U);
-            (void)hipFree(f.M);
-            (void)hipFree(f.sub);
-            (void)hipFree(f.xloc);
-            (void)hipFree(f.idloc);
-            f = FactorOut();
-        }
-        (void)hipFree(la_XL);
-        (void)hipFree(la_PvL);
-        (void)hipFree(la_WR);
-        (void)hipFree(la_PH);
-        (void)hipFree(la_PvLb);
-        (void)hipFree(la_Dbb);
-        (void)hipFree(la_Y);
-        (void)hipFree(la_model);
-        (void)hipFree(la_stamps);
-        (void)hipFree(la_done);
-        la_stamps = nullptr;
-        la_done   = nullptr;
-        la_XL = la_PvL = la_WR = la_PH = la_PvLb = la_Dbb = la_Y = nullptr;
-        la_model = nullptr;
-        la_kpad  = 0;
-    }
 
     int la_ensure(int kp_cols)
     {
         constexpr int KM = 2 * kLaMaxObs;
-        if (stream_f == nullptr)
+        if (!la_ready)
         {
             // The chain kernel owns its compute unit by the LDS it asks for (see ekf_la_chain_kernel); the persistent
             // P-GEMM's grid is reduced by that unit's two workgroups (la_cus).
             int lo = 0, hi = 0;
             CSLAM_HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-            CSLAM_HIP_TRY(hipStreamCreateWithPriority(&stream_f, hipStreamNonBlocking, hi));
-            la_cus = 1;
-            CSLAM_HIP_TRY(hipEventCreateWithFlags(&ev_fb, hipEventDisableTiming));
-            CSLAM_HIP_TRY(hipEventCreateWithFlags(&ev_raw, hipEventDisableTiming));
+            Stream sf;
+            LaSet  nl;
+            int    rc = sf.create_with_priority(hipStreamNonBlocking, hi);
+            if (rc || (rc = nl.ev_fb.create(hipEventDisableTiming)) || (rc = nl.ev_raw.create(hipEventDisableTiming)))
+            {
+                return rc;
+            }
             CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_kernel<T, 32>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds(32)));
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds<T>(32)));
             CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_kernel<T, 64>),
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds(64)));
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds<T>(64)));
             // words 0..255: 16 counters (stride 16) of finished blocks-kernel workgroups; words 256..767: 32 copies
             // (stride 16) of the last window whose chain kernel has finished
-            CSLAM_HIP_TRY(hipMalloc(&la_done, 768 * sizeof(unsigned)));
-            CSLAM_HIP_TRY(hipMemset(la_done, 0, 768 * sizeof(unsigned)));
-            la_target = 0;
-            la_seq    = 0;
-            for (FactorOut& f : fo)
+            CSLAM_TRY(nl.done.alloc_zeroed_blocking(768));
+            for (FactorOut& f : nl.fo)
             {
-                CSLAM_HIP_TRY(hipMalloc(&f.S, (size_t)KM * (KM + 1) * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.G, (size_t)KM * (KM + 1) * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.Gt, (size_t)KM * (KM + 1) * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.V, (size_t)KM * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.t, (size_t)KM * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.U, (size_t)KM * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.M, (size_t)3 * KM * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.sub, (size_t)(3 + KM) * KM * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.xloc, (size_t)(3 + KM) * sizeof(T)));
-                CSLAM_HIP_TRY(hipMalloc(&f.idloc, (size_t)kLaMaxObs * sizeof(int)));
+                const size_t kk = (size_t)KM * (KM + 1);
+                if ((rc = f.S.alloc(kk)) || (rc = f.G.alloc(kk)) || (rc = f.Gt.alloc(kk)) || (rc = f.V.alloc(KM)) ||
+                    (rc = f.t.alloc(KM)) || (rc = f.U.alloc(KM)) || (rc = f.M.alloc((size_t)3 * KM)) ||
+                    (rc = f.sub.alloc((size_t)(3 + KM) * KM)) || (rc = f.xloc.alloc(3 + KM)) ||
+                    (rc = f.idloc.alloc(kLaMaxObs)))
+                {
+                    return rc;
+                }
             }
-            CSLAM_HIP_TRY(hipMalloc(&la_XL, (size_t)2 * KM * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&la_PvL, (size_t)2 * KM * 3 * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&la_PH, (size_t)KM * KM * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&la_PvLb, (size_t)KM * 3 * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&la_Dbb, (size_t)KM * KM * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&la_Y, (size_t)KM * KM * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&la_model, 2 * sizeof(LaModel<T>)));
+            if ((rc = nl.XL.alloc((size_t)2 * KM)) || (rc = nl.PvL.alloc((size_t)2 * KM * 3)) ||
+                (rc = nl.PH.alloc((size_t)KM * KM)) || (rc = nl.PvLb.alloc((size_t)KM * 3)) ||
+                (rc = nl.Dbb.alloc((size_t)KM * KM)) || (rc = nl.Y.alloc((size_t)KM * KM)) ||
+                (rc = nl.model.alloc(2)) || (getenv("CSLAM_LA_STAMPS") && (rc = nl.stamps.alloc_zeroed_blocking(32))))
+            {
+                return rc;
+            }
             if (const char* fv = getenv("CSLAM_LA_FUSED"))
             {
                 la_fused = atoi(fv) ? 1 : 0;
             }
-            if (getenv("CSLAM_LA_STAMPS"))
-            {
-                CSLAM_HIP_TRY(hipMalloc(&la_stamps, 32 * sizeof(long long)));
-                CSLAM_HIP_TRY(hipMemset(la_stamps, 0, 32 * sizeof(long long)));
-            }
+            stream_f_own = std::move(sf);
+            stream_f     = stream_f_own.get();
+            la           = std::move(nl);
+            la_cus       = 1;
+            la_target    = 0;
+            la_seq       = 0;
+            la_ready     = true;
         }
         if (kp_cols > la_kpad)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream_f));
-            (void)hipFree(la_WR);
-            la_WR   = nullptr;
-            la_kpad = 0;
             const int kpad = round_up(std::max(kp_cols, 128), 64);
-            CSLAM_HIP_TRY(hipMalloc(&la_WR, (size_t)2 * KM * kpad * sizeof(T))); // [kpad columns][128 slots]
+            DevBuf<T> wr;
+            CSLAM_TRY(wr.alloc((size_t)2 * KM * kpad)); // [kpad columns][128 slots]
+            la_WR   = std::move(wr);
             la_kpad = kpad;
         }
         return CSLAM_OK;
@@ -1768,31 +1633,31 @@ struct Ekf : EkfBase
     FactorArgs<T> la_factor_args(const LaUpd& u, FactorOut& f)
     {
         FactorArgs<T> a;
-        a.X   = f.xloc;
+        a.X   = f.xloc.get();
         a.n   = 3 + 2 * u.m;
         a.Z   = u.dZ;
-        a.idf = fo[0].idloc; // 1, 2, ... (written once per window by the blocks kernel)
+        a.idf = la.fo[0].idloc.get(); // 1, 2, ... (written once per window by the blocks kernel)
         a.m   = u.m;
         for (int i = 0; i < 4; i++)
         {
             a.R[i] = u.R[i];
         }
-        a.PHT      = dPHT; // (not read: the compact block is supplied)
+        a.PHT      = ws.dPHT.get(); // (not read: the compact block is supplied)
         a.ldw      = ldp;
-        a.dS       = f.S;
-        a.dG       = f.G;
-        a.dGt      = f.Gt;
-        a.dV       = f.V;
-        a.dt       = f.t;
-        a.flags    = dFlags;
-        a.scratchS = dScrS;
-        a.scratchG = dScrG;
+        a.dS       = f.S.get();
+        a.dG       = f.G.get();
+        a.dGt      = f.Gt.get();
+        a.dV       = f.V.get();
+        a.dt       = f.t.get();
+        a.flags    = dFlags.get();
+        a.scratchS = ws.dScrS.get();
+        a.scratchG = ws.dScrG.get();
         a.textbook = (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1;
-        a.stamps   = (la_stamps && &f == &fo[0]) ? la_stamps : nullptr;
-        a.sub      = f.sub;
-        a.dM       = f.M;
+        a.stamps   = (la.stamps.get() && &f == &la.fo[0]) ? la.stamps.get() : nullptr;
+        a.sub      = f.sub.get();
+        a.dM       = f.M.get();
         a.pp       = PredictArgs<T>{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0}; // (applied by blocks / carry)
-        a.P3       = dPv;
+        a.P3       = dPv.get();
         a.ldp3     = ldp;
         a.pred_out = nullptr;
         a.lds_S    = 1;
@@ -1806,27 +1671,29 @@ struct Ekf : EkfBase
         const int k = 2 * u.m;
         pp          = u.pp;
         fuse_now    = pp.valid != 0;
-        if (fuse_now && dPred == nullptr)
+        int rc      = CSLAM_OK;
+        if (fuse_now && !dPred.get() && (rc = dPred.alloc(16)))
         {
-            CSLAM_HIP_TRY(hipMalloc(&dPred, 16 * sizeof(T)));
+            return rc;
         }
         last_k = k;
         PredictArgs<T> pnone{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
         PredictArgs<T> pa   = fuse_now ? pp : pnone;
-        T*             pred = fuse_now ? dPred : (T*)nullptr;
+        T*             pred = fuse_now ? dPred.get() : (T*)nullptr;
         const T*       Wg   = kp > 0 ? (const T*)wbase(wcur) : (const T*)nullptr;
         if (kp > kGatherCorr)
         {
             const dim3 wgrid((n + 255) / 256, (u.m + kGatherObsWide - 1) / kGatherObsWide);
-            hipLaunchKernelGGL((ekf_gather_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream, dX, dP, dPv,
-                               ldp, n, u.dZ, u.dIdf, u.m, dPHT, ldp, lower, (T*)nullptr, pa, pred, Wg, ldp, kp,
-                               (const int*)nullptr, dFlags, (T*)nullptr);
+            hipLaunchKernelGGL((ekf_gather_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream,
+                               dX.get(), dP.get(), dPv.get(), ldp, n, u.dZ, u.dIdf, u.m, ws.dPHT.get(), ldp, lower,
+                               (T*)nullptr, pa, pred, Wg, ldp, kp, (const int*)nullptr, dFlags.get(), (T*)nullptr);
         }
         else
         {
             const dim3 ggrid((n + 255) / 256, (u.m + kGatherObs - 1) / kGatherObs);
-            hipLaunchKernelGGL(ekf_gather_kernel<T>, ggrid, dim3(256), 0, stream, dX, dP, dPv, ldp, n, u.dZ, u.dIdf, u.m, dPHT,
-                               ldp, lower, (T*)nullptr, pa, pred, Wg, ldp, kp, (const int*)nullptr, dFlags, (T*)nullptr);
+            hipLaunchKernelGGL(ekf_gather_kernel<T>, ggrid, dim3(256), 0, stream, dX.get(), dP.get(), dPv.get(), ldp, n,
+                               u.dZ, u.dIdf, u.m, ws.dPHT.get(), ldp, lower, (T*)nullptr, pa, pred, Wg, ldp, kp,
+                               (const int*)nullptr, dFlags.get(), (T*)nullptr);
         }
         CSLAM_HIP_TRY(hipGetLastError());
         if (ev_factor != nullptr)
@@ -1834,7 +1701,7 @@ struct Ekf : EkfBase
             CSLAM_HIP_TRY(hipStreamWaitEvent(stream, ev_factor, 0));
         }
         T*  slot = wbase(wcur) + (size_t)kp * ldp;
-        int rc   = launch_gain(k, slot, f.Gt, f.U, f.M);
+        rc       = launch_gain(k, slot, f.Gt.get(), f.U.get(), f.M.get());
         if (rc)
         {
             return rc;
@@ -1843,9 +1710,9 @@ struct Ekf : EkfBase
         fuse_now  = false;
         last_slot = slot;
         kp += k;
-        dbgS      = f.S;
-        dbgGt     = f.Gt;
-        dbgV      = f.V;
+        dbgS      = f.S.get();
+        dbgGt     = f.Gt.get();
+        dbgV      = f.V.get();
         g_from_gt = true;
         sub_valid = false;
         return CSLAM_OK;
@@ -1888,15 +1755,15 @@ struct Ekf : EkfBase
         const unsigned n_blocks = (unsigned)(3 + ka + 2 * kb);
         auto launch_chain = [&]() -> int {
             LaChainArgs<T> ch;
-            ch.fa   = la_factor_args(ua, fo[0]);
-            ch.fb   = la_factor_args(nu == 2 ? ub : ua, fo[1]);
-            ch.du_a = fo[0].U;
-            ch.du_b = fo[1].U;
+            ch.fa   = la_factor_args(ua, la.fo[0]);
+            ch.fb   = la_factor_args(nu == 2 ? ub : ua, la.fo[1]);
+            ch.du_a = la.fo[0].U.get();
+            ch.du_b = la.fo[1].U.get();
             ch.nu   = nu;
-            ch.done = la_done;
+            ch.done = la.done.get();
             ch.target  = la_target + n_blocks;
             ch.timeout = 20000000ull; // 0.2 s of s_memrealtime ticks
-            ch.chain_done = la_done + 256;
+            ch.chain_done = la.done.get() + 256;
             ch.seq        = ++la_seq;
             LaCarryArgs<T>& ca = ch.ca;
             ca.n       = n;
@@ -1904,29 +1771,29 @@ struct Ekf : EkfBase
             ca.m_b     = nu == 2 ? ub.m : 0;
             ca.idf_b   = nu == 2 ? ub.dIdf : ua.dIdf;
             ca.pp_b    = nu == 2 ? ub.pp : ua.pp;
-            ca.PH      = la_PH;
-            ca.Dbb     = la_Dbb;
-            ca.PvLb    = la_PvLb;
-            ca.XLb     = la_XL + ka;
-            ca.model_a = la_model;
-            ca.Gt_a    = fo[0].Gt;
-            ca.u_a     = fo[0].U;
-            ca.M_a     = fo[0].M;
-            ca.sub_a   = fo[0].sub;
-            ca.sub_b   = fo[1].sub;
-            ca.xloc_b  = fo[1].xloc;
-            ca.model_b = la_model + 1;
-            ca.Y_b     = la_Y;
+            ca.PH      = la.PH.get();
+            ca.Dbb     = la.Dbb.get();
+            ca.PvLb    = la.PvLb.get();
+            ca.XLb     = la.XL.get() + ka;
+            ca.model_a = la.model.get();
+            ca.Gt_a    = la.fo[0].Gt.get();
+            ca.u_a     = la.fo[0].U.get();
+            ca.M_a     = la.fo[0].M.get();
+            ca.sub_a   = la.fo[0].sub.get();
+            ca.sub_b   = la.fo[1].sub.get();
+            ca.xloc_b  = la.fo[1].xloc.get();
+            ca.model_b = la.model.get() + 1;
+            ca.Y_b     = la.Y.get();
             if (std::max(ka, kb) <= 32)
             {
-                hipLaunchKernelGGL((ekf_la_chain_kernel<T, 32>), dim3(1), dim3(256), la_chain_lds(32), stream_f, ch);
+                hipLaunchKernelGGL((ekf_la_chain_kernel<T, 32>), dim3(1), dim3(256), la_chain_lds<T>(32), stream_f, ch);
             }
             else
             {
-                hipLaunchKernelGGL((ekf_la_chain_kernel<T, 64>), dim3(1), dim3(256), la_chain_lds(64), stream_f, ch);
+                hipLaunchKernelGGL((ekf_la_chain_kernel<T, 64>), dim3(1), dim3(256), la_chain_lds<T>(64), stream_f, ch);
             }
             CSLAM_HIP_TRY(hipGetLastError());
-            CSLAM_HIP_TRY(hipEventRecord(ev_fb, stream_f));
+            CSLAM_HIP_TRY(hipEventRecord(la.ev_fb.get(), stream_f));
             return CSLAM_OK;
         };
         if (!safe && (rc = launch_chain()))
@@ -1938,8 +1805,8 @@ struct Ekf : EkfBase
         //    for the factor step.  (From here to the blocks launch nothing may fail: the chain kernel is waiting.)
         const T* Wp = wbase(wcur);
         LaRowsArgs<T> ra;
-        ra.X     = dX;
-        ra.Pv    = dPv;
+        ra.X     = dX.get();
+        ra.Pv    = dPv.get();
         ra.ldp   = ldp;
         ra.n     = n;
         ra.idf_a = ua.dIdf;
@@ -1950,47 +1817,47 @@ struct Ekf : EkfBase
         ra.ldw   = ldp;
         ra.kp    = kp;
         ra.kpad  = la_kpad;
-        ra.XL    = la_XL;
-        ra.PvL   = la_PvL;
-        ra.WR    = la_WR;
-        ra.flags = dFlags;
+        ra.XL    = la.XL.get();
+        ra.PvL   = la.PvL.get();
+        ra.WR    = la_WR.get();
+        ra.flags = dFlags.get();
         hipLaunchKernelGGL(ekf_la_rows_kernel<T>, dim3(ka + kb), dim3(128), 0, stream, ra);
         LaPrepArgs<T> pa;
-        pa.P       = dP;
+        pa.P       = dP.get();
         pa.ldp     = ldp;
         pa.n       = n;
         pa.lower   = lower;
-        pa.X       = dX;
-        pa.Pv      = dPv;
+        pa.X       = dX.get();
+        pa.Pv      = dPv.get();
         pa.idf_a   = ua.dIdf;
         pa.idf_b   = nu == 2 ? ub.dIdf : ua.dIdf;
         pa.ra      = ka;
         pa.rb      = kb;
         pa.pp_a    = ua.pp;
-        pa.XL      = la_XL;
-        pa.PvL     = la_PvL;
-        pa.WR      = la_WR;
+        pa.XL      = la.XL.get();
+        pa.PvL     = la.PvL.get();
+        pa.WR      = la_WR.get();
         pa.kp      = kp;
         pa.kpad    = la_kpad;
-        pa.sub_a   = fo[0].sub;
-        pa.PH      = la_PH;
-        pa.Dbb     = la_Dbb;
-        pa.PvLb    = la_PvLb;
-        pa.model_a = la_model;
-        pa.xloc_a  = fo[0].xloc;
-        pa.idloc   = fo[0].idloc;
+        pa.sub_a   = la.fo[0].sub.get();
+        pa.PH      = la.PH.get();
+        pa.Dbb     = la.Dbb.get();
+        pa.PvLb    = la.PvLb.get();
+        pa.model_a = la.model.get();
+        pa.xloc_a  = la.fo[0].xloc.get();
+        pa.idloc   = la.fo[0].idloc.get();
         // the P-GEMM that follows signals the chain when it is the plain single-stream psym4 launch (always in the steady state);
         // otherwise the blocks kernel's workgroups release their rows themselves
         const int  k8f      = round_up(kp, 8);
         const bool pg_signal = !la_wg_signal && !safe && kp > 0 && seq.count == 0 && sizeof(T) == 4 && k8f <= 128 && lower && ldp < 32768 &&
                                !limbs_take(k8f) && stream_b == stream && hd_cols[wcur] == 0;
-        pa.done    = pg_signal ? (unsigned*)nullptr : la_done;
+        pa.done    = pg_signal ? (unsigned*)nullptr : la.done.get();
         hipLaunchKernelGGL(ekf_la_blocks_kernel<T>, dim3(n_blocks), dim3(64), 0, stream, pa);
         CSLAM_HIP_TRY(hipGetLastError());
         if (safe)
         {
-            CSLAM_HIP_TRY(hipEventRecord(ev_raw, stream));
-            CSLAM_HIP_TRY(hipStreamWaitEvent(stream_f, ev_raw, 0));
+            CSLAM_HIP_TRY(hipEventRecord(la.ev_raw.get(), stream));
+            CSLAM_HIP_TRY(hipStreamWaitEvent(stream_f, la.ev_raw.get(), 0));
             if ((rc = launch_chain())) // (its wait for the blocks kernel's counters passes at once)
             {
                 return rc;
@@ -2004,7 +1871,7 @@ struct Ekf : EkfBase
         {
             const unsigned add = la_sig_add;
             la_sig_add         = 0;
-            hipLaunchKernelGGL(ekf_la_signal_kernel, dim3(1), dim3(64), 0, stream, la_done, add);
+            hipLaunchKernelGGL(ekf_la_signal_kernel, dim3(1), dim3(64), 0, stream, la.done.get(), add);
         }
         if (rc)
         {
@@ -2020,21 +1887,21 @@ struct Ekf : EkfBase
                 fused = true;
                 if (safe) // (see g_engines: no waiting inside the wide kernel then)
                 {
-                    CSLAM_HIP_TRY(hipStreamWaitEvent(stream, ev_fb, 0));
+                    CSLAM_HIP_TRY(hipStreamWaitEvent(stream, la.ev_fb.get(), 0));
                 }
                 LaWideArgs wa;
-                wa.chain_done = la_done + 256; // (waits for the chain kernel in the kernel: a stream event costs ~6 us here)
+                wa.chain_done = la.done.get() + 256; // (waits for the chain kernel in the kernel: a stream event costs ~6 us here)
                 wa.seq        = la_seq;
                 wa.timeout    = 20000000ull;
-                wa.flags      = dFlags;
-                wa.stamps     = la_stamps ? la_stamps + 16 : nullptr;
+                wa.flags      = dFlags.get();
+                wa.stamps     = la.stamps.get() ? la.stamps.get() + 16 : nullptr;
                 wa.wg_times   = nullptr;
-                wa.P       = dP;
+                wa.P       = dP.get();
                 wa.ldp     = ldp;
                 wa.n       = n;
                 wa.lower   = getenv("CSLAM_LA_TIMING_DIRECT") ? 0 : lower; // (timing experiment only: wrong results)
-                wa.X       = dX;
-                wa.Pv      = dPv;
+                wa.X       = dX.get();
+                wa.Pv      = dPv.get();
                 wa.nu      = nu;
                 wa.idf_a   = ua.dIdf;
                 wa.idf_b   = nu == 2 ? ub.dIdf : ua.dIdf;
@@ -2044,21 +1911,21 @@ struct Ekf : EkfBase
                 wa.valid_b = nu == 2 ? ub.pp.valid : 0;
                 wa.w_a     = ua.pp.w;
                 wa.w_b     = nu == 2 ? ub.pp.w : 0;
-                wa.model_a = la_model;
-                wa.model_b = la_model + 1;
-                wa.Gt_a    = fo[0].Gt;
-                wa.u_a     = fo[0].U;
-                wa.M_a     = fo[0].M;
-                wa.sub_a   = fo[0].sub;
-                wa.Gt_b    = fo[1].Gt;
-                wa.u_b     = fo[1].U;
-                wa.M_b     = fo[1].M;
-                wa.sub_b   = fo[1].sub;
-                wa.Y_b     = la_Y;
+                wa.model_a = la.model.get();
+                wa.model_b = la.model.get() + 1;
+                wa.Gt_a    = la.fo[0].Gt.get();
+                wa.u_a     = la.fo[0].U.get();
+                wa.M_a     = la.fo[0].M.get();
+                wa.sub_a   = la.fo[0].sub.get();
+                wa.Gt_b    = la.fo[1].Gt.get();
+                wa.u_b     = la.fo[1].U.get();
+                wa.M_b     = la.fo[1].M.get();
+                wa.sub_b   = la.fo[1].sub.get();
+                wa.Y_b     = la.Y.get();
                 wa.W1a     = wbase(wcur) + (size_t)kp * ldp;
                 wa.W1b     = wa.W1a + (size_t)ka * ldp;
                 wa.ldw     = ldp;
-                wa.wv_out  = dWv;
+                wa.wv_out  = ws.dWv.get();
                 if (la_k64 && ua.m == 32 && (nu == 1 || ub.m == 32))
                 {
                     hipLaunchKernelGGL(ekf_la_wide_f32_k64, dim3(round_up(n, kTile) / 32), dim3(128), 0, stream, wa);
@@ -2074,17 +1941,18 @@ struct Ekf : EkfBase
                 sub_valid = false;
             }
         }
-        if (!fused && ((rc = la_wide(ua, fo[0], ev_fb)) || (nu == 2 && (rc = la_wide(ub, fo[1], nullptr)))))
+        if (!fused && ((rc = la_wide(ua, la.fo[0], la.ev_fb.get())) || (nu == 2 && (rc = la_wide(ub, la.fo[1],
+                                                                                                 nullptr)))))
         {
             return rc;
         }
         pp = held;
         la_windows++;
-        if (la_stamps && la_windows == 300)
+        if (la.stamps.get() && la_windows == 300)
         {
             long long h[32];
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            CSLAM_HIP_TRY(hipMemcpy(h, la_stamps, sizeof(h), hipMemcpyDeviceToHost));
+            CSLAM_HIP_TRY(hipMemcpy(h, la.stamps.get(), sizeof(h), hipMemcpyDeviceToHost));
             fprintf(stderr, "[cslam la wide stamps, 10 ns ticks] ids+columns issue:%lld poll+DMA wait:%lld pht_a:%lld gain_a:%lld store+share W1_a:%lld pht_b+corr:%lld share+G_b:%lld gain_b:%lld store_b:%lld\n",
                     h[17] - h[16], h[18] - h[17], h[19] - h[18], h[20] - h[19], h[21] - h[20], h[22] - h[21], h[23] - h[22],
                     h[24] - h[23], h[25] - h[24]);
@@ -2204,8 +2072,8 @@ struct Ekf : EkfBase
         {
             // (pending panels: their rows for the new feature are zero, which is right -- the kernel writes values of
             // the true P, built from the pose stripe)
-            hipLaunchKernelGGL(ekf_augment_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, dX, dP, dPv, ldp, n, Z[2 * i],
-                               Z[2 * i + 1], R[0], R[1], R[2], R[3], lower);
+            hipLaunchKernelGGL(ekf_augment_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, dX.get(), dP.get(),
+                               dPv.get(), ldp, n, Z[2 * i], Z[2 * i + 1], R[0], R[1], R[2], R[3], lower);
             CSLAM_HIP_TRY(hipGetLastError());
             n += 2;
         }
@@ -2240,7 +2108,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(hFlags, dFlags, 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(hFlags.get(), dFlags.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         int f = sticky_host;
         if (hFlags[0] & kFlagZeroed)
@@ -2263,7 +2131,7 @@ struct Ekf : EkfBase
         if (clear)
         {
             sticky_host = 0;
-            CSLAM_HIP_TRY(hipMemsetAsync(dFlags, 0, 2 * sizeof(int), stream));
+            CSLAM_HIP_TRY(hipMemsetAsync(dFlags.get(), 0, 2 * sizeof(int), stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         }
         return CSLAM_OK;
@@ -2304,7 +2172,7 @@ struct Ekf : EkfBase
         }
         if (PHT)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(PHT, (size_t)n * sizeof(T), dPHT, (size_t)ldp * sizeof(T),
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(PHT, (size_t)n * sizeof(T), ws.dPHT.get(), (size_t)ldp * sizeof(T),
                                            (size_t)n * sizeof(T), (size_t)k, hipMemcpyDeviceToHost, stream));
         }
         if (W1)
@@ -2313,25 +2181,27 @@ struct Ekf : EkfBase
                                            (size_t)n * sizeof(T), (size_t)k, hipMemcpyDeviceToHost, stream));
             // its pose rows were zeroed in the store after the pose stripe took its share (ekf_pose_downdate_kernel
             // saved them): rows 0..2 <- dWv (3 x k, row c at c*k)
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(W1, (size_t)n * sizeof(T), dWv, sizeof(T), sizeof(T), (size_t)k,
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(W1, (size_t)n * sizeof(T), ws.dWv.get(), sizeof(T), sizeof(T), (size_t)k,
                                            hipMemcpyDeviceToHost, stream));
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(static_cast<T*>(W1) + 1, (size_t)n * sizeof(T), dWv + k, sizeof(T), sizeof(T),
-                                           (size_t)k, hipMemcpyDeviceToHost, stream));
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(static_cast<T*>(W1) + 2, (size_t)n * sizeof(T), dWv + 2 * k, sizeof(T), sizeof(T),
-                                           (size_t)k, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(static_cast<T*>(W1) + 1, (size_t)n * sizeof(T), ws.dWv.get() + k, sizeof(T),
+                                           sizeof(T), (size_t)k, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(static_cast<T*>(W1) + 2, (size_t)n * sizeof(T), ws.dWv.get() + 2 * k,
+                                           sizeof(T), sizeof(T), (size_t)k, hipMemcpyDeviceToHost, stream));
         }
         if (S)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(S, dbgS ? dbgS : dS, (size_t)k * k * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(S, dbgS ? dbgS : ws.dS.get(), (size_t)k * k * sizeof(T), hipMemcpyDeviceToHost,
+                                         stream));
         }
         if (G && !g_from_gt)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(G, dG, (size_t)k * k * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(G, ws.dG.get(), (size_t)k * k * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         if (G && g_from_gt) // the tuned factor kernels publish only G^T (what the gain kernel reads)
         {
             std::vector<T> Gt((size_t)k * k);
-            CSLAM_HIP_TRY(hipMemcpyAsync(Gt.data(), dbgGt ? dbgGt : dGt, Gt.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(Gt.data(), dbgGt ? dbgGt : ws.dGt.get(), Gt.size() * sizeof(T),
+                                         hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
             T* out = static_cast<T*>(G);
             for (int c = 0; c < k; c++)
@@ -2344,7 +2214,8 @@ struct Ekf : EkfBase
         }
         if (V)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(V, dbgV ? dbgV : dV, (size_t)k * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(V, dbgV ? dbgV : ws.dV.get(), (size_t)k * sizeof(T), hipMemcpyDeviceToHost,
+                                         stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -2373,10 +2244,10 @@ int Ekf<T>::ensure_tile_list(int tiles)
     {
         return rc;
     }
-    (void)hipFree(dTiles);
-    dTiles = nullptr;
-    CSLAM_HIP_TRY(hipMalloc(&dTiles, h.size() * sizeof(int2)));
-    CSLAM_HIP_TRY(hipMemcpy(dTiles, h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
+    DevBuf<int2> list;
+    CSLAM_TRY(list.alloc(h.size()));
+    dTiles = std::move(list);
+    CSLAM_HIP_TRY(hipMemcpy(dTiles.get(), h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
     tiles_built = tiles;
     n_sym_tiles = (int)h.size();
     return CSLAM_OK;
@@ -2415,11 +2286,10 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
         if (need > wb_bytes)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // (grows with n and the window: rare)
-            (void)hipFree(dWb);
-            dWb      = nullptr;
-            wb_bytes = 0;
-            const size_t cap = (size_t)2 * 3 * 32 * round_up(ncap, kTile) * 16; // every window up to 256 columns
-            CSLAM_HIP_TRY(hipMalloc(&dWb, cap));
+            const size_t  cap = (size_t)2 * 3 * 32 * round_up(ncap, kTile) * 16; // every window up to 256 columns
+            DevBuf<uint4> wb;
+            CSLAM_TRY(wb.alloc(cap / sizeof(uint4)));
+            dWb      = std::move(wb);
             wb_bytes = cap;
         }
         if ((rc = ensure_tiles_morton(tiles, stream)))
@@ -2427,7 +2297,7 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
             return rc;
         }
         hipLaunchKernelGGL(ekf_limb_split_kernel, dim3((rows + 255) / 256, kgs), dim3(256), 0, stream, W, ldp, k, rows, kgs,
-                           dWb);
+                           dWb.get());
         // (ring of 3 panel buffers, 72 KB: two workgroups per compute unit)
         limb_parity ^= 1;
 #define CSLAM_LAUNCH_PSYM5(MODE, NCH, NP, RR)                                                                          \
@@ -2440,9 +2310,9 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));               \
             attr_set = true;                                                                                           \
         }                                                                                                              \
-        hipLaunchKernelGGL((ekf_downdate_psym5_bf16<MODE, NCH, NP, RR>), dim3(G), block, (size_t)RR * 24576, stream, dP, ldp, \
-                           (const uint4*)dWb, rows, (const int2*)dTilesM, (const int*)dSegOff, dTicketX + 8 * limb_parity,  \
-                           dTicketX + 8 * (limb_parity ^ 1));                                                          \
+        hipLaunchKernelGGL((ekf_downdate_psym5_bf16<MODE, NCH, NP, RR>), dim3(G), block, (size_t)RR * 24576, stream, dP.get(), ldp, \
+                           (const uint4*)dWb.get(), rows, (const int2*)dTilesM.get(), (const int*)dSegOff.get(), dTicketX.get() + 8 * limb_parity,  \
+                           dTicketX.get() + 8 * (limb_parity ^ 1));                                                          \
     } while (0)
 #define CSLAM_LAUNCH_PSYM5R(NCH, RR)                                                                                   \
     do                                                                                                                 \
@@ -2484,12 +2354,12 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
             limb_parity ^= 1;
         }
 #define CSLAM_LAUNCH_PSYM4(MODE, NCH, KC)                                                                             \
-    hipLaunchKernelGGL((ekf_downdate_psym4_f32<MODE, NCH, KC>), dim3(G), block, 0, stream, dP, ldp, W, ldp, k,         \
-                       xq ? (const int2*)dTilesM : (const int2*)dTiles, n_sym_tiles,                                  \
-                       xq ? dTicketX + 8 * limb_parity : dTicket + (launch_parity & 1),                              \
-                       xq ? dTicketX + 8 * (limb_parity ^ 1) : dTicket + ((launch_parity + 1) & 1),                  \
-                       (unsigned long long*)nullptr, xq ? (const int*)dSegOff : (const int*)nullptr, 0u, 0u, 0u, 0u,           \
-                       la_sig_add ? la_done : (unsigned*)nullptr, la_sig_add, 1, 0)
+    hipLaunchKernelGGL((ekf_downdate_psym4_f32<MODE, NCH, KC>), dim3(G), block, 0, stream, dP.get(), ldp, W, ldp, k,         \
+                       xq ? (const int2*)dTilesM.get() : (const int2*)dTiles.get(), n_sym_tiles,                                  \
+                       xq ? dTicketX.get() + 8 * limb_parity : dTicket.get() + (launch_parity & 1),                              \
+                       xq ? dTicketX.get() + 8 * (limb_parity ^ 1) : dTicket.get() + ((launch_parity + 1) & 1),                  \
+                       (unsigned long long*)nullptr, xq ? (const int*)dSegOff.get() : (const int*)nullptr, 0u, 0u, 0u, 0u,           \
+                       la_sig_add ? la.done.get() : (unsigned*)nullptr, la_sig_add, 1, 0)
         if (k8 <= 64)
         {
             if (nt) { CSLAM_LAUNCH_PSYM4(1, 2, 32); } else { CSLAM_LAUNCH_PSYM4(0, 2, 32); }
@@ -2508,14 +2378,14 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
     else if (lower)
     {
         // any k, block-lower storage: the unpipelined persistent symmetric kernel (windows beyond 128 columns)
-        hipLaunchKernelGGL((ekf_downdate_psym_f32<64, true, false>), dim3(G), block, 0, stream, dP, ldp, W, ldp, k8, dTiles,
-                           n_sym_tiles, (long long*)nullptr);
+        hipLaunchKernelGGL((ekf_downdate_psym_f32<64, true, false>), dim3(G), block, 0, stream, dP.get(), ldp, W, ldp,
+                           k8, dTiles.get(), n_sym_tiles, (long long*)nullptr);
     }
     else
     {
         // full storage (CSLAM_STORAGE=full): the same kernel with mirror stores
-        hipLaunchKernelGGL((ekf_downdate_psym_f32<64, true, true>), dim3(G), block, 0, stream, dP, ldp, W, ldp, k8, dTiles,
-                           n_sym_tiles, (long long*)nullptr);
+        hipLaunchKernelGGL((ekf_downdate_psym_f32<64, true, true>), dim3(G), block, 0, stream, dP.get(), ldp, W, ldp,
+                           k8, dTiles.get(), n_sym_tiles, (long long*)nullptr);
     }
     CSLAM_HIP_TRY(hipGetLastError());
     return CSLAM_OK;
@@ -2528,9 +2398,10 @@ bool Ekf<float>::launch_gain_fast(int k, int n_pad, float* slot, const float* Gt
     {
         return false; // u is produced by the tuned factor kernels only
     }
-    hipLaunchKernelGGL((ekf_panel_mfma_f32<false, true>), dim3(n_pad / 32, (k + 31) / 32), dim3(64), 0, stream, dPHT, ldp, n,
-                       k, k, Gt, k, U, slot, ldp, dX, fuse_now ? (const float*)dPred : (const float*)nullptr, pp.w, dPv, ldp,
-                       M, dWv);
+    hipLaunchKernelGGL((ekf_panel_mfma_f32<false, true>), dim3(n_pad / 32, (k + 31) / 32), dim3(64), 0, stream,
+                       ws.dPHT.get(), ldp, n, k, k, Gt, k, U, slot, ldp, dX.get(),
+                       fuse_now ? (const float*)dPred.get() : (const float*)nullptr, pp.w, dPv.get(), ldp, M,
+                       ws.dWv.get());
     pose_fused_in_gain = (M != nullptr);
     return true;
 }
@@ -2540,7 +2411,7 @@ bool Ekf<float>::launch_corr_fast(int k, const float* Wp, int kc)
 {
     const int n_pad = round_up(n, kTile);
     hipLaunchKernelGGL((ekf_panel_mfma_f32<true, false>), dim3(n_pad / 32, (k + 31) / 32), dim3(64), 0, stream, Wp, ldp, n,
-                       kc, k, dY, k, nullptr, dPHT, ldp, nullptr);
+                       kc, k, ws.dY.get(), k, nullptr, ws.dPHT.get(), ldp, nullptr);
     return true;
 }
 
@@ -2549,7 +2420,7 @@ bool Ekf<double>::launch_corr_fast(int k, const double* Wp, int kc)
 {
     const int n_pad = round_up(n, kTile);
     hipLaunchKernelGGL((ekf_panel_mfma_f64<true, false>), dim3(n_pad / 16, (k + 15) / 16), dim3(64), 0, stream, Wp, ldp, n, kc,
-                       k, dY, k, nullptr, dPHT, ldp, nullptr);
+                       k, ws.dY.get(), k, nullptr, ws.dPHT.get(), ldp, nullptr);
     return true;
 }
 
@@ -2560,9 +2431,9 @@ bool Ekf<double>::launch_gain_fast(int k, int n_pad, double* slot, const double*
     {
         return false;
     }
-    hipLaunchKernelGGL((ekf_panel_mfma_f64<false, true>), dim3(n_pad / 16, (k + 15) / 16), dim3(64), 0, stream, dPHT, ldp, n, k,
-                       k, Gt, k, U, slot, ldp, dX, dPv, ldp, M, dWv, fuse_now ? (const double*)dPred : (const double*)nullptr,
-                       pp.w);
+    hipLaunchKernelGGL((ekf_panel_mfma_f64<false, true>), dim3(n_pad / 16, (k + 15) / 16), dim3(64), 0, stream,
+                       ws.dPHT.get(), ldp, n, k, k, Gt, k, U, slot, ldp, dX.get(), dPv.get(), ldp, M, ws.dWv.get(),
+                       fuse_now ? (const double*)dPred.get() : (const double*)nullptr, pp.w);
     pose_fused_in_gain = (M != nullptr);
     return true;
 }
@@ -2589,13 +2460,13 @@ int Ekf<double>::launch_downdate(const double* W, int k, hipStream_t stream)
     const size_t lds  = (size_t)(kcm == 16 ? 2 : 1) * kcm * (128 + 16 * cb) * sizeof(double); // (16: two buffers)
     if (cb == 2)
     {
-        hipLaunchKernelGGL(ekf_downdate_f64<2>, dim3(tiles_r * tiles_c), dim3(256), lds, stream, dP, ldp, W, ldp, k, tiles_r, lower,
-                           kcm);
+        hipLaunchKernelGGL(ekf_downdate_f64<2>, dim3(tiles_r * tiles_c), dim3(256), lds, stream, dP.get(), ldp, W, ldp,
+                           k, tiles_r, lower, kcm);
     }
     else
     {
-        hipLaunchKernelGGL(ekf_downdate_f64<4>, dim3(tiles_r * tiles_c), dim3(256), lds, stream, dP, ldp, W, ldp, k, tiles_r, lower,
-                           kcm);
+        hipLaunchKernelGGL(ekf_downdate_f64<4>, dim3(tiles_r * tiles_c), dim3(256), lds, stream, dP.get(), ldp, W, ldp,
+                           k, tiles_r, lower, kcm);
     }
     CSLAM_HIP_TRY(hipGetLastError());
     return CSLAM_OK;

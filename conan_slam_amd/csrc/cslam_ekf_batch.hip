@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "cslam_common.hpp"
+#include "device_owners.hpp"
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
 #include "ekf_landmark_kernels.hpp"
@@ -106,20 +107,21 @@ __global__ void __launch_bounds__(256) ekf_landmark_read_batch(const float* __re
 struct cslam_ekf_batch
 {
     int device = 0, I = 0, n = 0, ldp = 0, quirks = 0, num_cus = 0;
-    hipStream_t stream = nullptr, stream_f = nullptr;
-    float *   dX = nullptr, *dPv = nullptr, *dP = nullptr, *dW = nullptr, *dFo = nullptr, *dLa = nullptr, *dWv = nullptr;
-    unsigned* dDone  = nullptr;
-    int *     dFlags = nullptr, *dIdloc = nullptr;
-    const float** dZtab   = nullptr; // [2][I] (two generations: a run() may be enqueued while the previous one executes)
-    const int**   dIdftab = nullptr;
-    int           tab_gen = 0;
-    hipEvent_t    ev_gen[2]   = {nullptr, nullptr}; // the last kernel that reads generation g has finished
-    bool          gen_used[2] = {false, false};
+    Stream      stream_own, stream_f_own; // (declared before the buffers and events: destroyed after them)
+    hipStream_t stream = nullptr, stream_f = nullptr; // = stream_own.get(), stream_f_own.get()
+    DevBuf<float>        dX, dPv, dP, dW, dFo, dLa, dWv;
+    DevBuf<unsigned>     dDone;
+    DevBuf<int>          dFlags, dIdloc;
+    DevBuf<const float*> dZtab; // [2][I] (two generations: a run() may be enqueued while the previous one executes)
+    DevBuf<const int*>   dIdftab;
+    int                  tab_gen = 0;
+    Event                ev_gen[2];                   // the last kernel that reads generation g has finished
+    bool                 gen_used[2] = {false, false}; // ... and has been recorded
     // P-GEMM tile lists, one per row-tile count T (the map grows): list T is the union of the instances' lower-triangular
     // tiles (ti, tj) with ti < T, instance-major, at dTiles + tile_off[T].  All are built at create time and never
     // change, so a P-GEMM still in flight keeps reading the list it was launched with when n crosses a 128-row boundary.
-    int2*            dTiles  = nullptr;
-    int*             dTicket = nullptr;
+    DevBuf<int2>     dTiles;
+    DevBuf<int>      dTicket;
     std::vector<int> tile_off, tile_cnt;
     int              parity = 0;
     int              ncap   = 0; // n at max_landmarks
@@ -127,9 +129,9 @@ struct cslam_ekf_batch
     // handle's queueing model (cslam_ekf.hip, "predict / heading"), one state for all instances
     PredictArgs<float> pp{0, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0}; // the held predict
     PoseSeq<float>     pseq{};                                          // queued control steps
-    float*             dHead     = nullptr; // [I][ldp]: the column of heading steps without a map (n = 3)
-    int*               dPoseDone = nullptr; // [I]: ticket counters of ekf_pose_step_batch_kernel
-    float*             dLm       = nullptr; // landmark read outputs: 12 floats per instance and landmark of capacity
+    DevBuf<float>      dHead;     // [I][ldp]: the column of heading steps without a map (n = 3)
+    DevBuf<int>        dPoseDone; // [I]: ticket counters of ekf_pose_step_batch_kernel
+    DevBuf<float>      dLm;       // landmark read outputs: 12 floats per instance and landmark of capacity
     // per-instance controls (cslam_ekf_batch_predict_each): the held predict's (v, swa) per instance, and a ring of
     // kCtlSlots slots [kPoseSeqMax][I][2] -- one per pose-queue launch -- filled in pinned host memory, copied in on the
     // main stream and read by ekf_pose_step_batch_each_kernel.  A slot is refilled only after ev_ctl says the launch that
@@ -137,9 +139,10 @@ struct cslam_ekf_batch
     static constexpr int kCtlSlots = 4;
     bool                 pp_each  = false;
     std::vector<float>   each_v, each_swa;
-    float *              dCtl = nullptr, *hCtl = nullptr;
-    hipEvent_t           ev_ctl[kCtlSlots] = {nullptr, nullptr, nullptr, nullptr};
-    bool                 ctl_used[kCtlSlots] = {false, false, false, false};
+    DevBuf<float>        dCtl;
+    PinnedBuf<float>     hCtl;
+    Event                ev_ctl[kCtlSlots];
+    bool                 ctl_used[kCtlSlots] = {false, false, false, false}; // slot's event recorded, not waited for yet
     int                  ctl_slot = 0;
     unsigned             ctl_each = 0; // steps of pseq whose controls are in slot ctl_slot
     int           wcur = 0, kp = 0; // pending region and its columns
@@ -148,25 +151,17 @@ struct cslam_ekf_batch
     // A/B switches (env CSLAM_BATCH_WG_SIGNAL=1, CSLAM_BATCH_WIDE_PAIRS=1): the first forms of two stages, kept measurable
     int wg_signal = 0, wide_pairs = 2;
     int la_k64 = 1; // CSLAM_LA_K64=0: the general wide kernel for m = 32 too (A/B)
-    long long* dStamps = nullptr; // CSLAM_BATCH_STAMPS=1: see LaBatchWin::stamps (printed after 300 windows)
+    DevBuf<long long> dStamps; // CSLAM_BATCH_STAMPS=1: see LaBatchWin::stamps (printed after 300 windows)
     // bench support: HIP events around one P-GEMM launch in `prof_every` (an event pair costs ~11 us of stream time)
     int                                          prof_every = 0;
     long long                                    prof_seen  = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
+    std::vector<std::pair<Event, Event>>           prof_ev;
     size_t                                       prof_used = 0;
 
     static constexpr int kWcols = 128; // columns per instance and region: one window's panels
 
     size_t sW() const { return (size_t)kWcols * ldp; }
-    float* wregion(int r) const { return dW + (size_t)r * I * sW(); }
-
-    // dynamic LDS of ekf_la_chain_batch<K>: as Ekf<float>::la_chain_lds (cslam_ekf.hip) -- the workgroup's total is ~99 KB,
-    // which keeps the P-GEMM's 64 KB workgroups off its compute unit and still fits beside one wide-kernel workgroup
-    static size_t chain_lds(int K)
-    {
-        const size_t fixed = (K == 64) ? 53984 : ((K == 32) ? 15008 : 4736);
-        return std::max(la_carry_lds<float>(), (size_t)101 * 1024 - fixed);
-    }
+    float* wregion(int r) const { return dW.get() + (size_t)r * I * sW(); }
 
     int use_device()
     {
@@ -174,7 +169,7 @@ struct cslam_ekf_batch
         return CSLAM_OK;
     }
 
-    void release()
+    ~cslam_ekf_batch()
     {
         (void)hipSetDevice(device);
         if (stream)
@@ -184,56 +179,6 @@ struct cslam_ekf_batch
         if (stream_f)
         {
             (void)hipStreamSynchronize(stream_f);
-        }
-        (void)hipFree(dX);
-        (void)hipFree(dPv);
-        (void)hipFree(dP);
-        (void)hipFree(dW);
-        (void)hipFree(dFo);
-        (void)hipFree(dLa);
-        (void)hipFree(dWv);
-        (void)hipFree(dDone);
-        (void)hipFree(dFlags);
-        (void)hipFree(dIdloc);
-        (void)hipFree(dZtab);
-        (void)hipFree(dIdftab);
-        (void)hipFree(dTiles);
-        (void)hipFree(dHead);
-        (void)hipFree(dPoseDone);
-        (void)hipFree(dTicket);
-        (void)hipFree(dStamps);
-        (void)hipFree(dCtl);
-        (void)hipFree(dLm);
-        (void)hipHostFree(hCtl);
-        for (hipEvent_t& e : ev_ctl)
-        {
-            if (e)
-            {
-                (void)hipEventDestroy(e);
-                e = nullptr;
-            }
-        }
-        for (auto& e : prof_ev)
-        {
-            (void)hipEventDestroy(e.first);
-            (void)hipEventDestroy(e.second);
-        }
-        prof_ev.clear();
-        for (hipEvent_t& e : ev_gen)
-        {
-            if (e)
-            {
-                (void)hipEventDestroy(e);
-                e = nullptr;
-            }
-        }
-        if (stream)
-        {
-            (void)hipStreamDestroy(stream);
-        }
-        if (stream_f)
-        {
-            (void)hipStreamDestroy(stream_f);
         }
     }
 
@@ -259,8 +204,7 @@ struct cslam_ekf_batch
         if (getenv("CSLAM_BATCH_STAMPS"))
         {
             // 32 phase stamps, then {start, end} of up to 128 wide-kernel workgroups per instance
-            CSLAM_HIP_TRY(hipMalloc(&dStamps, (32 + (size_t)I * 256) * sizeof(long long)));
-            CSLAM_HIP_TRY(hipMemset(dStamps, 0, (32 + (size_t)I * 256) * sizeof(long long)));
+            CSLAM_TRY(dStamps.alloc_zeroed_blocking(32 + (size_t)I * 256));
         }
         hipDeviceProp_t prop;
         CSLAM_HIP_TRY(hipGetDeviceProperties(&prop, device));
@@ -271,37 +215,27 @@ struct cslam_ekf_batch
         }
         int lo = 0, hi = 0;
         CSLAM_HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        CSLAM_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        CSLAM_HIP_TRY(hipStreamCreateWithPriority(&stream_f, hipStreamNonBlocking, hi));
-        CSLAM_HIP_TRY(hipEventCreateWithFlags(&ev_gen[0], hipEventDisableTiming));
-        CSLAM_HIP_TRY(hipEventCreateWithFlags(&ev_gen[1], hipEventDisableTiming));
+        if ((rc = stream_own.create(hipStreamNonBlocking)) || (rc = stream_f_own.create_with_priority(hipStreamNonBlocking, hi)) ||
+            (rc = ev_gen[0].create(hipEventDisableTiming)) || (rc = ev_gen[1].create(hipEventDisableTiming)))
+        {
+            return rc;
+        }
+        stream   = stream_own.get();
+        stream_f = stream_f_own.get();
         const size_t L = (size_t)ldp;
-        CSLAM_HIP_TRY(hipMalloc(&dX, I * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dPv, I * 3 * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dP, I * L * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dW, 2 * I * sW() * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dFo, (size_t)I * labatch::kFoBlock * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dLa, (size_t)I * labatch::kLaBlock * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dWv, (size_t)I * 192 * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dDone, (size_t)I * labatch::kDoneBlock * sizeof(unsigned)));
-        CSLAM_HIP_TRY(hipMalloc(&dFlags, (size_t)I * 2 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dIdloc, (size_t)I * kLaMaxObs * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dZtab, (size_t)2 * I * sizeof(float*)));
-        CSLAM_HIP_TRY(hipMalloc(&dIdftab, (size_t)2 * I * sizeof(int*)));
-        CSLAM_HIP_TRY(hipMalloc(&dTicket, 2 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dHead, I * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dPoseDone, (size_t)I * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemset(dPoseDone, 0, (size_t)I * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemset(dX, 0, I * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dPv, 0, I * 3 * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dP, 0, I * L * L * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dW, 0, 2 * I * sW() * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dFo, 0, (size_t)I * labatch::kFoBlock * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dLa, 0, (size_t)I * labatch::kLaBlock * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dWv, 0, (size_t)I * 192 * sizeof(float)));
-        CSLAM_HIP_TRY(hipMemset(dDone, 0, (size_t)I * labatch::kDoneBlock * sizeof(unsigned)));
-        CSLAM_HIP_TRY(hipMemset(dFlags, 0, (size_t)I * 2 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemset(dTicket, 0, 2 * sizeof(int)));
+        if ((rc = dX.alloc_zeroed_blocking(I * L)) || (rc = dPv.alloc_zeroed_blocking(I * 3 * L)) ||
+            (rc = dP.alloc_zeroed_blocking(I * L * L)) || (rc = dW.alloc_zeroed_blocking(2 * I * sW())) ||
+            (rc = dFo.alloc_zeroed_blocking((size_t)I * labatch::kFoBlock)) ||
+            (rc = dLa.alloc_zeroed_blocking((size_t)I * labatch::kLaBlock)) ||
+            (rc = dWv.alloc_zeroed_blocking((size_t)I * 192)) ||
+            (rc = dDone.alloc_zeroed_blocking((size_t)I * labatch::kDoneBlock)) ||
+            (rc = dFlags.alloc_zeroed_blocking((size_t)I * 2)) || (rc = dIdloc.alloc((size_t)I * kLaMaxObs)) ||
+            (rc = dZtab.alloc((size_t)2 * I)) || (rc = dIdftab.alloc((size_t)2 * I)) ||
+            (rc = dTicket.alloc_zeroed_blocking(2)) || (rc = dHead.alloc(I * L)) ||
+            (rc = dPoseDone.alloc_zeroed_blocking((size_t)I)))
+        {
+            return rc;
+        }
         // the union of the instances' lower-triangular tiles, instance-major; x = row tile | instance << 16.  Tiles of
         // pure padding rows never change: list T holds the row tiles ti < T, for every T from today's n to capacity.
         const int         tiles = ldp / kTile;
@@ -323,14 +257,14 @@ struct cslam_ekf_batch
             }
             tile_cnt[T] = (int)h.size() - tile_off[T];
         }
-        CSLAM_HIP_TRY(hipMalloc(&dTiles, h.size() * sizeof(int2)));
-        CSLAM_HIP_TRY(hipMemcpy(dTiles, h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
+        CSLAM_TRY(dTiles.alloc(h.size()));
+        CSLAM_HIP_TRY(hipMemcpy(dTiles.get(), h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_batch<16>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds(16)));
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds<float>(16)));
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_batch<32>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds(32)));
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds<float>(32)));
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_batch<64>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)chain_lds(64)));
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds<float>(64)));
         return CSLAM_OK;
     }
 
@@ -351,7 +285,8 @@ struct cslam_ekf_batch
         {
             if (sig_add)
             {
-                hipLaunchKernelGGL(ekf_la_signal_batch, dim3(1), dim3(256), 0, stream, dDone, sig_add, I, labatch::kDoneBlock);
+                hipLaunchKernelGGL(ekf_la_signal_batch, dim3(1), dim3(256), 0, stream, dDone.get(), sig_add, I,
+                                   labatch::kDoneBlock);
                 CSLAM_HIP_TRY(hipGetLastError());
             }
             return CSLAM_OK;
@@ -365,7 +300,7 @@ struct cslam_ekf_batch
                                            (size_t)I, stream));
         }
         const int      T       = std::max(1, row_tiles());
-        const int2*    tl      = dTiles + tile_off[T];
+        const int2*    tl      = dTiles.get() + tile_off[T];
         const int      n_tiles = tile_cnt[T];
         const int      G       = std::min(n_tiles, 2 * (num_cus - I));
         const unsigned sPb    = (unsigned)((size_t)ldp * ldp * 4);
@@ -376,13 +311,13 @@ struct cslam_ekf_batch
         const bool timed = prof_every > 0 && (prof_seen++ % prof_every) == 0 && prof_used < prof_ev.size();
         if (timed)
         {
-            CSLAM_HIP_TRY(hipEventRecord(prof_ev[prof_used].first, stream));
+            CSLAM_HIP_TRY(hipEventRecord(prof_ev[prof_used].first.get(), stream));
         }
 #define CSLAM_LAUNCH_PSYM4B(NCH, KC)                                                                                  \
-    hipLaunchKernelGGL((ekf_downdate_psym4_f32<0, NCH, KC, false, true>), dim3(G), dim3(256), 0, stream, dP, ldp, W, ldp, \
-                       kp, tl, n_tiles, dTicket + parity, dTicket + (parity ^ 1),                  \
+    hipLaunchKernelGGL((ekf_downdate_psym4_f32<0, NCH, KC, false, true>), dim3(G), dim3(256), 0, stream, dP.get(), ldp, W, ldp, \
+                       kp, tl, n_tiles, dTicket.get() + parity, dTicket.get() + (parity ^ 1),                  \
                        (unsigned long long*)nullptr, (const int*)nullptr, sPb, sWb, p_span, w_span,                   \
-                       sig_add ? dDone : (unsigned*)nullptr, sig_add, I, (int)labatch::kDoneBlock)
+                       sig_add ? dDone.get() : (unsigned*)nullptr, sig_add, I, (int)labatch::kDoneBlock)
         if (k8 <= 64)
         {
             CSLAM_LAUNCH_PSYM4B(2, 32);
@@ -399,7 +334,7 @@ struct cslam_ekf_batch
         CSLAM_HIP_TRY(hipGetLastError());
         if (timed)
         {
-            CSLAM_HIP_TRY(hipEventRecord(prof_ev[prof_used++].second, stream));
+            CSLAM_HIP_TRY(hipEventRecord(prof_ev[prof_used++].second.get(), stream));
         }
         wcur ^= 1;
         kp = 0;
@@ -439,10 +374,10 @@ struct cslam_ekf_batch
         {
             if (ctl_each == 0 && ctl_used[ctl_slot]) // (the first step of this launch that uses the slot)
             {
-                CSLAM_HIP_TRY(hipEventSynchronize(ev_ctl[ctl_slot]));
+                CSLAM_HIP_TRY(hipEventSynchronize(ev_ctl[ctl_slot].get()));
                 ctl_used[ctl_slot] = false;
             }
-            float* hs = hCtl + ctl_slot_size() * ctl_slot + (size_t)s * I * 2;
+            float* hs = hCtl.get() + ctl_slot_size() * ctl_slot + (size_t)s * I * 2;
             for (int i = 0; i < I; i++)
             {
                 hs[2 * i]     = each_v[i];
@@ -457,18 +392,29 @@ struct cslam_ekf_batch
 
     int ensure_ctl()
     {
-        if (dCtl)
+        if (dCtl.get())
         {
             return CSLAM_OK;
         }
+        DevBuf<float>    d;
+        PinnedBuf<float> h;
+        Event            ev[kCtlSlots];
+        int              rc = d.alloc(kCtlSlots * ctl_slot_size());
+        if (rc || (rc = h.alloc(kCtlSlots * ctl_slot_size())))
+        {
+            return rc;
+        }
+        for (Event& e : ev)
+        {
+            CSLAM_TRY(e.create(hipEventDisableTiming));
+        }
         each_v.assign((size_t)I, 0.f);
         each_swa.assign((size_t)I, 0.f);
-        CSLAM_HIP_TRY(hipMalloc(&dCtl, kCtlSlots * ctl_slot_size() * sizeof(float)));
-        CSLAM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hCtl), kCtlSlots * ctl_slot_size() * sizeof(float),
-                                    hipHostMallocDefault));
-        for (hipEvent_t& e : ev_ctl)
+        dCtl = std::move(d);
+        hCtl = std::move(h);
+        for (int i = 0; i < kCtlSlots; i++)
         {
-            CSLAM_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            ev_ctl[i] = std::move(ev[i]);
         }
         return CSLAM_OK;
     }
@@ -482,20 +428,21 @@ struct cslam_ekf_batch
         const int n_pad = round_up(n, kTile);
         if (ctl_each == 0)
         {
-            hipLaunchKernelGGL(ekf_pose_step_batch_kernel<float>, dim3((n_pad + 255) / 256, I), dim3(256), 0, stream, dX, dPv,
-                               ldp, n, n_pad, pseq, wregion(wcur), (long)sW(), dHead, dPoseDone, dFlags);
+            hipLaunchKernelGGL(ekf_pose_step_batch_kernel<float>, dim3((n_pad + 255) / 256, I), dim3(256), 0, stream,
+                               dX.get(), dPv.get(), ldp, n, n_pad, pseq, wregion(wcur), (long)sW(), dHead.get(),
+                               dPoseDone.get(), dFlags.get());
             CSLAM_HIP_TRY(hipGetLastError());
         }
         else
         {
-            float* dslot = dCtl + ctl_slot_size() * ctl_slot;
-            CSLAM_HIP_TRY(hipMemcpyAsync(dslot, hCtl + ctl_slot_size() * ctl_slot, (size_t)pseq.count * I * 2 * sizeof(float),
-                                         hipMemcpyHostToDevice, stream));
-            hipLaunchKernelGGL(ekf_pose_step_batch_each_kernel<float>, dim3((n_pad + 255) / 256, I), dim3(256), 0, stream, dX,
-                               dPv, ldp, n, n_pad, pseq, PoseCtl<float>{dslot, ctl_each}, wregion(wcur), (long)sW(), dHead,
-                               dPoseDone, dFlags);
+            float* dslot = dCtl.get() + ctl_slot_size() * ctl_slot;
+            CSLAM_HIP_TRY(hipMemcpyAsync(dslot, hCtl.get() + ctl_slot_size() * ctl_slot,
+                                         (size_t)pseq.count * I * 2 * sizeof(float), hipMemcpyHostToDevice, stream));
+            hipLaunchKernelGGL(ekf_pose_step_batch_each_kernel<float>, dim3((n_pad + 255) / 256, I), dim3(256), 0,
+                               stream, dX.get(), dPv.get(), ldp, n, n_pad, pseq, PoseCtl<float>{dslot, ctl_each},
+                               wregion(wcur), (long)sW(), dHead.get(), dPoseDone.get(), dFlags.get());
             CSLAM_HIP_TRY(hipGetLastError());
-            CSLAM_HIP_TRY(hipEventRecord(ev_ctl[ctl_slot], stream)); // (after the copy and its reader)
+            CSLAM_HIP_TRY(hipEventRecord(ev_ctl[ctl_slot].get(), stream)); // (after the copy and its reader)
             ctl_used[ctl_slot] = true;
             ctl_slot           = (ctl_slot + 1) % kCtlSlots;
             ctl_each           = 0;
@@ -530,17 +477,17 @@ struct cslam_ekf_batch
         const int g = tab_gen;
         if (gen_used[g])
         {
-            CSLAM_HIP_TRY(hipEventSynchronize(ev_gen[g]));
+            CSLAM_HIP_TRY(hipEventSynchronize(ev_gen[g].get()));
         }
-        CSLAM_HIP_TRY(hipMemcpy(dZtab + (size_t)g * I, dZ, (size_t)I * sizeof(float*), hipMemcpyHostToDevice));
-        CSLAM_HIP_TRY(hipMemcpy(dIdftab + (size_t)g * I, d_idf, (size_t)I * sizeof(int*), hipMemcpyHostToDevice));
+        CSLAM_HIP_TRY(hipMemcpy(dZtab.get() + (size_t)g * I, dZ, (size_t)I * sizeof(float*), hipMemcpyHostToDevice));
+        CSLAM_HIP_TRY(hipMemcpy(dIdftab.get() + (size_t)g * I, d_idf, (size_t)I * sizeof(int*), hipMemcpyHostToDevice));
         *gen = g;
         return CSLAM_OK;
     }
 
     int inputs_done(int g)
     {
-        CSLAM_HIP_TRY(hipEventRecord(ev_gen[g], stream)); // (the chains of a window finish before its wide kernel does)
+        CSLAM_HIP_TRY(hipEventRecord(ev_gen[g].get(), stream)); // (the chains of a window finish before its wide kernel does)
         gen_used[g] = true;
         return CSLAM_OK;
     }
@@ -583,8 +530,8 @@ struct cslam_ekf_batch
         for (int f = 0; f < q; f++)
         {
             za.f = f;
-            hipLaunchKernelGGL(ekf_augment_batch_kernel<float>, dim3((n + 255) / 256, I), dim3(256), 0, stream, dX, dP, dPv, ldp,
-                               n, za, R[0], R[1], R[2], R[3]);
+            hipLaunchKernelGGL(ekf_augment_batch_kernel<float>, dim3((n + 255) / 256, I), dim3(256), 0, stream,
+                               dX.get(), dP.get(), dPv.get(), ldp, n, za, R[0], R[1], R[2], R[3]);
             CSLAM_HIP_TRY(hipGetLastError());
             n += 2;
         }
@@ -604,36 +551,36 @@ struct cslam_ekf_batch
         w.ldp      = ldp;
         w.lower    = 1;
         w.textbook = (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1;
-        w.X        = dX;
-        w.Pv       = dPv;
-        w.P        = dP;
+        w.X        = dX.get();
+        w.Pv       = dPv.get();
+        w.P        = dP.get();
         w.Wp       = wregion(wcur);
         w.sW       = (long)sW();
-        w.fo       = dFo;
-        w.la       = dLa;
-        w.wv       = dWv;
-        w.done     = dDone;
-        w.flags    = dFlags;
-        w.idloc    = dIdloc;
+        w.fo       = dFo.get();
+        w.la       = dLa.get();
+        w.wv       = dWv.get();
+        w.done     = dDone.get();
+        w.flags    = dFlags.get();
+        w.idloc    = dIdloc.get();
         w.kp       = kp;
         w.target   = target + n_blocks;
         w.seq      = ++seq;
         w.wg_signal = wg_signal;
         w.wide_direct = getenv("CSLAM_BATCH_TIMING_DIRECT") ? 1 : 0;
-        w.stamps      = dStamps;
+        w.stamps      = dStamps.get();
         w.timeout  = 20000000ull; // 0.2 s of s_memrealtime ticks: a stuck wait raises CSLAM_FACTOR_INTERNAL instead of hanging
         // 1. the factor chains first: each takes a compute unit and waits there for its instance's blocks
         if (std::max(ka, kb) <= 16)
         {
-            hipLaunchKernelGGL(ekf_la_chain_batch<16>, dim3(I), dim3(256), chain_lds(16), stream_f, w);
+            hipLaunchKernelGGL(ekf_la_chain_batch<16>, dim3(I), dim3(256), la_chain_lds<float>(16), stream_f, w);
         }
         else if (std::max(ka, kb) <= 32)
         {
-            hipLaunchKernelGGL(ekf_la_chain_batch<32>, dim3(I), dim3(256), chain_lds(32), stream_f, w);
+            hipLaunchKernelGGL(ekf_la_chain_batch<32>, dim3(I), dim3(256), la_chain_lds<float>(32), stream_f, w);
         }
         else
         {
-            hipLaunchKernelGGL(ekf_la_chain_batch<64>, dim3(I), dim3(256), chain_lds(64), stream_f, w);
+            hipLaunchKernelGGL(ekf_la_chain_batch<64>, dim3(I), dim3(256), la_chain_lds<float>(64), stream_f, w);
         }
         // 2. rows of the pending panels, then the small blocks of the current covariance (nothing may fail in between:
         //    the chains are waiting)
@@ -669,16 +616,17 @@ struct cslam_ekf_batch
         CSLAM_HIP_TRY(hipGetLastError());
         kp = ka + kb;
         windows++;
-        if (dStamps && windows == 300)
+        if (dStamps.get() && windows == 300)
         {
             long long h[32];
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            CSLAM_HIP_TRY(hipMemcpy(h, dStamps, sizeof(h), hipMemcpyDeviceToHost));
+            CSLAM_HIP_TRY(hipMemcpy(h, dStamps.get(), sizeof(h), hipMemcpyDeviceToHost));
             fprintf(stderr, "[cslam batch wide stamps, 10 ns ticks] ids+columns issue:%lld poll+DMA wait:%lld pht_a:%lld gain_a:%lld "
                             "store+share W1_a:%lld pht_b+corr:%lld share+G_b:%lld gain_b:%lld store_b:%lld\n",
                     h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5] - h[4], h[6] - h[5], h[7] - h[6], h[8] - h[7], h[9] - h[8]);
             std::vector<long long> wt((size_t)I * 256);
-            CSLAM_HIP_TRY(hipMemcpy(wt.data(), dStamps + 32, wt.size() * sizeof(long long), hipMemcpyDeviceToHost));
+            CSLAM_HIP_TRY(hipMemcpy(wt.data(), dStamps.get() + 32, wt.size() * sizeof(long long),
+                                    hipMemcpyDeviceToHost));
             const int nwg = std::min(128, round_up(n, kTile) / (32 * wide_pairs));
             long long t0  = wt[0];
             for (int i = 0; i < I; i++)
@@ -763,7 +711,6 @@ int cslam_ekf_batch_create_capacity(int instances, int max_landmarks, int n_land
     int rc    = b->init();
     if (rc)
     {
-        b->release();
         delete b;
         return rc;
     }
@@ -779,7 +726,6 @@ int cslam_ekf_batch_destroy(cslam_ekf_batch_t h)
         return CSLAM_OK;
     }
     live_engines().fetch_sub(1);
-    h->release();
     delete h;
     return CSLAM_OK;
 }
@@ -796,9 +742,9 @@ int cslam_ekf_batch_set_state(cslam_ekf_batch_t h, int instance, const float* X,
         return rc;
     }
     const size_t L  = (size_t)h->ldp;
-    float*       dX = h->dX + instance * L;
-    float*       dP = h->dP + instance * L * L;
-    float*       dV = h->dPv + instance * 3 * L;
+    float*       dX = h->dX.get() + instance * L;
+    float*       dP = h->dP.get() + instance * L * L;
+    float*       dV = h->dPv.get() + instance * 3 * L;
     CSLAM_HIP_TRY(hipMemcpyAsync(dX, X, (size_t)n * sizeof(float), hipMemcpyHostToDevice, h->stream));
     CSLAM_HIP_TRY(hipMemcpy2DAsync(dP, L * sizeof(float), P, (size_t)ldp * sizeof(float), (size_t)n * sizeof(float), (size_t)n,
                                    hipMemcpyHostToDevice, h->stream));
@@ -808,7 +754,7 @@ int cslam_ekf_batch_set_state(cslam_ekf_batch_t h, int instance, const float* X,
     {
         CSLAM_HIP_TRY(hipMemsetAsync(h->wregion(r) + instance * h->sW(), 0, h->sW() * sizeof(float), h->stream));
     }
-    CSLAM_HIP_TRY(hipMemsetAsync(h->dFlags + 2 * instance, 0, 2 * sizeof(int), h->stream));
+    CSLAM_HIP_TRY(hipMemsetAsync(h->dFlags.get() + 2 * instance, 0, 2 * sizeof(int), h->stream));
     CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
     return CSLAM_OK;
 }
@@ -856,15 +802,16 @@ int cslam_ekf_batch_get_state(cslam_ekf_batch_t h, int instance, float* X, float
     const int    n = h->n;
     if (X)
     {
-        CSLAM_HIP_TRY(hipMemcpyAsync(X, h->dX + instance * L, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(X, h->dX.get() + instance * L, (size_t)n * sizeof(float), hipMemcpyDeviceToHost,
+                                     h->stream));
     }
     if (P)
     {
-        float*    dP = h->dP + instance * L * L;
+        float*    dP = h->dP.get() + instance * L * L;
         const int g  = (n + 31) / 32;
         hipLaunchKernelGGL(ekf_mirror_upper_kernel<float>, dim3(g, g), dim3(256), 0, h->stream, dP, h->ldp, n);
         hipLaunchKernelGGL(ekf_patch_pose_kernel<float>, dim3((n + 255) / 256), dim3(256), 0, h->stream, dP,
-                           h->dPv + instance * 3 * L, h->ldp, n);
+                           h->dPv.get() + instance * 3 * L, h->ldp, n);
         CSLAM_HIP_TRY(hipGetLastError());
         CSLAM_HIP_TRY(hipMemcpy2DAsync(P, (size_t)ldp * sizeof(float), dP, L * sizeof(float), (size_t)n * sizeof(float), (size_t)n,
                                        hipMemcpyDeviceToHost, h->stream));
@@ -889,13 +836,13 @@ int cslam_ekf_batch_get_poses(cslam_ekf_batch_t h, float* x, float* pvv)
     const size_t L = (size_t)h->ldp;
     if (x)
     {
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(x, 3 * sizeof(float), h->dX, L * sizeof(float), 3 * sizeof(float), (size_t)h->I,
-                                       hipMemcpyDeviceToHost, h->stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(x, 3 * sizeof(float), h->dX.get(), L * sizeof(float), 3 * sizeof(float),
+                                       (size_t)h->I, hipMemcpyDeviceToHost, h->stream));
     }
     if (pvv) // (the stripe's columns of instance i are rows 3 i .. 3 i + 2 of the slab seen with pitch ldp)
     {
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(pvv, 3 * sizeof(float), h->dPv, L * sizeof(float), 3 * sizeof(float), (size_t)3 * h->I,
-                                       hipMemcpyDeviceToHost, h->stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(pvv, 3 * sizeof(float), h->dPv.get(), L * sizeof(float), 3 * sizeof(float),
+                                       (size_t)3 * h->I, hipMemcpyDeviceToHost, h->stream));
     }
     CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
     return CSLAM_OK;
@@ -920,15 +867,15 @@ int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, flo
     // the pending columns stay pending and every later result is the one the run would give without this read.  Every
     // writer of X, Pv, Ps and the pending store runs on the main stream (the chains on stream F hand over to the wide
     // kernel there), so the read is ordered behind them.
-    if (h->dLm == nullptr)
+    if (!h->dLm.get() && (rc = h->dLm.alloc((size_t)h->I * std::max((h->ncap - 3) / 2, 1) * 12)))
     {
-        CSLAM_HIP_TRY(hipMalloc(&h->dLm, (size_t)h->I * std::max((h->ncap - 3) / 2, 1) * 12 * sizeof(float)));
+        return rc;
     }
     const size_t c  = (size_t)h->I * count;
-    float*       ox = h->dLm, *opll = h->dLm + 2 * c, *opvl = h->dLm + 6 * c;
-    hipLaunchKernelGGL(ekf_landmark_read_batch, dim3((count + 255) / 256, h->I), dim3(256), 0, h->stream, h->dX, h->dPv, h->dP,
-                       h->ldp, h->wregion(h->wcur), (long)h->sW(), h->kp, first, count, x ? ox : nullptr,
-                       pll ? opll : nullptr, pvl ? opvl : nullptr);
+    float*       ox = h->dLm.get(), *opll = h->dLm.get() + 2 * c, *opvl = h->dLm.get() + 6 * c;
+    hipLaunchKernelGGL(ekf_landmark_read_batch, dim3((count + 255) / 256, h->I), dim3(256), 0, h->stream, h->dX.get(),
+                       h->dPv.get(), h->dP.get(), h->ldp, h->wregion(h->wcur), (long)h->sW(), h->kp, first, count,
+                       x ? ox : nullptr, pll ? opll : nullptr, pvl ? opvl : nullptr);
     CSLAM_HIP_TRY(hipGetLastError());
     if (x)
     {
@@ -962,9 +909,9 @@ int cslam_ekf_batch_trace(cslam_ekf_batch_t h, double* traces)
     std::vector<float> diag((size_t)n);
     for (int i = 0; i < h->I; i++)
     {
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(float), h->dP + i * L * L, (L + 1) * sizeof(float), sizeof(float),
-                                       (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(float), h->dPv + i * 3 * L, (L + 1) * sizeof(float), sizeof(float),
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(float), h->dP.get() + i * L * L, (L + 1) * sizeof(float),
+                                       sizeof(float), (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(diag.data(), sizeof(float), h->dPv.get() + i * 3 * L, (L + 1) * sizeof(float), sizeof(float),
                                        (size_t)3, hipMemcpyDeviceToHost, h->stream)); // the pose block lives in the stripe
         CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
         double s = 0.0;
@@ -989,7 +936,7 @@ int cslam_ekf_batch_factor_status(cslam_ekf_batch_t h, int* flags)
         return rc;
     }
     std::vector<int> f((size_t)2 * h->I);
-    CSLAM_HIP_TRY(hipMemcpy(f.data(), h->dFlags, f.size() * sizeof(int), hipMemcpyDeviceToHost));
+    CSLAM_HIP_TRY(hipMemcpy(f.data(), h->dFlags.get(), f.size() * sizeof(int), hipMemcpyDeviceToHost));
     for (int i = 0; i < h->I; i++)
     {
         flags[i] = f[2 * i];
@@ -1031,8 +978,8 @@ int cslam_ekf_batch_run(cslam_ekf_batch_t h, int steps, const double* v, const d
     {
         return rc;
     }
-    const float** zt = h->dZtab + (size_t)g * h->I;
-    const int**   it = h->dIdftab + (size_t)g * h->I;
+    const float** zt = h->dZtab.get() + (size_t)g * h->I;
+    const int**   it = h->dIdftab.get() + (size_t)g * h->I;
     const int     pw = h->predict_width();
     auto          pp = [&](int t) {
         return PredictArgs<float>{1, (float)v[t], (float)swa[t], Q[0], Q[1], Q[2], Q[3], (float)wb, (float)dt, pw};
@@ -1080,10 +1027,12 @@ int cslam_ekf_batch_set_profiling(cslam_ekf_batch_t h, int every)
     h->prof_used  = 0;
     while (every > 0 && h->prof_ev.size() < 256)
     {
-        hipEvent_t a = nullptr, b = nullptr;
-        CSLAM_HIP_TRY(hipEventCreate(&a));
-        CSLAM_HIP_TRY(hipEventCreate(&b));
-        h->prof_ev.push_back({a, b});
+        Event a, b;
+        if ((rc = a.create(hipEventDefault)) || (rc = b.create(hipEventDefault)))
+        {
+            return rc;
+        }
+        h->prof_ev.emplace_back(std::move(a), std::move(b));
     }
     return CSLAM_OK;
 }
@@ -1103,7 +1052,7 @@ int cslam_ekf_batch_get_pgemm_time(cslam_ekf_batch_t h, double* ms_sum, int* lau
     for (size_t i = 0; i < h->prof_used; i++)
     {
         float ms = 0.f;
-        CSLAM_HIP_TRY(hipEventElapsedTime(&ms, h->prof_ev[i].first, h->prof_ev[i].second));
+        CSLAM_HIP_TRY(hipEventElapsedTime(&ms, h->prof_ev[i].first.get(), h->prof_ev[i].second.get()));
         s += ms;
     }
     *ms_sum   = s;
@@ -1238,7 +1187,7 @@ int cslam_ekf_batch_update(cslam_ekf_batch_t h, const float* const* dZ, const in
     {
         return rc;
     }
-    if ((rc = h->update_window(h->dZtab + (size_t)g * h->I, h->dIdftab + (size_t)g * h->I, m, R)))
+    if ((rc = h->update_window(h->dZtab.get() + (size_t)g * h->I, h->dIdftab.get() + (size_t)g * h->I, m, R)))
     {
         return rc;
     }

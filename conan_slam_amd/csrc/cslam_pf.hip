@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "cslam_common.hpp"
+#include "device_owners.hpp"
 #include "pf_kernels.hpp"
 
 using namespace cslam;
@@ -332,7 +333,8 @@ struct PfBase
     int         np     = 0;
     int         nfcap  = 0;
     int         nf     = 0;
-    hipStream_t stream = nullptr;
+    Stream      stream_own;       // (in the base: destroyed after the buffers and events of Pf<T>)
+    hipStream_t stream = nullptr; // = stream_own.get()
 
     virtual int init()                                                                       = 0;
     virtual int set_uniform_weight(double w0)                                                 = 0;
@@ -365,85 +367,34 @@ struct PfBase
 template <typename T>
 struct Pf : PfBase
 {
-    T*      dW   = nullptr;
-    T*      dXv  = nullptr;
-    T*      dPv  = nullptr;
-    T*      dXF  = nullptr;
-    T*      dPF  = nullptr;
+    DevBuf<T>      dW, dXv, dPv, dXF, dPF;
     // the twin set the single-pass resample gathers into; the two sets are swapped after every resample call
-    T*      dXv2 = nullptr;
-    T*      dPv2 = nullptr;
-    T*      dXF2 = nullptr;
-    T*      dPF2 = nullptr;
-    T*      dObs = nullptr; // staging: Z (2*mcap T) | idf (mcap int) | normals (3*np T), filled by one copy per call
-    int*    dIdx = nullptr; // index lists of pack/unpack (max(mcap, np))
-    double* dSums = nullptr;
-    T*      dRec = nullptr; // scratch for gather_local
-    int     mcap = 0;
+    DevBuf<T>      dXv2, dPv2, dXF2, dPF2;
+    DevBuf<T>      dObs; // staging: Z (2*mcap T) | idf (mcap int) | normals (3*np T), filled by one copy per call
+    DevBuf<int>    dIdx; // index lists of pack/unpack (max(mcap, np))
+    DevBuf<double> dSums;
+    DevBuf<T>      dRec; // scratch for gather_local
+    int            mcap = 0;
 
     // Pinned staging ring.  The small host inputs of a call (Z, idf, normals, select) are copied into the next slot and
     // sent with ONE asynchronous copy, so the call returns without waiting for the stream (the caller's arrays are
     // consumed before return all the same).  The stream is drained once per lap of the ring, never per call.
     static constexpr int kStageSlots = 16;
-    char*             hStage         = nullptr;
+    PinnedBuf<char>   hStage;
     size_t            stage_slot     = 0;
     int               stage_pos      = 0;
     int               stage_inflight = 0;
-    hipEvent_t        stage_ev[kStageSlots] = {};
-    bool              stage_ev_set[kStageSlots] = {};
+    Event             stage_ev[kStageSlots]; // created (and recorded) by the first copy out of the slot
     int               stage_last = 0; // slot handed out by the last stage_slot_for()
     std::vector<char> staged; // Z || idf bytes currently in dObs (empty = unknown)
-    double*           hInfo = nullptr;
+    PinnedBuf<double> hInfo;
 
     ~Pf() override
     {
+        (void)hipSetDevice(device);
         if (stream)
         {
             (void)hipStreamSynchronize(stream);
-        }
-        (void)hipFree(dW);
-        (void)hipFree(dSumsG);
-        (void)hipFree(dWall);
-        (void)hipFree(dSelG);
-        (void)hipFree(dCumG);
-        (void)hipFree(dKeepG);
-        (void)hipFree(dSendIdx);
-        (void)hipFree(dCounts);
-        (void)hipFree(dSendBuf);
-        (void)hipFree(dRecvBuf);
-        if (hCounts)
-        {
-            (void)hipHostFree(hCounts);
-        }
-        (void)hipFree(dSel);
-        (void)hipFree(dCum);
-        (void)hipFree(dKeep);
-        (void)hipFree(dEnable);
-        (void)hipFree(dInfo);
-        (void)hipFree(dXv);
-        (void)hipFree(dPv);
-        (void)hipFree(dXF);
-        (void)hipFree(dPF);
-        (void)hipFree(dXv2);
-        (void)hipFree(dPv2);
-        (void)hipFree(dXF2);
-        (void)hipFree(dPF2);
-        (void)hipFree(dObs);
-        (void)hipFree(dIdx);
-        (void)hipFree(dSums);
-        (void)hipFree(dRec);
-        for (int i = 0; i < kStageSlots; i++)
-        {
-            if (stage_ev[i])
-            {
-                (void)hipEventDestroy(stage_ev[i]);
-            }
-        }
-        (void)hipHostFree(hStage);
-        (void)hipHostFree(hInfo);
-        if (stream)
-        {
-            (void)hipStreamDestroy(stream);
         }
     }
 
@@ -457,11 +408,11 @@ struct Pf : PfBase
     }
     int* dIdf() const
     {
-        return reinterpret_cast<int*>(reinterpret_cast<char*>(dObs) + off_idf());
+        return reinterpret_cast<int*>(reinterpret_cast<char*>(dObs.get()) + off_idf());
     }
     T* dNormals() const
     {
-        return reinterpret_cast<T*>(reinterpret_cast<char*>(dObs) + off_normals());
+        return reinterpret_cast<T*>(reinterpret_cast<char*>(dObs.get()) + off_normals());
     }
 
     int stage_slot_for(size_t bytes, char** out)
@@ -469,23 +420,22 @@ struct Pf : PfBase
         if (bytes > stage_slot)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipHostFree(hStage);
-            hStage         = nullptr;
-            size_t newsz   = std::max((bytes + 4095) / 4096 * 4096, 2 * stage_slot);
-            stage_slot     = 0;
-            CSLAM_HIP_TRY(hipHostMalloc(&hStage, newsz * kStageSlots, hipHostMallocDefault));
+            size_t          newsz = std::max((bytes + 4095) / 4096 * 4096, 2 * stage_slot);
+            PinnedBuf<char> ring;
+            CSLAM_TRY(ring.alloc(newsz * kStageSlots));
+            hStage         = std::move(ring);
             stage_slot     = newsz;
             stage_pos      = 0;
             stage_inflight = 0; // (the slots' events are all complete after the synchronisation above)
         }
         // a slot is reused one lap later: wait for the copy that read it last (long done in the steady state) instead of
         // draining the stream once per lap (which cost a ~60 us bubble every 16 calls)
-        if (stage_ev_set[stage_pos])
+        if (stage_ev[stage_pos])
         {
-            CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[stage_pos]));
+            CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[stage_pos].get()));
         }
         stage_last = stage_pos;
-        *out      = hStage + (size_t)stage_pos * stage_slot;
+        *out      = hStage.get() + (size_t)stage_pos * stage_slot;
         stage_pos = (stage_pos + 1) % kStageSlots;
         stage_inflight++;
         return CSLAM_OK;
@@ -494,12 +444,11 @@ struct Pf : PfBase
     // the copy out of the slot handed out last has been enqueued: mark it
     int stage_commit()
     {
-        if (!stage_ev_set[stage_last])
+        if (!stage_ev[stage_last])
         {
-            CSLAM_HIP_TRY(hipEventCreateWithFlags(&stage_ev[stage_last], hipEventDisableTiming));
-            stage_ev_set[stage_last] = true;
+            CSLAM_TRY(stage_ev[stage_last].create(hipEventDisableTiming));
         }
-        CSLAM_HIP_TRY(hipEventRecord(stage_ev[stage_last], stream));
+        CSLAM_HIP_TRY(hipEventRecord(stage_ev[stage_last].get(), stream));
         return CSLAM_OK;
     }
 
@@ -513,11 +462,11 @@ struct Pf : PfBase
     PfStore<T> store() const
     {
         PfStore<T> s;
-        s.w  = dW;
-        s.xv = dXv;
-        s.pv = dPv;
-        s.xf = dXF;
-        s.pf = dPF;
+        s.w  = dW.get();
+        s.xv = dXv.get();
+        s.pv = dPv.get();
+        s.xf = dXF.get();
+        s.pf = dPF.get();
         s.np = np;
         s.nf = nf;
         return s;
@@ -531,14 +480,17 @@ struct Pf : PfBase
         }
         int newm = (std::max(m, std::max(64, 2 * mcap)) + 3) / 4 * 4; // keeps the normals 16-byte aligned
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(dObs);
-        (void)hipFree(dIdx);
-        dObs = nullptr;
-        dIdx = nullptr;
-        mcap = 0;
+        DevBuf<T>   obs;
+        DevBuf<int> idx;
+        // (newm is a multiple of 4: its ints are a whole number of T)
+        int rc = obs.alloc((size_t)2 * newm + (size_t)4 * np + (size_t)newm * sizeof(int) / sizeof(T));
+        if (rc || (rc = idx.alloc((size_t)std::max(newm, np))))
+        {
+            return rc;
+        }
         staged.clear();
-        CSLAM_HIP_TRY(hipMalloc(&dObs, ((size_t)2 * newm + (size_t)4 * np) * sizeof(T) + (size_t)newm * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dIdx, (size_t)std::max(newm, np) * sizeof(int)));
+        dObs = std::move(obs);
+        dIdx = std::move(idx);
         mcap = newm;
         return CSLAM_OK;
     }
@@ -550,29 +502,19 @@ struct Pf : PfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        CSLAM_TRY(stream_own.create(hipStreamNonBlocking));
+        stream    = stream_own.get();
         size_t n1 = (size_t)np;
         size_t cf = (size_t)std::max(nfcap, 1);
-        CSLAM_HIP_TRY(hipMalloc(&dW, n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dXv, 3 * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dPv, 9 * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dXF, 2 * cf * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dPF, 4 * cf * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dSums, 2 * sizeof(double)));
-        CSLAM_HIP_TRY(hipMalloc(&dRec, n1 * (13 + 6 * cf) * sizeof(T)));
         // PF.cpp:319-341: X = 0, P = 0, empty map; w = 1/np until the driver sets the global value
-        CSLAM_HIP_TRY(hipMemsetAsync(dXv, 0, 3 * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPv, 0, 9 * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dXF, 0, 2 * cf * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPF, 0, 4 * cf * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMalloc(&dXv2, 3 * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dPv2, 9 * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dXF2, 2 * cf * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dPF2, 4 * cf * n1 * sizeof(T)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dXv2, 0, 3 * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPv2, 0, 9 * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dXF2, 0, 2 * cf * n1 * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dPF2, 0, 4 * cf * n1 * sizeof(T), stream));
+        if ((rc = dW.alloc(n1)) || (rc = dXv.alloc_zeroed(3 * n1, stream)) || (rc = dPv.alloc_zeroed(9 * n1, stream)) ||
+            (rc = dXF.alloc_zeroed(2 * cf * n1, stream)) || (rc = dPF.alloc_zeroed(4 * cf * n1, stream)) ||
+            (rc = dSums.alloc(2)) || (rc = dRec.alloc(n1 * (13 + 6 * cf))) || (rc = dXv2.alloc_zeroed(3 * n1,
+            stream)) || (rc = dPv2.alloc_zeroed(9 * n1, stream)) || (rc = dXF2.alloc_zeroed(2 * cf * n1, stream)) ||
+            (rc = dPF2.alloc_zeroed(4 * cf * n1, stream)))
+        {
+            return rc;
+        }
         rc = ensure_m(64);
         if (rc)
         {
@@ -594,7 +536,8 @@ struct Pf : PfBase
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW, np, (T)w0, 1);
+        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
+                           (T)w0, 1);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -683,7 +626,7 @@ struct Pf : PfBase
             std::memcpy(slot + off_normals(), extra, extra_bytes);
         }
         staged.clear();
-        CSLAM_HIP_TRY(hipMemcpyAsync(dObs, slot, bytes, hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dObs.get(), slot, bytes, hipMemcpyHostToDevice, stream));
         if ((rc = stage_commit()))
         {
             return rc;
@@ -713,8 +656,9 @@ struct Pf : PfBase
             return rc;
         }
         const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream, store(), dObs, dIdf(), m,
-                           R[0], R[1], R[2], R[3], dNormals(), PfPredict<T>{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0}, 0);
+        hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
+                           store(), dObs.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(), PfPredict<T>{0, (T)0,
+                           (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0}, 0);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -735,8 +679,8 @@ struct Pf : PfBase
             return rc;
         }
         const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_feature_update_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(), dObs, dIdf(),
-                           m, R[0], R[1], R[2], R[3], (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1);
+        hipLaunchKernelGGL(pf_feature_update_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(),
+                           dObs.get(), dIdf(), m, R[0], R[1], R[2], R[3], (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -761,8 +705,8 @@ struct Pf : PfBase
             return rc;
         }
         const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, q), dim3(64), 0, stream, store(), dObs, q, R[0],
-                           R[1], R[2], R[3]);
+        hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, q), dim3(64), 0, stream, store(), dObs.get(),
+                           q, R[0], R[1], R[2], R[3]);
         CSLAM_HIP_TRY(hipGetLastError());
         nf += q;
         return CSLAM_OK;
@@ -779,9 +723,9 @@ struct Pf : PfBase
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW, np, dSums);
+        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, dSums.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        CSLAM_HIP_TRY(hipMemcpyAsync(sums, dSums, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(sums, dSums.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
@@ -793,7 +737,8 @@ struct Pf : PfBase
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW, np, (T)scale, 0);
+        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
+                           (T)scale, 0);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -805,7 +750,7 @@ struct Pf : PfBase
             return fail(CSLAM_ERR_BAD_ARG, "pf_weights_device_ptr: null");
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // the caller will read it from another stream
-        *p = dW;
+        *p = dW.get();
         return CSLAM_OK;
     }
 
@@ -820,7 +765,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(w, dW, (size_t)np * sizeof(T), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(w, dW.get(), (size_t)np * sizeof(T), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
@@ -836,7 +781,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dW, w, (size_t)np * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dW.get(), w, (size_t)np * sizeof(T), hipMemcpyHostToDevice, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
@@ -869,7 +814,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dIdx, idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dIdx.get(), idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, stream));
         return CSLAM_OK;
     }
 
@@ -888,7 +833,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx, count,
+        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx.get(), count,
                            static_cast<T*>(drec));
         CSLAM_HIP_TRY(hipGetLastError());
         CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // the buffer is handed to a collective on another stream
@@ -910,7 +855,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx, count,
+        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx.get(), count,
                            static_cast<const T*>(drec));
         CSLAM_HIP_TRY(hipGetLastError());
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
@@ -925,7 +870,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx, np, dRec);
+        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx.get(), np, dRec.get());
         CSLAM_HIP_TRY(hipGetLastError());
         std::vector<int> ident((size_t)np);
         for (int i = 0; i < np; i++)
@@ -933,8 +878,9 @@ struct Pf : PfBase
             ident[i] = i;
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dIdx, ident.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx, np, dRec);
+        CSLAM_HIP_TRY(hipMemcpyAsync(dIdx.get(), ident.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice,
+                                     stream));
+        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx.get(), np, dRec.get());
         CSLAM_HIP_TRY(hipGetLastError());
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return set_uniform_weight(w_new);
@@ -943,11 +889,9 @@ struct Pf : PfBase
     // PF.cpp:473-500 for a single shard that holds the whole particle set, without leaving the device: plan
     // (sums, normalise, Neff, decision, keep[]) -> pack(keep) -> unpack(identity) -> w = 1/N, the last three gated by a
     // device flag.  One D2H of {Neff, flag} at the end, and only if the caller asks for them.
-    T*      dSel  = nullptr;
-    T*      dCum  = nullptr;
-    int*    dKeep = nullptr;
-    int*    dEnable = nullptr;
-    double* dInfo = nullptr;
+    DevBuf<T>      dSel, dCum;
+    DevBuf<int>    dKeep, dEnable;
+    DevBuf<double> dInfo;
     int resample_local(const void* select, double n_eff, int status, double* neff, int* did) override
     {
         if (!select)
@@ -959,15 +903,9 @@ struct Pf : PfBase
         {
             return rc;
         }
-        if (!dSel)
+        if ((rc = ensure_resample_buffers()))
         {
-            CSLAM_HIP_TRY(hipMalloc(&dSel, (size_t)np * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dCum, (size_t)np * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dKeep, (size_t)np * sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dEnable, sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dInfo, 4 * sizeof(double)));
-            CSLAM_HIP_TRY(hipMemsetAsync(dInfo, 0, 4 * sizeof(double), stream));
-            CSLAM_HIP_TRY(hipHostMalloc(&hInfo, 4 * sizeof(double), hipHostMallocDefault));
+            return rc;
         }
         char* slot = nullptr;
         if ((rc = stage_slot_for((size_t)np * sizeof(T), &slot)))
@@ -975,18 +913,18 @@ struct Pf : PfBase
             return rc;
         }
         std::memcpy(slot, select, (size_t)np * sizeof(T));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dSel, slot, (size_t)np * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dSel.get(), slot, (size_t)np * sizeof(T), hipMemcpyHostToDevice, stream));
         if ((rc = stage_commit()))
         {
             return rc;
         }
-        if ((rc = launch_resample(dSel, n_eff, status)))
+        if ((rc = launch_resample(dSel.get(), n_eff, status)))
         {
             return rc;
         }
         if (neff || did)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(hInfo, dInfo, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(hInfo.get(), dInfo.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
             stage_inflight = 0;
             if (neff)
@@ -1005,27 +943,16 @@ struct Pf : PfBase
     // include/cslam.h.  Everything is ordered on the handle's stream; the host reads back the two global sums (the
     // decision must be the same on every rank and drives which collectives run) and, when it resamples, the
     // 2 x world record counts of the exchange.
-    double* dSumsG   = nullptr;
-    T*      dWall    = nullptr;
-    T*      dSelG    = nullptr;
-    T*      dCumG    = nullptr; // running sum of the gathered weights (pf_keep_kernel)
-    int*    dKeepG   = nullptr;
-    int*    dSendIdx = nullptr;
-    int*    dCounts  = nullptr;
-    int*    hCounts  = nullptr;
-    T*      dSendBuf = nullptr;
-    T*      dRecvBuf = nullptr;
+    DevBuf<double>    dSumsG;
+    DevBuf<T>         dWall, dSelG;
+    DevBuf<T>         dCumG; // running sum of the gathered weights (pf_keep_kernel)
+    DevBuf<int>       dKeepG, dSendIdx, dCounts;
+    PinnedBuf<double> hCounts; // the two global sums first, later the record counts (ints from double 4 on)
+    DevBuf<T>         dSendBuf, dRecvBuf;
     int     sh_world = 0;
     int     sh_nf    = -1;
     std::vector<int> last_counts; // 2 * world record counts of the last exchange (send per destination, receive per source)
     int              last_n_send = 0;
-
-    template <typename P>
-    static void refree(P*& p)
-    {
-        (void)hipFree(p);
-        p = nullptr;
-    }
 
     // buffers of the sharded resample: everything that can fail is allocated BEFORE the first collective, so that a rank
     // never leaves its peers waiting inside one because a local allocation failed
@@ -1035,40 +962,41 @@ struct Pf : PfBase
         if (sh_world != world)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            refree(dSumsG);
-            refree(dWall);
-            refree(dSelG);
-            refree(dCumG);
-            refree(dKeepG);
-            refree(dSendIdx);
-            refree(dCounts);
-            if (hCounts)
+            DevBuf<double>    sums;
+            DevBuf<T>         wall, sel, cum;
+            DevBuf<int>       keep, send_idx, counts;
+            PinnedBuf<double> hcounts;
+            int               rc = sums.alloc(2);
+            if (rc || (rc = wall.alloc((size_t)N)) || (rc = sel.alloc((size_t)N)) || (rc = cum.alloc((size_t)N)) ||
+                (rc = keep.alloc((size_t)N)) || (rc = send_idx.alloc((size_t)N)) ||
+                (rc = counts.alloc((size_t)2 * world)) || (rc = hcounts.alloc((size_t)2 * world + 4)))
             {
-                (void)hipHostFree(hCounts);
-                hCounts = nullptr;
+                return rc;
             }
-            sh_world = 0;
-            sh_nf    = -1;
-            CSLAM_HIP_TRY(hipMalloc(&dSumsG, 2 * sizeof(double)));
-            CSLAM_HIP_TRY(hipMalloc(&dWall, (size_t)N * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dSelG, (size_t)N * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dCumG, (size_t)N * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dKeepG, (size_t)N * sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dSendIdx, (size_t)N * sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dCounts, (size_t)2 * world * sizeof(int)));
-            CSLAM_HIP_TRY(hipHostMalloc(&hCounts, ((size_t)2 * world + 4) * sizeof(double), hipHostMallocDefault));
+            dSumsG   = std::move(sums);
+            dWall    = std::move(wall);
+            dSelG    = std::move(sel);
+            dCumG    = std::move(cum);
+            dKeepG   = std::move(keep);
+            dSendIdx = std::move(send_idx);
+            dCounts  = std::move(counts);
+            hCounts  = std::move(hcounts);
             sh_world = world;
+            sh_nf    = -1; // (the record buffers below are sized by N as well)
         }
         if (sh_nf != nf)
         {
             const size_t rec = (size_t)(13 + 6 * nf);
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            refree(dSendBuf);
-            refree(dRecvBuf);
-            sh_nf = -1;
-            CSLAM_HIP_TRY(hipMalloc(&dSendBuf, (size_t)N * rec * sizeof(T))); // worst case: every slot keeps a particle of this rank
-            CSLAM_HIP_TRY(hipMalloc(&dRecvBuf, (size_t)np * rec * sizeof(T)));
-            sh_nf = nf;
+            DevBuf<T> send, recv;
+            int       rc = send.alloc((size_t)N * rec); // worst case: every slot keeps a particle of this rank
+            if (rc || (rc = recv.alloc((size_t)np * rec)))
+            {
+                return rc;
+            }
+            dSendBuf = std::move(send);
+            dRecvBuf = std::move(recv);
+            sh_nf    = nf;
         }
         return CSLAM_OK;
     }
@@ -1097,25 +1025,26 @@ struct Pf : PfBase
             return rc;
         }
         std::memcpy(slot, select, (size_t)N * sizeof(T));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dSelG, slot, (size_t)N * sizeof(T), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dSelG.get(), slot, (size_t)N * sizeof(T), hipMemcpyHostToDevice, stream));
         if ((rc = stage_commit()))
         {
             return rc;
         }
         // 1. global weight sums
-        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW, np, dSums);
+        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, dSums.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        if ((rc = c->all_reduce_sum_f64(dSums, dSumsG, 2, stream)))
+        if ((rc = c->all_reduce_sum_f64(dSums.get(), dSumsG.get(), 2, stream)))
         {
             return rc;
         }
-        double* hs = reinterpret_cast<double*>(hCounts); // (pinned; the counts use it later)
-        CSLAM_HIP_TRY(hipMemcpyAsync(hs, dSumsG, 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        double* hs = reinterpret_cast<double*>(hCounts.get()); // (pinned; the counts use it later)
+        CSLAM_HIP_TRY(hipMemcpyAsync(hs, dSumsG.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         stage_inflight = 0;
         const double ws = hs[0], ws2 = hs[1];
         // 2. w /= ws (PF.cpp:482-487), Neff = 1 / sum (w/ws)^2 (PF.cpp:549-554), the decision (PF.cpp:490)
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW, np, (T)(1.0 / ws), 0);
+        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
+                           (T)(1.0 / ws), 0);
         CSLAM_HIP_TRY(hipGetLastError());
         const double ne = (ws2 > 0.0) ? (ws * ws) / ws2 : 0.0;
         const bool   go = (ne < n_eff) && status;
@@ -1134,17 +1063,19 @@ struct Pf : PfBase
             return CSLAM_OK;
         }
         // 3. every rank plans the same keep[] from the gathered weights and the shared strata
-        if ((rc = c->all_gather(dW, dWall, (size_t)L, dt, sizeof(T), stream)))
+        if ((rc = c->all_gather(dW.get(), dWall.get(), (size_t)L, dt, sizeof(T), stream)))
         {
             return rc;
         }
-        hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, dWall, N, dSelG, dKeepG, dCumG);
+        hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, dWall.get(), N, dSelG.get(), dKeepG.get(),
+                           dCumG.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pf_exchange_plan_kernel<0>, dim3(1), dim3(256), 0, stream, dKeepG, N, L, rank, world, dSendIdx,
-                           dCounts);
+        hipLaunchKernelGGL(pf_exchange_plan_kernel<0>, dim3(1), dim3(256), 0, stream, dKeepG.get(), N, L, rank, world,
+                           dSendIdx.get(), dCounts.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        int* hc = reinterpret_cast<int*>(hCounts) + 8;
-        CSLAM_HIP_TRY(hipMemcpyAsync(hc, dCounts, (size_t)2 * world * sizeof(int), hipMemcpyDeviceToHost, stream));
+        int* hc = reinterpret_cast<int*>(hCounts.get()) + 8;
+        CSLAM_HIP_TRY(hipMemcpyAsync(hc, dCounts.get(), (size_t)2 * world * sizeof(int), hipMemcpyDeviceToHost,
+                                     stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         stage_inflight = 0;
         int n_send = 0, n_recv = 0;
@@ -1165,7 +1096,8 @@ struct Pf : PfBase
         // 4. records out of the store (before any slot is overwritten), exchange, records into the slots in order
         if (n_send > 0)
         {
-            hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(n_send), dim3(256), 0, stream, store(), dSendIdx, n_send, dSendBuf);
+            hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(n_send), dim3(256), 0, stream, store(), dSendIdx.get(), n_send,
+                               dSendBuf.get());
             CSLAM_HIP_TRY(hipGetLastError());
         }
         // the records that stay on this rank: a device copy, outside the group
@@ -1178,8 +1110,8 @@ struct Pf : PfBase
             }
             if (hc[rank] > 0)
             {
-                CSLAM_HIP_TRY(hipMemcpyAsync(dRecvBuf + roff * rec, dSendBuf + soff * rec, (size_t)hc[rank] * rec * sizeof(T),
-                                             hipMemcpyDeviceToDevice, stream));
+                CSLAM_HIP_TRY(hipMemcpyAsync(dRecvBuf.get() + roff * rec, dSendBuf.get() + soff * rec,
+                                             (size_t)hc[rank] * rec * sizeof(T), hipMemcpyDeviceToDevice, stream));
             }
         }
         if ((rc = c->group_start()))
@@ -1194,11 +1126,11 @@ struct Pf : PfBase
             {
                 if (sc > 0)
                 {
-                    rc = c->send(dSendBuf + soff * rec, sc * rec, dt, sizeof(T), r, stream);
+                    rc = c->send(dSendBuf.get() + soff * rec, sc * rec, dt, sizeof(T), r, stream);
                 }
                 if (rcv > 0 && rc == CSLAM_OK)
                 {
-                    rc = c->recv(dRecvBuf + roff * rec, rcv * rec, dt, sizeof(T), r, stream);
+                    rc = c->recv(dRecvBuf.get() + roff * rec, rcv * rec, dt, sizeof(T), r, stream);
                 }
             }
             soff += sc;
@@ -1209,7 +1141,8 @@ struct Pf : PfBase
         {
             return rc ? rc : rc_end;
         }
-        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(L), dim3(256), 0, stream, store(), (const int*)nullptr, L, dRecvBuf);
+        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(L), dim3(256), 0, stream, store(), (const int*)nullptr, L,
+                           dRecvBuf.get());
         CSLAM_HIP_TRY(hipGetLastError());
         return set_uniform_weight(1.0 / (double)N); // PF.cpp:495-499
     }
@@ -1239,7 +1172,8 @@ struct Pf : PfBase
             {
                 return rc;
             }
-            CSLAM_HIP_TRY(hipMemcpyAsync(send_idx, dSendIdx, (size_t)last_n_send * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(send_idx, dSendIdx.get(), (size_t)last_n_send * sizeof(int),
+                                         hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
             stage_inflight = 0;
         }
@@ -1249,17 +1183,18 @@ struct Pf : PfBase
     // plan (sums, normalise, Neff, decision, keep[]) -> gather -> copy back + w = 1/N, the last two gated by a device flag
     int launch_resample(const T* d_select, double n_eff, int status)
     {
-        hipLaunchKernelGGL(pf_resample_plan_kernel<T>, dim3(1), dim3(256), 0, stream, dW, np, d_select, n_eff, status, dCum,
-                           dKeep, dInfo, dEnable);
+        hipLaunchKernelGGL(pf_resample_plan_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, d_select, n_eff,
+                           status, dCum.get(), dKeep.get(), dInfo.get(), dEnable.get());
         CSLAM_HIP_TRY(hipGetLastError());
         const dim3 ggrid(13 + 6 * store().nf, (np + 255) / 256);
         const T    w_new = (T)(1.0 / (double)np);
         PfStore<T> twin  = store();
-        twin.xv          = dXv2;
-        twin.pv          = dPv2;
-        twin.xf          = dXF2;
-        twin.pf          = dPF2;
-        hipLaunchKernelGGL(pf_gather_move_kernel<T>, ggrid, dim3(256), 0, stream, store(), twin, dKeep, dEnable, w_new);
+        twin.xv          = dXv2.get();
+        twin.pv          = dPv2.get();
+        twin.xf          = dXF2.get();
+        twin.pf          = dPF2.get();
+        hipLaunchKernelGGL(pf_gather_move_kernel<T>, ggrid, dim3(256), 0, stream, store(), twin, dKeep.get(),
+                           dEnable.get(), w_new);
         CSLAM_HIP_TRY(hipGetLastError());
         std::swap(dXv, dXv2); // the twin set is the store now (whether particles moved or were copied in place)
         std::swap(dPv, dPv2);
@@ -1270,16 +1205,26 @@ struct Pf : PfBase
 
     int ensure_resample_buffers()
     {
-        if (!dSel)
+        if (dSel.get())
         {
-            CSLAM_HIP_TRY(hipMalloc(&dSel, (size_t)np * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dCum, (size_t)np * sizeof(T)));
-            CSLAM_HIP_TRY(hipMalloc(&dKeep, (size_t)np * sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dEnable, sizeof(int)));
-            CSLAM_HIP_TRY(hipMalloc(&dInfo, 4 * sizeof(double)));
-            CSLAM_HIP_TRY(hipMemsetAsync(dInfo, 0, 4 * sizeof(double), stream));
-            CSLAM_HIP_TRY(hipHostMalloc(&hInfo, 4 * sizeof(double), hipHostMallocDefault));
+            return CSLAM_OK;
         }
+        DevBuf<T>         sel, cum;
+        DevBuf<int>       keep, enable;
+        DevBuf<double>    info;
+        PinnedBuf<double> hinfo;
+        int               rc = sel.alloc((size_t)np);
+        if (rc || (rc = cum.alloc((size_t)np)) || (rc = keep.alloc((size_t)np)) || (rc = enable.alloc(1)) ||
+            (rc = info.alloc_zeroed(4, stream)) || (rc = hinfo.alloc(4)))
+        {
+            return rc;
+        }
+        dSel    = std::move(sel);
+        dCum    = std::move(cum);
+        dKeep   = std::move(keep);
+        dEnable = std::move(enable);
+        dInfo   = std::move(info);
+        hInfo   = std::move(hinfo);
         return CSLAM_OK;
     }
 
@@ -1320,12 +1265,12 @@ struct Pf : PfBase
         // (a second stream for this copy, double-buffered inputs and event hand-overs so that it runs under the previous
         // step's kernels was tried: 14.8 k instead of 16.7 k steps/s -- four more runtime calls per step cost more host
         // time than the 10 us of stream time they free)
-        CSLAM_HIP_TRY(hipMemcpyAsync(dObs, slot, bytes, hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dObs.get(), slot, bytes, hipMemcpyHostToDevice, stream));
         if ((rc = stage_commit()))
         {
             return rc;
         }
-        char*      base = reinterpret_cast<char*>(dObs);
+        char*      base = reinterpret_cast<char*>(dObs.get());
         const T*   sZ   = reinterpret_cast<const T*>(base);
         const int* sIdf = reinterpret_cast<const int*>(base + off_idf());
         const T*   sNrm = reinterpret_cast<const T*>(base + off_normals());
@@ -1375,7 +1320,7 @@ struct Pf : PfBase
         {
             return rc;
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(hInfo, dInfo, 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(hInfo.get(), dInfo.get(), 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         stage_inflight = 0;
         if (last_neff)
@@ -1407,23 +1352,25 @@ struct Pf : PfBase
         const size_t s = sizeof(T), pitch = (size_t)np * s;
         if (w)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(w, dW + i, s, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(w, dW.get() + i, s, hipMemcpyDeviceToHost, stream));
         }
         if (Xv)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(Xv, s, dXv + i, pitch, s, 3, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(Xv, s, dXv.get() + i, pitch, s, 3, hipMemcpyDeviceToHost, stream));
         }
         if (Pv)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(Pv, s, dPv + i, pitch, s, 9, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(Pv, s, dPv.get() + i, pitch, s, 9, hipMemcpyDeviceToHost, stream));
         }
         if (XF && nf > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(XF, s, dXF + i, pitch, s, (size_t)2 * nf, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(XF, s, dXF.get() + i, pitch, s, (size_t)2 * nf, hipMemcpyDeviceToHost,
+                                           stream));
         }
         if (PF && nf > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(PF, s, dPF + i, pitch, s, (size_t)4 * nf, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(PF, s, dPF.get() + i, pitch, s, (size_t)4 * nf, hipMemcpyDeviceToHost,
+                                           stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -1444,23 +1391,25 @@ struct Pf : PfBase
         const size_t s = sizeof(T), pitch = (size_t)np * s;
         if (w)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(dW + i, w, s, hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(dW.get() + i, w, s, hipMemcpyHostToDevice, stream));
         }
         if (Xv)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dXv + i, pitch, Xv, s, s, 3, hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(dXv.get() + i, pitch, Xv, s, s, 3, hipMemcpyHostToDevice, stream));
         }
         if (Pv)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dPv + i, pitch, Pv, s, s, 9, hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(dPv.get() + i, pitch, Pv, s, s, 9, hipMemcpyHostToDevice, stream));
         }
         if (XF && nfeat > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dXF + i, pitch, XF, s, s, (size_t)2 * nfeat, hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(dXF.get() + i, pitch, XF, s, s, (size_t)2 * nfeat, hipMemcpyHostToDevice,
+                                           stream));
         }
         if (PF && nfeat > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dPF + i, pitch, PF, s, s, (size_t)4 * nfeat, hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(dPF.get() + i, pitch, PF, s, s, (size_t)4 * nfeat, hipMemcpyHostToDevice,
+                                           stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         nf = nfeat; // every particle of the store carries the same number of features

@@ -22,6 +22,7 @@
 
 #include "cslam_common.hpp"
 #include "device_math.hpp"
+#include "device_owners.hpp"
 #include "sim_kernels.hpp"
 #include "../../include/cslam.h"
 
@@ -76,7 +77,8 @@ __global__ void __launch_bounds__(kSimThreads) sim_associate_table_kernel(const 
 struct SimBase
 {
     int         dtype = CSLAM_F32, device = 0, nlm = 0;
-    hipStream_t stream = nullptr;
+    Stream      stream_own;       // (in the base: destroyed after the buffers of Sim<T>)
+    hipStream_t stream = nullptr; // = stream_own.get()
     virtual ~SimBase() {}
     virtual int init(const void* LM)                                                                 = 0;
     virtual int get_observations(const void* xv, double rmax, void* Zh, int* tagsh, int* m)         = 0;
@@ -90,54 +92,39 @@ struct SimBase
 template <typename T>
 struct Sim : SimBase
 {
-    T*   dLM = nullptr;
-    T*   dZ = nullptr;
-    T*   dZF = nullptr;
-    T*   dZN = nullptr;
-    T*   dNorm = nullptr;
-    int* dTags = nullptr;
-    int* dIdf = nullptr;
-    int* dTable = nullptr;
-    int* dCount = nullptr; // [0] scan size, [1] known, [2] new
-    int  m_last = 0;
+    DevBuf<T>   dLM, dZ, dZF, dZN, dNorm;
+    DevBuf<int> dTags, dIdf, dTable;
+    DevBuf<int> dCount; // [0] scan size, [1] known, [2] new
+    int         m_last = 0;
 
     ~Sim() override
     {
         (void)hipSetDevice(device);
-        (void)hipFree(dLM);
-        (void)hipFree(dZ);
-        (void)hipFree(dZF);
-        (void)hipFree(dZN);
-        (void)hipFree(dNorm);
-        (void)hipFree(dTags);
-        (void)hipFree(dIdf);
-        (void)hipFree(dTable);
-        (void)hipFree(dCount);
         if (stream)
         {
-            (void)hipStreamDestroy(stream);
+            (void)hipStreamSynchronize(stream);
         }
     }
 
     int init(const void* LM) override
     {
         CSLAM_HIP_TRY(hipSetDevice(device));
-        CSLAM_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        int rc = stream_own.create(hipStreamNonBlocking);
+        if (rc)
+        {
+            return rc;
+        }
+        stream           = stream_own.get();
         const size_t cap = (size_t)std::max(nlm, 1);
-        CSLAM_HIP_TRY(hipMalloc(&dLM, 2 * cap * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dZ, 2 * cap * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dZF, 2 * cap * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dZN, 2 * cap * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dNorm, 2 * cap * sizeof(T)));
-        CSLAM_HIP_TRY(hipMalloc(&dTags, cap * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dIdf, cap * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dTable, cap * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dCount, 4 * sizeof(int)));
-        CSLAM_HIP_TRY(hipMemsetAsync(dTable, 0, cap * sizeof(int), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dCount, 0, 4 * sizeof(int), stream));
+        if ((rc = dLM.alloc(2 * cap)) || (rc = dZ.alloc(2 * cap)) || (rc = dZF.alloc(2 * cap)) ||
+            (rc = dZN.alloc(2 * cap)) || (rc = dNorm.alloc(2 * cap)) || (rc = dTags.alloc(cap)) ||
+            (rc = dIdf.alloc(cap)) || (rc = dTable.alloc_zeroed(cap, stream)) || (rc = dCount.alloc_zeroed(4, stream)))
+        {
+            return rc;
+        }
         if (nlm > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(dLM, LM, 2 * (size_t)nlm * sizeof(T), hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(dLM.get(), LM, 2 * (size_t)nlm * sizeof(T), hipMemcpyHostToDevice, stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -147,10 +134,10 @@ struct Sim : SimBase
     {
         CSLAM_HIP_TRY(hipSetDevice(device));
         const T* xv = static_cast<const T*>(xvv);
-        hipLaunchKernelGGL(sim_get_observations_kernel<T>, dim3(1), dim3(kSimThreads), 0, stream, dLM, nlm, xv[0], xv[1], xv[2],
-                           (T)rmax, dZ, dTags, dCount);
+        hipLaunchKernelGGL(sim_get_observations_kernel<T>, dim3(1), dim3(kSimThreads), 0, stream, dLM.get(), nlm, xv[0],
+                           xv[1], xv[2], (T)rmax, dZ.get(), dTags.get(), dCount.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        CSLAM_HIP_TRY(hipMemcpyAsync(&m_last, dCount, sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(&m_last, dCount.get(), sizeof(int), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         if (m)
         {
@@ -158,11 +145,12 @@ struct Sim : SimBase
         }
         if (m_last > 0 && Zh)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(Zh, dZ, 2 * (size_t)m_last * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(Zh, dZ.get(), 2 * (size_t)m_last * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         if (m_last > 0 && tagsh)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(tagsh, dTags, (size_t)m_last * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(tagsh, dTags.get(), (size_t)m_last * sizeof(int), hipMemcpyDeviceToHost,
+                                         stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -176,9 +164,10 @@ struct Sim : SimBase
         }
         CSLAM_HIP_TRY(hipSetDevice(device));
         const T* R = static_cast<const T*>(Rv);
-        CSLAM_HIP_TRY(hipMemcpyAsync(dNorm, normals, 2 * (size_t)m_last * sizeof(T), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL(sim_add_noise_kernel<T>, dim3((m_last + 255) / 256), dim3(256), 0, stream, dZ, dNorm, m_last,
-                           (T)std::sqrt(R[0]), (T)std::sqrt(R[3]));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dNorm.get(), normals, 2 * (size_t)m_last * sizeof(T), hipMemcpyHostToDevice,
+                                     stream));
+        hipLaunchKernelGGL(sim_add_noise_kernel<T>, dim3((m_last + 255) / 256), dim3(256), 0, stream, dZ.get(),
+                           dNorm.get(), m_last, (T)std::sqrt(R[0]), (T)std::sqrt(R[3]));
         CSLAM_HIP_TRY(hipGetLastError());
         CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // (the pageable host buffer may be reused by the caller)
         return CSLAM_OK;
@@ -187,11 +176,11 @@ struct Sim : SimBase
     int associate(int nf, void* ZFh, int* idfh, int* mf, void* ZNh, int* mn) override
     {
         CSLAM_HIP_TRY(hipSetDevice(device));
-        hipLaunchKernelGGL(sim_associate_table_kernel<T>, dim3(1), dim3(kSimThreads), 0, stream, dZ, dTags, dCount, dTable, nf,
-                           dZF, dIdf, dZN, dCount + 1);
+        hipLaunchKernelGGL(sim_associate_table_kernel<T>, dim3(1), dim3(kSimThreads), 0, stream, dZ.get(), dTags.get(),
+                           dCount.get(), dTable.get(), nf, dZF.get(), dIdf.get(), dZN.get(), dCount.get() + 1);
         CSLAM_HIP_TRY(hipGetLastError());
         int c[3] = {0, 0, 0};
-        CSLAM_HIP_TRY(hipMemcpyAsync(c, dCount, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(c, dCount.get(), 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         if (mf)
         {
@@ -203,15 +192,15 @@ struct Sim : SimBase
         }
         if (c[1] > 0 && ZFh)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(ZFh, dZF, 2 * (size_t)c[1] * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(ZFh, dZF.get(), 2 * (size_t)c[1] * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         if (c[1] > 0 && idfh)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(idfh, dIdf, (size_t)c[1] * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(idfh, dIdf.get(), (size_t)c[1] * sizeof(int), hipMemcpyDeviceToHost, stream));
         }
         if (c[2] > 0 && ZNh)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(ZNh, dZN, 2 * (size_t)c[2] * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(ZNh, dZN.get(), 2 * (size_t)c[2] * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -219,11 +208,11 @@ struct Sim : SimBase
 
     int ptrs(const void** pZF, const int** pIdf, const void** pZN, const void** pZ, const int** pTags) override
     {
-        if (pZF) *pZF = dZF;
-        if (pIdf) *pIdf = dIdf;
-        if (pZN) *pZN = dZN;
-        if (pZ) *pZ = dZ;
-        if (pTags) *pTags = dTags;
+        if (pZF) *pZF = dZF.get();
+        if (pIdf) *pIdf = dIdf.get();
+        if (pZN) *pZN = dZN.get();
+        if (pZ) *pZ = dZ.get();
+        if (pTags) *pTags = dTags.get();
         return CSLAM_OK;
     }
 
@@ -232,7 +221,7 @@ struct Sim : SimBase
         CSLAM_HIP_TRY(hipSetDevice(device));
         if (nlm > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(t, dTable, (size_t)nlm * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(t, dTable.get(), (size_t)nlm * sizeof(int), hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         }
         return CSLAM_OK;
@@ -242,7 +231,7 @@ struct Sim : SimBase
         CSLAM_HIP_TRY(hipSetDevice(device));
         if (nlm > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(dTable, t, (size_t)nlm * sizeof(int), hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(dTable.get(), t, (size_t)nlm * sizeof(int), hipMemcpyHostToDevice, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         }
         return CSLAM_OK;

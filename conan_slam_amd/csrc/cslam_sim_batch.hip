@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "cslam_common.hpp"
+#include "device_owners.hpp"
 #include "device_math.hpp"
 #include "sim_kernels.hpp"
 #include "sim_scan_view.hpp"
@@ -124,18 +125,19 @@ struct cslam_sim_batch
     struct Slot
     {
         int        m = 0, mf = 0, mn = 0, nf = 0;
-        bool       updated = false, augmented = false, ev_used = false;
-        hipEvent_t ev = nullptr;
+        bool  updated = false, augmented = false, ev_used = false;
+        Event ev;
     };
 
-    int         device = 0, nlm = 0, I = 0;
-    hipStream_t stream = nullptr;
-    float *     dLM = nullptr, *dF = nullptr; // dF: per slot 3 x 64 common floats, then ZF [I][64], ZN [I][64]
-    int *       dTable = nullptr, *dI = nullptr; // dI: per slot tags, idf, route (32 each), count (4)
-    long long*  dSeeds = nullptr;
-    const float** dZtab   = nullptr; // [kSlots][I], written once
-    const int**   dIdftab = nullptr;
-    int*        hCount = nullptr; // pinned, 4 ints
+    int                 device = 0, nlm = 0, I = 0;
+    Stream              stream_own;
+    hipStream_t         stream = nullptr; // = stream_own.get()
+    DevBuf<float>       dLM, dF;          // dF: per slot 3 x 64 common floats, then ZF [I][64], ZN [I][64]
+    DevBuf<int>         dTable, dI;       // dI: per slot tags, idf, route (32 each), count (4)
+    DevBuf<long long>   dSeeds;
+    DevBuf<const float*> dZtab; // [kSlots][I], written once
+    DevBuf<const int*>  dIdftab;
+    PinnedBuf<int>      hCount; // 4 ints
     Slot        slot[kSlots];
     int         cur = -1; // the current scan's slot, -1: none yet
     int         nf  = 0;  // table entries assigned
@@ -145,11 +147,11 @@ struct cslam_sim_batch
 
     SlotCommon common(int k) const
     {
-        float* f = dF + (size_t)k * f_stride();
-        int*   q = dI + (size_t)k * i_stride();
+        float* f = dF.get() + (size_t)k * f_stride();
+        int*   q = dI.get() + (size_t)k * i_stride();
         return SlotCommon{f, f + kScanStride, f + 2 * kScanStride, q, q + kScanMaxObs, q + 2 * kScanMaxObs, q + 3 * kScanMaxObs};
     }
-    float* zf(int k) const { return dF + (size_t)k * f_stride() + 3 * kScanStride; }
+    float* zf(int k) const { return dF.get() + (size_t)k * f_stride() + 3 * kScanStride; }
     float* zn(int k) const { return zf(k) + (size_t)I * kScanStride; }
 
     ~cslam_sim_batch()
@@ -163,45 +165,35 @@ struct cslam_sim_batch
         {
             if (s.ev)
             {
-                (void)hipEventSynchronize(s.ev); // (a consumer may still be reading the slot)
-                (void)hipEventDestroy(s.ev);
+                (void)hipEventSynchronize(s.ev.get()); // (a consumer may still be reading the slot)
             }
-        }
-        (void)hipFree(dLM);
-        (void)hipFree(dF);
-        (void)hipFree(dTable);
-        (void)hipFree(dI);
-        (void)hipFree(dSeeds);
-        (void)hipFree(dZtab);
-        (void)hipFree(dIdftab);
-        (void)hipHostFree(hCount);
-        if (stream)
-        {
-            (void)hipStreamDestroy(stream);
         }
     }
 
     int init(const float* LM, const long long* seeds)
     {
         CSLAM_HIP_TRY(hipSetDevice(device));
-        CSLAM_HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        int rc = stream_own.create(hipStreamNonBlocking);
+        if (rc)
+        {
+            return rc;
+        }
+        stream           = stream_own.get();
         const size_t cap = (size_t)std::max(nlm, 1);
-        CSLAM_HIP_TRY(hipMalloc(&dLM, 2 * cap * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dTable, cap * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dF, kSlots * f_stride() * sizeof(float)));
-        CSLAM_HIP_TRY(hipMalloc(&dI, kSlots * i_stride() * sizeof(int)));
-        CSLAM_HIP_TRY(hipMalloc(&dSeeds, (size_t)I * sizeof(long long)));
-        CSLAM_HIP_TRY(hipMalloc(&dZtab, (size_t)kSlots * I * sizeof(float*)));
-        CSLAM_HIP_TRY(hipMalloc(&dIdftab, (size_t)kSlots * I * sizeof(int*)));
-        CSLAM_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hCount), 4 * sizeof(int), hipHostMallocDefault));
-        CSLAM_HIP_TRY(hipMemsetAsync(dTable, 0, cap * sizeof(int), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dF, 0, kSlots * f_stride() * sizeof(float), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dI, 0, kSlots * i_stride() * sizeof(int), stream));
+        if ((rc = dLM.alloc(2 * cap)) || (rc = dTable.alloc_zeroed(cap, stream)) ||
+            (rc = dF.alloc_zeroed(kSlots * f_stride(), stream)) || (rc = dI.alloc_zeroed(kSlots * i_stride(),
+            stream)) || (rc = dSeeds.alloc((size_t)I)) || (rc = dZtab.alloc((size_t)kSlots * I)) ||
+            (rc = dIdftab.alloc((size_t)kSlots * I)) || (rc = hCount.alloc(4)))
+        {
+            return rc;
+        }
         if (nlm > 0)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(dLM, LM, 2 * (size_t)nlm * sizeof(float), hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(dLM.get(), LM, 2 * (size_t)nlm * sizeof(float), hipMemcpyHostToDevice,
+                                         stream));
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dSeeds, seeds, (size_t)I * sizeof(long long), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dSeeds.get(), seeds, (size_t)I * sizeof(long long), hipMemcpyHostToDevice,
+                                     stream));
         // the pointer tables of every slot, once: instance i's ZF column block and the common idf
         std::vector<const float*> zt((size_t)kSlots * I);
         std::vector<const int*>   it((size_t)kSlots * I);
@@ -213,12 +205,14 @@ struct cslam_sim_batch
                 it[(size_t)k * I + i] = common(k).idf;
             }
         }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dZtab, zt.data(), zt.size() * sizeof(float*), hipMemcpyHostToDevice, stream));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dIdftab, it.data(), it.size() * sizeof(int*), hipMemcpyHostToDevice, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dZtab.get(), zt.data(), zt.size() * sizeof(float*), hipMemcpyHostToDevice,
+                                     stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dIdftab.get(), it.data(), it.size() * sizeof(int*), hipMemcpyHostToDevice,
+                                     stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         for (Slot& s : slot)
         {
-            CSLAM_HIP_TRY(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+            CSLAM_TRY(s.ev.create(hipEventDisableTiming));
         }
         return CSLAM_OK;
     }
@@ -230,18 +224,19 @@ struct cslam_sim_batch
         Slot&     s = slot[k];
         if (s.ev_used) // the last kernel that read this slot, kSlots - 1 scans ago
         {
-            CSLAM_HIP_TRY(hipEventSynchronize(s.ev));
+            CSLAM_HIP_TRY(hipEventSynchronize(s.ev.get()));
             s.ev_used = false;
         }
         const SlotCommon c = common(k);
-        hipLaunchKernelGGL(sim_batch_scan_kernel, dim3(1), dim3(kSimThreads), 0, stream, dLM, nlm, xv[0], xv[1], xv[2], (float)rmax,
-                           dTable, nf, c);
+        hipLaunchKernelGGL(sim_batch_scan_kernel, dim3(1), dim3(kSimThreads), 0, stream, dLM.get(), nlm, xv[0], xv[1],
+                           xv[2], (float)rmax, dTable.get(), nf, c);
         CSLAM_HIP_TRY(hipGetLastError());
         const float              s0 = R ? std::sqrt(R[0]) : 0.f, s1 = R ? std::sqrt(R[3]) : 0.f;
         const unsigned long long key = (unsigned long long)(10000000ll + step) * 64ull;
-        hipLaunchKernelGGL(sim_batch_noise_kernel, dim3(I), dim3(64), 0, stream, c, dSeeds, key, R ? 1 : 0, s0, s1, zf(k), zn(k));
+        hipLaunchKernelGGL(sim_batch_noise_kernel, dim3(I), dim3(64), 0, stream, c, dSeeds.get(), key, R ? 1 : 0, s0,
+                           s1, zf(k), zn(k));
         CSLAM_HIP_TRY(hipGetLastError());
-        CSLAM_HIP_TRY(hipMemcpyAsync(hCount, c.count, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(hCount.get(), c.count, 3 * sizeof(int), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         if (hCount[0] > kScanMaxObs)
         {
@@ -305,10 +300,10 @@ int sim_batch_current(cslam_sim_batch_t s, SimScanView* v)
     v->nf        = k.nf;
     v->updated   = k.updated ? 1 : 0;
     v->augmented = k.augmented ? 1 : 0;
-    v->Ztab      = s->dZtab + (size_t)s->cur * s->I;
-    v->idftab    = s->dIdftab + (size_t)s->cur * s->I;
+    v->Ztab      = s->dZtab.get() + (size_t)s->cur * s->I;
+    v->idftab    = s->dIdftab.get() + (size_t)s->cur * s->I;
     v->ZN        = s->zn(s->cur);
-    v->consumed  = k.ev;
+    v->consumed  = k.ev.get();
     return CSLAM_OK;
 }
 
@@ -411,7 +406,8 @@ int cslam_sim_batch_get_table(cslam_sim_batch_t h, int* table)
     CSLAM_HIP_TRY(hipSetDevice(h->device));
     if (h->nlm > 0)
     {
-        CSLAM_HIP_TRY(hipMemcpyAsync(table, h->dTable, (size_t)h->nlm * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(table, h->dTable.get(), (size_t)h->nlm * sizeof(int), hipMemcpyDeviceToHost,
+                                     h->stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return CSLAM_OK;
@@ -436,7 +432,8 @@ int cslam_sim_batch_set_table(cslam_sim_batch_t h, const int* table)
     CSLAM_HIP_TRY(hipSetDevice(h->device));
     if (h->nlm > 0)
     {
-        CSLAM_HIP_TRY(hipMemcpyAsync(h->dTable, table, (size_t)h->nlm * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(h->dTable.get(), table, (size_t)h->nlm * sizeof(int), hipMemcpyHostToDevice,
+                                     h->stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
     }
     h->nf = top;

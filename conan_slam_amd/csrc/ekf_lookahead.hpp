@@ -430,6 +430,25 @@ inline size_t la_carry_lds()
     return ((size_t)KM * LD + (size_t)(3 + KM) * LB + kLaMaxObs * 10 + (3 + KM) + 4 * KM + 3 * KM) * sizeof(T) + 64;
 }
 
+// Dynamic LDS of the chain kernels <T, K> (ekf_la_chain_kernel, ekf_la_chain_batch): the carry step's arrays (in f64 the
+// factor body's arrays live in the same space), padded in f32 so that the workgroup's total LDS is ~99 KB: more than 96 KB
+// keeps the persistent P-GEMM's 64 KB workgroups off its compute unit, less than 106 KB lets it start beside ONE workgroup
+// of the wide kernel (54 KB) -- a chain kernel that found no unit before the P-GEMM filled the chip must still be able to
+// start while the wide kernel's workgroups wait for it.
+template <typename T>
+inline size_t la_chain_lds(int K)
+{
+    const size_t need = la_carry_lds<T>();
+    if (sizeof(T) == 8)
+    {
+        return std::max(need, (size_t)(K * (K + 1) + (3 + K) * (K + 1) + (K / 2) * 10 + 6 * K) * sizeof(double) +
+                                  (size_t)(K / 2 + 4) * sizeof(int) + 16);
+    }
+    // static LDS of the f32 chain kernels by K (tools/kernel_resources.py)
+    const size_t fixed = (K == 64) ? 53984 : ((K == 32) ? 15008 : 4736);
+    return std::max(need, (size_t)101 * 1024 - fixed);
+}
+
 // One workgroup of 256 threads between factor(a) and factor(b) (inside ekf_la_chain_kernel).  smem: la_carry_lds<T>() bytes.
 template <typename T>
 __device__ __forceinline__ void ekf_la_carry_body(const LaCarryArgs<T>& a, unsigned char* smem)
