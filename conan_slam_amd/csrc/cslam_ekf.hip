@@ -45,14 +45,44 @@ __global__ void ekf_la_signal_kernel(unsigned* signal, unsigned add)
         atomicAdd(signal, add);
     }
 }
+// the snapshot job a wide launch may carry (LaSnapJob): the host adds ONE workgroup to the grid for it, the last one.  It
+// copies 3 m words with plain vector loads and stores and leaves; no other workgroup looks at the job, and this one neither
+// polls for the chain nor touches a row, so the wide kernel's own critical path is what it was.
+__device__ __forceinline__ bool la_wide_snapshot(const LaSnapJob& j)
+{
+    if (j.Z == nullptr || blockIdx.x + 1 != gridDim.x)
+    {
+        return false;
+    }
+    for (int i = threadIdx.x; i < 3 * j.m; i += 128)
+    {
+        if (i < 2 * j.m)
+        {
+            j.Z_out[i] = j.Z[i];
+        }
+        else
+        {
+            j.idf_out[i - 2 * j.m] = j.idf[i - 2 * j.m];
+        }
+    }
+    return true;
+}
 // the wide half of a look-ahead window (ekf_lookahead.hpp: ekf_la_wide_body), one filter
 __global__ void __launch_bounds__(128) ekf_la_wide_f32(LaWideArgs a)
 {
+    if (la_wide_snapshot(a.snap))
+    {
+        return;
+    }
     ekf_la_wide_body<1, 0>(a);
 }
 // ... with both updates of m = 32 observations (k = 64 known at compile time)
 __global__ void __launch_bounds__(128) ekf_la_wide_f32_k64(LaWideArgs a)
 {
+    if (la_wide_snapshot(a.snap))
+    {
+        return;
+    }
     ekf_la_wide_body<1, 64>(a);
 }
 } // namespace cslam
@@ -100,6 +130,7 @@ struct EkfBase
     hipStream_t stream   = nullptr; // A: everything except the P-GEMM (= stream_own.get())
     hipStream_t stream_b = nullptr; // B: the P-GEMM (== stream when not pipelined, else stream_b_own.get())
     long long   la_windows = 0;     // look-ahead windows launched (cslam_ekf_lookahead_windows)
+    long long   stage_launches = 0; // ekf_stage_obs_kernel launches (cslam_ekf_stage_launches)
 
     virtual int init()                                                                        = 0;
     virtual int set_state(const void* X, int n, const void* P, int ldp)                        = 0;
@@ -224,6 +255,7 @@ struct Ekf : EkfBase
     ~Ekf() override
     {
         (void)hipSetDevice(device);
+        (void)la_launch_held_wide(nullptr); // (its chain kernel has run: the window ends as every other one does)
         if (stream)
         {
             (void)hipStreamSynchronize(stream);
@@ -322,6 +354,10 @@ struct Ekf : EkfBase
         if (const char* sv = getenv("CSLAM_LA_WG_SIGNAL"))
         {
             la_wg_signal = atoi(sv) ? 1 : 0;
+        }
+        if (const char* sv = getenv("CSLAM_LA_HOLD_WIDE"))
+        {
+            la_hold_wide = atoi(sv) ? 1 : 0;
         }
         if (const char* sv = getenv("CSLAM_PSYM_NT"))
         {
@@ -592,6 +628,14 @@ struct Ekf : EkfBase
 
     size_t slot_bytes(int mc) const { return (size_t)mc * (2 * sizeof(T) + sizeof(int)); }
 
+    // the next slot of the ring (ensure_m(m) has been called)
+    int stage_take_slot()
+    {
+        const int slot = stage_next;
+        stage_next     = (stage_next + 1) % kStagingSlots;
+        return slot;
+    }
+
     int ensure_m(int m)
     {
         if (m <= mcap)
@@ -632,8 +676,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        int slot = stage_next;
-        stage_next = (stage_next + 1) % kStagingSlots;
+        int slot = stage_take_slot();
         if (stage_ev[slot])
         {
             CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[slot].get()));
@@ -649,6 +692,7 @@ struct Ekf : EkfBase
             hipLaunchKernelGGL(ekf_stage_obs_kernel<T>, dim3((3 * m + 255) / 256), dim3(256), 0, stream,
                                static_cast<const T*>(Z), idf, m, reinterpret_cast<T*>(ds), reinterpret_cast<int*>(ds + zb));
             CSLAM_HIP_TRY(hipGetLastError());
+            stage_launches++;
         }
         else
         {
@@ -1497,7 +1541,20 @@ struct Ekf : EkfBase
         DevBuf<LaModel<T>> model; // [2]: predict + observation model of update a / b
         DevBuf<unsigned>   done;  // device counter: workgroups of the blocks kernels that have finished
         DevBuf<long long>  stamps; // CSLAM_LA_STAMPS=1: phase stamps of factor(a) underneath the P-GEMM (diagnostics)
+        DevBuf<int>        idf_keep; // update b's feature ids and ...
+        DevBuf<T>          z_keep;   // ... Z, copied by the rows kernel of a window whose wide launch is held
     };
+    // A window's wide launch, built but not yet submitted (la_launch_held_wide).  Everything on the host is already as if
+    // it had been launched (kp, last_slot, sub_valid, the held predict): only the device has not been told.
+    struct LaHeld
+    {
+        bool       valid = false;
+        bool       k64   = false;
+        unsigned   grid  = 0;
+        LaWideArgs wa;
+    };
+    LaHeld      la_held;
+    int         la_hold_wide = 1; // CSLAM_LA_HOLD_WIDE=0: every window launches its own wide kernel at once (A/B)
     LaUpd       la_q[2];
     int         la_n = 0;
     LaSet       la;
@@ -1555,7 +1612,9 @@ struct Ekf : EkfBase
             if ((rc = nl.XL.alloc((size_t)2 * KM)) || (rc = nl.PvL.alloc((size_t)2 * KM * 3)) ||
                 (rc = nl.PH.alloc((size_t)KM * KM)) || (rc = nl.PvLb.alloc((size_t)KM * 3)) ||
                 (rc = nl.Dbb.alloc((size_t)KM * KM)) || (rc = nl.Y.alloc((size_t)KM * KM)) ||
-                (rc = nl.model.alloc(2)) || (getenv("CSLAM_LA_STAMPS") && (rc = nl.stamps.alloc_zeroed_blocking(32))))
+                (rc = nl.model.alloc(2)) || (rc = nl.idf_keep.alloc(kLaMaxObs)) ||
+                (rc = nl.z_keep.alloc(2 * kLaMaxObs)) ||
+                (getenv("CSLAM_LA_STAMPS") && (rc = nl.stamps.alloc_zeroed_blocking(32))))
             {
                 return rc;
             }
@@ -1598,6 +1657,57 @@ struct Ekf : EkfBase
                kp_call_limit == 0;
     }
 
+    // The wide launch of a window is the last thing the window enqueues, and nothing waits for it until the next call on
+    // the handle arrives.  With CSLAM_LA_HOLD_WIDE (default) the call that completes a window therefore stops after the
+    // P-GEMM and keeps the wide launch, arguments ready, in la_held; the NEXT call that enqueues anything on the handle's
+    // streams, waits for them, or ends the handle submits it first.  All of them pass through one of four places:
+    // la_enqueue (below), la_drain (every other entry point: resolve_predict, queue_step, ensure_m, factor_status, ...),
+    // update() in front of a host-staged copy, and the destructor.  A predict is held on the host and launches
+    // nothing, so it leaves the wide held.  The order of the kernels on the main stream is exactly what it was.
+    //   What a caller may conclude from the main stream (cslam_ekf_get_streams) is also what it was.  Without the hold,
+    // the wide kernel at the end of b's call waits for the chain kernel on stream F, so a caller that has waited for the
+    // main stream knows that every reader of b's buffers has finished.  A window whose wide launch is held therefore
+    // reads b's caller buffers from main-stream kernels of b's call only (rows, blocks); the chain kernel and the held
+    // wide kernel read the engine's copies (la.z_keep / la.idf_keep, written by the rows kernel: see la_launch_window).
+    // `job`: the snapshot the launch carries (LaSnapJob), or nullptr.  On an error the launch stays held.
+    int la_launch_held_wide(const LaSnapJob* job)
+    {
+        if (!la_held.valid)
+        {
+            return CSLAM_OK;
+        }
+        if constexpr (std::is_same<T, float>::value)
+        {
+            int rc = use_device();
+            if (rc)
+            {
+                return rc;
+            }
+            if (g_engines.load() > 1) // (a second engine has appeared since: no unguarded wait inside the kernel, see g_engines)
+            {
+                CSLAM_HIP_TRY(hipStreamWaitEvent(stream, la.ev_fb.get(), 0));
+            }
+            LaWideArgs& wa = la_held.wa;
+            unsigned    g  = la_held.grid;
+            if (job != nullptr)
+            {
+                wa.snap = *job;
+                g += 1; // the workgroup that does the copy (la_wide_snapshot)
+            }
+            if (la_held.k64)
+            {
+                hipLaunchKernelGGL(ekf_la_wide_f32_k64, dim3(g), dim3(128), 0, stream, wa);
+            }
+            else
+            {
+                hipLaunchKernelGGL(ekf_la_wide_f32, dim3(g), dim3(128), 0, stream, wa);
+            }
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        la_held.valid = false;
+        return CSLAM_OK;
+    }
+
     int la_enqueue(const T* dZ, const int* dIdf, int m, const T* R, bool on_device)
     {
         // The first update of a window stays queued after this call returns, and the window reads its inputs when it
@@ -1605,15 +1715,53 @@ struct Ekf : EkfBase
         // the staging ring: every read of a caller's dZ / d_idf is enqueued during that call (cslam.h).  The snapshot
         // reaches the window's readers like a host-staged copy does: the rows and blocks kernels follow it on the main
         // stream, and the chain kernel on stream F reads Z only after the blocks kernel has released it (or, with
-        // several engines, behind that kernel's event).  (On stream F with an event wait on the main stream instead,
-        // it measured no faster: DESIGN.md.)
+        // several engines, behind that kernel's event).
+        //   In the steady state the previous window's wide launch is held (la_launch_held_wide) and is submitted here: it
+        // carries the snapshot as a side job of one extra workgroup, so the copy costs no launch of its own.  Only where
+        // no wide is held -- the first window after a drain, a predecessor on the classic path, several engines alive,
+        // CSLAM_LA_HOLD_WIDE=0 -- does ekf_stage_obs_kernel run (cslam_ekf_stage_launches counts those).  (The stage
+        // kernel on stream F with an event wait on the main stream instead measured no faster: DESIGN.md.)
+        //   The ring slot of a carried snapshot needs no event.  stage_ev[slot] protects the slot's PINNED HOST half, which
+        // the CPU rewrites outside any stream; a carried copy does not touch it (a later host-staged use of the slot still
+        // waits for the event of the slot's last host-staged use).  The DEVICE half is protected by stream order alone, as
+        // it always was: a slot comes round again kStagingSlots stages -- at least 31 windows -- later; its readers were
+        // the rows, blocks and wide kernels of its window on the main stream and that window's chain kernel on stream F,
+        // which the window's wide kernel waits for (in the kernel, or behind ev_fb) before it ends; and the writer, this
+        // window's predecessor's wide kernel, is enqueued on the main stream behind all of them.
         if (on_device && la_n == 0)
         {
-            if (int rc = stage_obs(dZ, dIdf, m, true, &dZ, &dIdf))
+            int rc = la_held.valid ? ensure_m(m) : CSLAM_OK; // (a ring that has to grow drains, and submits the held launch)
+            if (rc)
+            {
+                return rc;
+            }
+            if constexpr (std::is_same<T, float>::value)
+            {
+                if (la_held.valid)
+                {
+                    unsigned char* ds = dStage.get() + slot_bytes(mcap) * stage_take_slot();
+                    LaSnapJob      job;
+                    job.Z       = dZ;
+                    job.idf     = dIdf;
+                    job.Z_out   = reinterpret_cast<T*>(ds);
+                    job.idf_out = reinterpret_cast<int*>(ds + (size_t)m * 2 * sizeof(T));
+                    job.m       = m;
+                    if ((rc = la_launch_held_wide(&job)))
+                    {
+                        return rc;
+                    }
+                    dZ       = job.Z_out;
+                    dIdf     = job.idf_out;
+                    on_device = false; // (staged)
+                }
+            }
+            if (on_device && (rc = stage_obs(dZ, dIdf, m, true, &dZ, &dIdf)))
             {
                 return rc;
             }
         }
+        // (otherwise nothing is held here: update() submits it in front of a host-staged copy, and a window's second
+        // update follows a first one that has submitted it)
         LaUpd u;
         u.dZ   = dZ;
         u.dIdf = dIdf;
@@ -1625,7 +1773,7 @@ struct Ekf : EkfBase
         u.pp     = pp; // the held predict belongs to this update
         pp.valid = 0;
         la_q[la_n++] = u;
-        return la_n == 2 ? la_launch_window() : CSLAM_OK;
+        return la_n == 2 ? la_launch_window(true) : CSLAM_OK;
     }
 
     // the factor kernel's arguments for one update of a window: compact inputs (a local state vector of 3 + 2m entries with
@@ -1718,14 +1866,15 @@ struct Ekf : EkfBase
         return CSLAM_OK;
     }
 
-    int la_launch_window()
+    // may_hold: the caller is the update that completes the window (la_enqueue), so the wide launch may wait for the next call
+    int la_launch_window(bool may_hold = false)
     {
         const int nu = la_n;
         if (nu == 0)
         {
             return CSLAM_OK;
         }
-        la_n = 0;
+        la_n = 0; // (no wide launch is held here: the call that queued update a has submitted it)
         const LaUpd ua = la_q[0], ub = la_q[1];
         const PredictArgs<T> held = pp; // a predict accepted AFTER the queued updates stays held
         int rc = use_device();
@@ -1753,10 +1902,18 @@ struct Ekf : EkfBase
         //    launched behind the blocks kernel's event instead, see g_engines)
         const bool     safe     = g_engines.load() > 1;
         const unsigned n_blocks = (unsigned)(3 + ka + 2 * kb);
+        // hold: the wide launch waits for the next call (la_launch_held_wide).  Update b's caller buffers are then read by
+        // the rows and blocks kernels only; the chain kernel and the wide kernel read the rows kernel's copies.
+        const bool hold = may_hold && la_hold_wide && la_fused && !safe && nu == 2 && std::is_same<T, float>::value &&
+                          !la.stamps.get();
         auto launch_chain = [&]() -> int {
             LaChainArgs<T> ch;
             ch.fa   = la_factor_args(ua, la.fo[0]);
             ch.fb   = la_factor_args(nu == 2 ? ub : ua, la.fo[1]);
+            if (hold)
+            {
+                ch.fb.Z = la.z_keep.get();
+            }
             ch.du_a = la.fo[0].U.get();
             ch.du_b = la.fo[1].U.get();
             ch.nu   = nu;
@@ -1769,7 +1926,7 @@ struct Ekf : EkfBase
             ca.n       = n;
             ca.m_a     = ua.m;
             ca.m_b     = nu == 2 ? ub.m : 0;
-            ca.idf_b   = nu == 2 ? ub.dIdf : ua.dIdf;
+            ca.idf_b   = hold ? la.idf_keep.get() : (nu == 2 ? ub.dIdf : ua.dIdf);
             ca.pp_b    = nu == 2 ? ub.pp : ua.pp;
             ca.PH      = la.PH.get();
             ca.Dbb     = la.Dbb.get();
@@ -1821,6 +1978,9 @@ struct Ekf : EkfBase
         ra.PvL   = la.PvL.get();
         ra.WR    = la_WR.get();
         ra.flags = dFlags.get();
+        ra.idf_b_keep = hold ? la.idf_keep.get() : (int*)nullptr;
+        ra.Z_b        = ub.dZ;
+        ra.Z_b_keep   = hold ? la.z_keep.get() : (T*)nullptr;
         hipLaunchKernelGGL(ekf_la_rows_kernel<T>, dim3(ka + kb), dim3(128), 0, stream, ra);
         LaPrepArgs<T> pa;
         pa.P       = dP.get();
@@ -1885,10 +2045,7 @@ struct Ekf : EkfBase
             if (la_fused)
             {
                 fused = true;
-                if (safe) // (see g_engines: no waiting inside the wide kernel then)
-                {
-                    CSLAM_HIP_TRY(hipStreamWaitEvent(stream, la.ev_fb.get(), 0));
-                }
+                // (several engines alive: la_launch_held_wide puts the wait for ev_fb in front of the launch)
                 LaWideArgs wa;
                 wa.chain_done = la.done.get() + 256; // (waits for the chain kernel in the kernel: a stream event costs ~6 us here)
                 wa.seq        = la_seq;
@@ -1904,7 +2061,7 @@ struct Ekf : EkfBase
                 wa.Pv      = dPv.get();
                 wa.nu      = nu;
                 wa.idf_a   = ua.dIdf;
-                wa.idf_b   = nu == 2 ? ub.dIdf : ua.dIdf;
+                wa.idf_b   = hold ? la.idf_keep.get() : (nu == 2 ? ub.dIdf : ua.dIdf);
                 wa.ma      = ua.m;
                 wa.mb      = nu == 2 ? ub.m : 0;
                 wa.valid_a = ua.pp.valid;
@@ -1926,15 +2083,15 @@ struct Ekf : EkfBase
                 wa.W1b     = wa.W1a + (size_t)ka * ldp;
                 wa.ldw     = ldp;
                 wa.wv_out  = ws.dWv.get();
-                if (la_k64 && ua.m == 32 && (nu == 1 || ub.m == 32))
+                wa.snap    = LaSnapJob{nullptr, nullptr, nullptr, nullptr, 0};
+                la_held.wa    = wa;
+                la_held.k64   = la_k64 && ua.m == 32 && (nu == 1 || ub.m == 32);
+                la_held.grid  = (unsigned)(round_up(n, kTile) / 32);
+                la_held.valid = true;
+                if (!hold && (rc = la_launch_held_wide(nullptr)))
                 {
-                    hipLaunchKernelGGL(ekf_la_wide_f32_k64, dim3(round_up(n, kTile) / 32), dim3(128), 0, stream, wa);
+                    return rc;
                 }
-                else
-                {
-                    hipLaunchKernelGGL(ekf_la_wide_f32, dim3(round_up(n, kTile) / 32), dim3(128), 0, stream, wa);
-                }
-                CSLAM_HIP_TRY(hipGetLastError());
                 last_slot = nullptr; // (PHT is not materialised on this path: nothing for debug_last_update)
                 last_k    = 0;
                 kp += ka + kb;
@@ -1963,7 +2120,7 @@ struct Ekf : EkfBase
     }
 
     // every call that needs the state as of the last update() goes through here first
-    int la_drain() override { return la_n ? la_launch_window() : CSLAM_OK; }
+    int la_drain() override { return la_n ? la_launch_window() : la_launch_held_wide(nullptr); }
 
     int update(const void* Zv, int m, const void* Rv, const int* idf, int batch, bool on_device) override
     {
@@ -1993,7 +2150,8 @@ struct Ekf : EkfBase
                     return fail(CSLAM_ERR_BAD_ARG, "update: idf[%d]=%d outside 1..%d", i, idf[i], nf);
                 }
             }
-            if ((rc = stage_obs(Zv, idf, m, false, &dZ, &dIdf)))
+            // (a held wide launch keeps its place on the main stream: in front of this update's copy)
+            if ((rc = la_launch_held_wide(nullptr)) || (rc = stage_obs(Zv, idf, m, false, &dZ, &dIdf)))
             {
                 return rc;
             }
@@ -2796,6 +2954,17 @@ int cslam_ekf_lookahead_windows(cslam_ekf_t h, long long* windows)
         return fail(CSLAM_ERR_BAD_ARG, "lookahead_windows: null");
     }
     *windows = B(h)->la_windows;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_stage_launches(cslam_ekf_t h, long long* launches)
+{
+    CSLAM_NEED(h);
+    if (!launches)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "stage_launches: null");
+    }
+    *launches = B(h)->stage_launches;
     return CSLAM_OK;
 }
 

@@ -63,6 +63,11 @@ struct LaRowsArgs
     int        ldw, kp, kpad;
     T *        XL, *PvL, *WR;
     int*       flags;
+    // single filter only (ekf_la_rows_kernel), when the window's wide launch is held: the engine's own copies of update
+    // b's inputs -- ids (m_b) and Z (2 m_b = rb values) -- for every reader that is not on the main stream; or nullptr
+    int*       idf_b_keep;
+    const T*   Z_b;
+    T*         Z_b_keep;
 };
 
 template <typename T>
@@ -106,6 +111,20 @@ __device__ __forceinline__ void ekf_la_rows_body(const LaRowsArgs<T>& a)
 template <typename T>
 __global__ void __launch_bounds__(128) ekf_la_rows_kernel(LaRowsArgs<T> a)
 {
+    // When the window's wide launch is held back until the next call (cslam_ekf.hip: la_launch_held_wide), update b's
+    // caller buffers may be read by main-stream kernels of b's own call only: the held wide kernel would read the ids one
+    // call late, and the chain kernel on stream F (which reads Z_b and the ids) is no longer waited for by anything on
+    // the main stream within that call.  So slot s of update b keeps Z_b[s] (rb = 2 m_b slots: one value each) and every
+    // observation's first slot keeps its id, here, and those two kernels read the copies.
+    const int sb = (int)blockIdx.x - a.ra;
+    if (a.idf_b_keep != nullptr && sb >= 0 && threadIdx.x == 5)
+    {
+        a.Z_b_keep[sb] = a.Z_b[sb];
+        if ((sb & 1) == 0)
+        {
+            a.idf_b_keep[sb >> 1] = a.idf_b[sb >> 1];
+        }
+    }
     ekf_la_rows_body<T>(a);
 }
 
@@ -870,6 +889,18 @@ __global__ void __launch_bounds__(256) ekf_la_chain_kernel(LaChainArgs<T> a)
 // block follows the gain kernel's rule (the thread of the larger index applies its increment to both (r, c) and (c, r)).
 // grid = n_pad / 32 workgroups of 128 threads.
 // ------------------------------------------------------------------------------------------------
+// Side job of a single filter's wide launch (ekf_la_wide_f32 / _k64 in cslam_ekf.hip; the batched engine has none): the
+// snapshot of the NEXT window's first update -- Z (2 m values) and idf (m ids) from the caller's buffers into a slot of
+// the staging ring -- done by one extra workgroup, the last of the grid, which takes no part in the wide kernel itself.
+struct LaSnapJob
+{
+    const float* Z; // nullptr: no job (and no extra workgroup)
+    const int*   idf;
+    float*       Z_out;
+    int*         idf_out;
+    int          m;
+};
+
 struct LaWideArgs
 {
     const float* P;
@@ -892,6 +923,7 @@ struct LaWideArgs
     int*            flags;
     long long*      stamps; // diagnostics (CSLAM_LA_STAMPS): s_memrealtime at phase boundaries of one workgroup, or nullptr
     long long*      wg_times; // diagnostics (CSLAM_BATCH_STAMPS): {start, end} of every workgroup (s_memrealtime), or nullptr
+    LaSnapJob       snap;     // single filter only; the batched engine's kernels never read it
 };
 
 __device__ __forceinline__ int la_q_of(int t, int r, int lh)

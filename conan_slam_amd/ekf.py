@@ -125,6 +125,19 @@ class EKF:
         check(self._L.cslam_ekf_lookahead_windows(self._h, C.byref(w)))
         return w.value
 
+    def streams(self):
+        """(chain stream, P-GEMM stream) of the handle as integer hipStream_t values (cslam_ekf_get_streams): for callers
+        that order their own work, or the reuse of their input buffers, against the engine's"""
+        a, b = C.c_void_p(None), C.c_void_p(None)
+        check(self._L.cslam_ekf_get_streams(self._h, C.byref(a), C.byref(b)))
+        return a.value or 0, b.value or 0
+
+    def stage_launches(self) -> int:
+        """launches of the kernel that snapshots a queued update's device inputs (cslam_ekf_stage_launches)"""
+        w = C.c_longlong(0)
+        check(self._L.cslam_ekf_stage_launches(self._h, C.byref(w)))
+        return w.value
+
     def landmarks(self, first: int = 1, count: int = None):
         """(x [c, 2], P [c, 2, 2], Pvl [c, 3, 2]) of landmarks first .. first + c - 1 (1-based; count None: to the
         last): means, marginal 2 x 2 blocks and pose-landmark blocks P[0:3, fx:fx+2], read without applying the pending

@@ -176,6 +176,11 @@ int cslam_ekf_get_streams(cslam_ekf_t h, void** chain_stream, void** pgemm_strea
  * handle has launched so far: lets a caller or a test confirm which schedule ran. */
 int cslam_ekf_lookahead_windows(cslam_ekf_t h, long long* windows);
 
+/* Launches of the kernel that snapshots a queued update's device-resident inputs into the handle's staging ring.  In a
+ * run of look-ahead windows only the first window after a drain needs one: from then on the previous window's wide
+ * kernel carries the copy (CSLAM_LA_HOLD_WIDE=0: every window).  Lets a test confirm which of the two ran. */
+int cslam_ekf_stage_launches(cslam_ekf_t h, long long* launches);
+
 /* Cap on the workgroups of the persistent covariance-downdate kernel (0 = default: two per compute unit, i.e. the
  * whole chip).  For several filter instances that run side by side on one GPU (Monte-Carlo runs, one stream each): with
  * the default every instance's P-GEMM occupies all compute units for its duration and the other instances' small
