@@ -4,64 +4,15 @@ import numpy as np
 import pytest
 
 from helpers import assert_close
+# the builders live in pf_builders.py: one copy for this file, test_pf_edges_gpu.py and test_adapter_gpu.py
+from pf_builders import DTYPES, TOL
+from pf_builders import compare as _compare
+from pf_builders import obs_for as _obs_for
+from pf_builders import random_particles as _random_particles
+from pf_builders import shard_from as _shard_from
 from pyoracle import Oracle, REF_EXACT, TEXTBOOK
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [np.float32, np.float64]
-TOL = {np.dtype(np.float32): 2e-5, np.dtype(np.float64): 1e-12}
-
-
-def _random_particles(np_, nf, dtype, seed=0):
-    """Well-conditioned particles around a common pose with nf mapped features each."""
-    rng = np.random.default_rng(seed)
-    parts = []
-    for _ in range(np_):
-        Xv = np.array([rng.normal(0, 2.0), rng.normal(0, 2.0), rng.normal(0.2, 0.05)], dtype=dtype)
-        A = rng.normal(size=(3, 3)) * np.array([0.3, 0.3, 0.02])[:, None]
-        Pv = np.asfortranarray((A @ A.T + np.diag([0.05, 0.05, 1e-4])).astype(dtype))
-        XF = np.asfortranarray(rng.uniform(-300, 300, size=(2, nf)).astype(dtype))
-        PF = np.zeros((4, nf), dtype=dtype, order="F")
-        for f in range(nf):
-            B = rng.normal(size=(2, 2)) * 0.5
-            PF[:, f] = (B @ B.T + 0.2 * np.eye(2)).reshape(-1, order="F")
-        w = dtype(rng.uniform(0.5, 1.5) / np_)
-        parts.append([w, Xv, Pv, XF, PF])
-    return parts
-
-
-def _shard_from(parts, nfcap, dtype, quirks=REF_EXACT):
-    from conan_slam_amd.pf import ParticleShard
-
-    sh = ParticleShard(len(parts), nfcap, dtype=dtype, quirks=quirks)
-    for i, (w, Xv, Pv, XF, PF) in enumerate(parts):
-        sh.set_particle(i, w, Xv, Pv, XF, PF)
-    return sh
-
-
-def _obs_for(parts, idf, dtype, seed=3):
-    """Observations of the listed features as seen from the mean particle pose (+ noise)."""
-    rng = np.random.default_rng(seed)
-    X = np.mean([p[1] for p in parts], axis=0).astype(np.float64)
-    XF = parts[0][3].astype(np.float64)
-    Z = np.zeros((2, len(idf)))
-    for i, f in enumerate(idf):
-        dx, dy = XF[0, f - 1] - X[0], XF[1, f - 1] - X[1]
-        Z[0, i] = np.hypot(dx, dy) + rng.normal() * 0.2
-        Z[1, i] = np.arctan2(dy, dx) - X[2] + rng.normal() * 0.01
-    return np.asfortranarray(Z.astype(dtype))
-
-
-def _compare(sh, parts, dtype, tag, wtol=None):
-    tol = TOL[np.dtype(dtype)]
-    for i, (w, Xv, Pv, XF, PF) in enumerate(parts):
-        gw, gX, gP, gXF, gPF = sh.get_particle(i)
-        assert_close(f"{tag} Xv[{i}]", gX, Xv, tol)
-        assert_close(f"{tag} Pv[{i}]", gP, Pv, tol)
-        assert_close(f"{tag} XF[{i}]", gXF, XF, tol)
-        assert_close(f"{tag} PF[{i}]", gPF, PF, tol)
-        rel = abs(float(gw) - float(w)) / max(abs(float(w)), 1e-300)
-        assert rel <= (wtol if wtol is not None else 50 * tol), (tag, i, float(gw), float(w))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
