@@ -37,6 +37,8 @@ LANDMARK_SYMBOLS = ("cslam_ekf_get_landmarks", "cslam_ekf_batch_get_landmarks")
 _PROTOTYPES = {
     "cslam_ekf_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     "cslam_ekf_batch_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    # launches of the look-ahead windows' rows kernel (zero where the row-major panel mirror serves the blocks kernel)
+    "cslam_ekf_rows_launches": [C.c_void_p, C.POINTER(C.c_longlong)],
     # the batched scan generator and the two batch calls that consume its scans
     "cslam_sim_batch_create": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_void_p)],
     "cslam_sim_batch_destroy": [C.c_void_p],

@@ -85,6 +85,23 @@ __global__ void __launch_bounds__(128) ekf_la_wide_f32_k64(LaWideArgs a)
     }
     ekf_la_wide_body<1, 64>(a);
 }
+
+// ... and the same kernel leaving the row-major mirror WT of both panels behind (ekf_la_wide_body: MIRROR)
+__global__ void __launch_bounds__(128) ekf_la_wide_f32_k64m(LaWideArgs a, float* WT)
+{
+    if (la_wide_snapshot(a.snap))
+    {
+        return;
+    }
+    ekf_la_wide_body<1, 64, 1>(a, WT);
+}
+
+// the blocks kernel that reads the panel rows from that mirror and needs no rows kernel (ekf_la_blocks_mirror_body);
+// the grid of ekf_la_blocks_kernel, 256 threads
+__global__ void __launch_bounds__(256) ekf_la_blocks_mirror_kernel(LaPrepArgs<float> a, LaMirrorArgs mi)
+{
+    ekf_la_blocks_mirror_body(a, mi);
+}
 } // namespace cslam
 
 using namespace cslam;
@@ -131,6 +148,7 @@ struct EkfBase
     hipStream_t stream_b = nullptr; // B: the P-GEMM (== stream when not pipelined, else stream_b_own.get())
     long long   la_windows = 0;     // look-ahead windows launched (cslam_ekf_lookahead_windows)
     long long   stage_launches = 0; // ekf_stage_obs_kernel launches (cslam_ekf_stage_launches)
+    long long   rows_launches = 0;  // ekf_la_rows_kernel launches (cslam_ekf_rows_launches)
 
     virtual int init()                                                                        = 0;
     virtual int set_state(const void* X, int n, const void* P, int ldp)                        = 0;
@@ -359,6 +377,10 @@ struct Ekf : EkfBase
         {
             la_hold_wide = atoi(sv) ? 1 : 0;
         }
+        if (const char* sv = getenv("CSLAM_LA_MIRROR"))
+        {
+            la_mirror = atoi(sv) ? 1 : 0;
+        }
         if (const char* sv = getenv("CSLAM_PSYM_NT"))
         {
             psym_nt = atoi(sv) ? 1 : 0;
@@ -425,6 +447,7 @@ struct Ekf : EkfBase
         hd_cols[0] = hd_cols[1] = 0;
         wcap      = neww;
         wcur      = 0;
+        la_mirror_cols = 0;
         last_slot = nullptr;
         return CSLAM_OK;
     }
@@ -517,6 +540,7 @@ struct Ekf : EkfBase
         }
         wcur ^= 1;
         kp = 0;
+        la_mirror_cols = 0; // (the mirror described the columns that have just been applied)
         // the other region becomes the pending store: a still older P-GEMM may be reading it
         if ((rc = own_region(wcur)))
         {
@@ -728,6 +752,7 @@ struct Ekf : EkfBase
         // panels: rows beyond the new n must read as zero (the tuned gain kernel relies on it)
         kp        = 0; // a new state discards updates that were never applied
         wcur      = 0;
+        la_mirror_cols = 0;
         last_slot = nullptr;
         hd_cols[0] = hd_cols[1] = 0;
         CSLAM_HIP_TRY(hipMemsetAsync(dSign.get(), 0, ((size_t)2 * wcap + 2) * sizeof(int), stream));
@@ -1542,7 +1567,7 @@ struct Ekf : EkfBase
         DevBuf<unsigned>   done;  // device counter: workgroups of the blocks kernels that have finished
         DevBuf<long long>  stamps; // CSLAM_LA_STAMPS=1: phase stamps of factor(a) underneath the P-GEMM (diagnostics)
         DevBuf<int>        idf_keep; // update b's feature ids and ...
-        DevBuf<T>          z_keep;   // ... Z, copied by the rows kernel of a window whose wide launch is held
+        DevBuf<T>          z_keep;   // ... Z, copied by the rows kernel (mirror form: the blocks kernel) of a window whose wide launch is held
     };
     // A window's wide launch, built but not yet submitted (la_launch_held_wide).  Everything on the host is already as if
     // it had been launched (kp, last_slot, sub_valid, the held predict): only the device has not been told.
@@ -1552,6 +1577,7 @@ struct Ekf : EkfBase
         bool       k64   = false;
         unsigned   grid  = 0;
         LaWideArgs wa;
+        float*     wt = nullptr; // != nullptr: the k = 64 kernel that also writes the row-major mirror
     };
     LaHeld      la_held;
     int         la_hold_wide = 1; // CSLAM_LA_HOLD_WIDE=0: every window launches its own wide kernel at once (A/B)
@@ -1570,6 +1596,17 @@ struct Ekf : EkfBase
     unsigned    la_sig_add = 0;
     int         la_k64 = 1;       // CSLAM_LA_K64=0: the general wide kernel for m = 32 too (A/B)
     int         la_wg_signal = 0; // CSLAM_LA_WG_SIGNAL=1: always the blocks kernel's own release (A/B: the first form)
+    // The row-major mirror of the pending panels (f32; written by ekf_la_wide_f32_k64m, read by the NEXT window's
+    // ekf_la_blocks_mirror_kernel, which precedes the next wide kernel on the main stream: one buffer suffices).
+    // la_mirror_cols: how many leading columns of the current pending store it covers, for a state of la_mirror_n rows.
+    // A window takes the mirror path only when that is all kp of them: whatever else adds columns to the store (the
+    // classic path, heading columns, sequential updates, the general wide kernel, CSLAM_LA_FUSED=0) leaves kp larger, and
+    // whatever applies or discards the store (flush, set_state, a store that grows) sets the count to 0.
+    DevBuf<float> la_WT;
+    int           la_wt_rows     = 0;
+    int           la_mirror_cols = 0;
+    int           la_mirror_n    = 0;
+    int           la_mirror      = 1; // CSLAM_LA_MIRROR=0: rows + blocks kernels for every window, no mirror stores (A/B)
 
     int         la_fused   = 1; // env CSLAM_LA_FUSED=0: gather + gain per update instead of the one wide launch (A/B)
     // what debug_last_update reads (the handle's workspace, or the factor slot of a window's last update)
@@ -1640,6 +1677,17 @@ struct Ekf : EkfBase
             la_WR   = std::move(wr);
             la_kpad = kpad;
         }
+        if (la_mirror && std::is_same<T, float>::value && round_up(n, kTile) > la_wt_rows)
+        {
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream_f));
+            const int     rows = round_up(n, kTile);
+            DevBuf<float> wt;
+            CSLAM_TRY(wt.alloc((size_t)rows * 128)); // [rows][128 columns]
+            la_WT          = std::move(wt);
+            la_wt_rows     = rows;
+            la_mirror_cols = 0;
+        }
         return CSLAM_OK;
     }
 
@@ -1668,7 +1716,8 @@ struct Ekf : EkfBase
     // the wide kernel at the end of b's call waits for the chain kernel on stream F, so a caller that has waited for the
     // main stream knows that every reader of b's buffers has finished.  A window whose wide launch is held therefore
     // reads b's caller buffers from main-stream kernels of b's call only (rows, blocks); the chain kernel and the held
-    // wide kernel read the engine's copies (la.z_keep / la.idf_keep, written by the rows kernel: see la_launch_window).
+    // wide kernel read the engine's copies (la.z_keep / la.idf_keep, written by the rows kernel or, where the mirror form
+    // runs, by the blocks kernel: see la_launch_window).
     // `job`: the snapshot the launch carries (LaSnapJob), or nullptr.  On an error the launch stays held.
     int la_launch_held_wide(const LaSnapJob* job)
     {
@@ -1694,7 +1743,11 @@ struct Ekf : EkfBase
                 wa.snap = *job;
                 g += 1; // the workgroup that does the copy (la_wide_snapshot)
             }
-            if (la_held.k64)
+            if (la_held.k64 && la_held.wt != nullptr)
+            {
+                hipLaunchKernelGGL(ekf_la_wide_f32_k64m, dim3(g), dim3(128), 0, stream, wa, la_held.wt);
+            }
+            else if (la_held.k64)
             {
                 hipLaunchKernelGGL(ekf_la_wide_f32_k64, dim3(g), dim3(128), 0, stream, wa);
             }
@@ -1903,7 +1956,7 @@ struct Ekf : EkfBase
         const bool     safe     = g_engines.load() > 1;
         const unsigned n_blocks = (unsigned)(3 + ka + 2 * kb);
         // hold: the wide launch waits for the next call (la_launch_held_wide).  Update b's caller buffers are then read by
-        // the rows and blocks kernels only; the chain kernel and the wide kernel read the rows kernel's copies.
+        // the rows and blocks kernels only; the chain kernel and the wide kernel read the copies those keep.
         const bool hold = may_hold && la_hold_wide && la_fused && !safe && nu == 2 && std::is_same<T, float>::value &&
                           !la.stamps.get();
         auto launch_chain = [&]() -> int {
@@ -1981,7 +2034,18 @@ struct Ekf : EkfBase
         ra.idf_b_keep = hold ? la.idf_keep.get() : (int*)nullptr;
         ra.Z_b        = ub.dZ;
         ra.Z_b_keep   = hold ? la.z_keep.get() : (T*)nullptr;
-        hipLaunchKernelGGL(ekf_la_rows_kernel<T>, dim3(ka + kb), dim3(128), 0, stream, ra);
+        // (the mirror form of the blocks kernel needs no rows kernel: when the mirror covers every pending column, or
+        // there is none)
+        bool use_mirror = false;
+        if constexpr (std::is_same<T, float>::value)
+        {
+            use_mirror = la_mirror && (kp == 0 || (la_mirror_cols == kp && la_mirror_n == n && kp <= 128 && kp % 4 == 0));
+        }
+        if (!use_mirror)
+        {
+            hipLaunchKernelGGL(ekf_la_rows_kernel<T>, dim3(ka + kb), dim3(128), 0, stream, ra);
+            rows_launches++;
+        }
         LaPrepArgs<T> pa;
         pa.P       = dP.get();
         pa.ldp     = ldp;
@@ -2012,7 +2076,24 @@ struct Ekf : EkfBase
         const bool pg_signal = !la_wg_signal && !safe && kp > 0 && seq.count == 0 && sizeof(T) == 4 && k8f <= 128 && lower && ldp < 32768 &&
                                !limbs_take(k8f) && stream_b == stream && hd_cols[wcur] == 0;
         pa.done    = pg_signal ? (unsigned*)nullptr : la.done.get();
-        hipLaunchKernelGGL(ekf_la_blocks_kernel<T>, dim3(n_blocks), dim3(64), 0, stream, pa);
+        if constexpr (std::is_same<T, float>::value)
+        {
+            if (use_mirror)
+            {
+                LaMirrorArgs mi;
+                mi.WT         = la_WT.get();
+                mi.XLb        = la.XL.get() + ka;
+                mi.flags      = dFlags.get();
+                mi.idf_b_keep = ra.idf_b_keep;
+                mi.Z_b        = ra.Z_b;
+                mi.Z_b_keep   = ra.Z_b_keep;
+                hipLaunchKernelGGL(ekf_la_blocks_mirror_kernel, dim3(n_blocks), dim3(256), 0, stream, pa, mi);
+            }
+        }
+        if (!use_mirror)
+        {
+            hipLaunchKernelGGL(ekf_la_blocks_kernel<T>, dim3(n_blocks), dim3(64), 0, stream, pa);
+        }
         CSLAM_HIP_TRY(hipGetLastError());
         if (safe)
         {
@@ -2086,6 +2167,10 @@ struct Ekf : EkfBase
                 wa.snap    = LaSnapJob{nullptr, nullptr, nullptr, nullptr, 0};
                 la_held.wa    = wa;
                 la_held.k64   = la_k64 && ua.m == 32 && (nu == 1 || ub.m == 32);
+                // (the mirror's column q is the store's column q: the panels must start at column 0 of the store)
+                la_held.wt     = (la_mirror && la_held.k64 && kp == 0) ? la_WT.get() : nullptr;
+                la_mirror_cols = la_held.wt ? ka + kb : 0;
+                la_mirror_n    = n;
                 la_held.grid  = (unsigned)(round_up(n, kTile) / 32);
                 la_held.valid = true;
                 if (!hold && (rc = la_launch_held_wide(nullptr)))
@@ -2954,6 +3039,17 @@ int cslam_ekf_lookahead_windows(cslam_ekf_t h, long long* windows)
         return fail(CSLAM_ERR_BAD_ARG, "lookahead_windows: null");
     }
     *windows = B(h)->la_windows;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_rows_launches(cslam_ekf_t h, long long* launches)
+{
+    CSLAM_NEED(h);
+    if (!launches)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "rows_launches: null");
+    }
+    *launches = B(h)->rows_launches;
     return CSLAM_OK;
 }
 

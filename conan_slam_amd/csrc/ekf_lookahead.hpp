@@ -16,6 +16,9 @@
 //                          model (EKF.cpp:354-404), so the rows leave as what the factor chain needs: row of
 //                          sub_a = PHT_a[rows(a), :] (ekf_gather_kernel's compact block), row of PHT_a[rows(b), :],
 //                          row of D_bb                                                         (main stream, many workgroups)
+//   ekf_la_blocks_mirror_kernel  the same rows without a rows kernel in front (single filter, f32, windows of two
+//                          32-observation updates): the panel rows come from the row-major mirror that the previous
+//                          window's wide kernel left behind (ekf_la_wide_body: MIRROR)              (main stream, many workgroups)
 //   ekf_la_carry_kernel    update b on stream F, between the two factor kernels: carries the rows of b through update a
 //                          WITHOUT the wide kernels -- W1_a[rows(b)] = PHT_a[rows(b)] G_a, P[rows(b), rows(b)] -= W1 W1^T,
 //                          X[rows(b)] += PHT_a[rows(b)] u_a, the pose stripe rows -= PHT_a M_a (slam.h:257-260 restricted
@@ -424,6 +427,290 @@ template <typename T>
 __global__ void __launch_bounds__(64) ekf_la_blocks_kernel(LaPrepArgs<T> a)
 {
     ekf_la_blocks_body<T>(a);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same rows WITHOUT a rows kernel in front (single filter, f32; ekf_la_blocks_mirror_kernel in cslam_ekf.hip).  The
+// k = 64 wide kernel of the previous window has left a row-major copy WT[row * 128 + q] of the pending panels
+// (ekf_la_wide_body: MIRROR), so a panel row is 512 contiguous bytes.  Same grid and row types as ekf_la_blocks_body, 256
+// threads: the workgroup reads its own row and the <= 64 rows of its column slots with coalesced 16-byte loads (eight per
+// thread, all issued at once), parks the latter in LDS (s_wt, row stride kLaWtLd) and thread c then walks the row of slot
+// c from there in ascending q -- the sums and their order are those of the WR form, and so is every output bit.  X and
+// the stripe entries come straight from X / Pv (a.XL, a.PvL and a.WR are not read), and the workgroups of update b's
+// rows against a (type 2) write what the rows kernel used to leave for the chain kernel and the held wide kernel: XL
+// of b's slots and the kept copies of Z_b / idf_b, each entry by one workgroup; the bad-id flag is raised here too.
+// (The first form of this idea let every lane walk its own mirror row in global memory: one cache-line look-up per
+// lane per load, 128 deep, which cost the blocks kernel what the rows launch had cost.)
+// ------------------------------------------------------------------------------------------------
+struct LaMirrorArgs
+{
+    const float* WT;  // row-major mirror of the kp pending columns (kp a multiple of 4, <= 128)
+    float*       XLb; // out: X at the rows of update b's slots (LaCarryArgs::XLb)
+    int*         flags;
+    int*         idf_b_keep; // as in LaRowsArgs: the engine's copies of update b's inputs when the wide launch is held, or nullptr
+    const float* Z_b;
+    float*       Z_b_keep;
+};
+
+constexpr int kLaWtLd = 128 + 4; // LDS row stride of the mirror rows: 16-byte aligned, conflict-free 16-byte reads
+
+__device__ __forceinline__ void ekf_la_blocks_mirror_body(const LaPrepArgs<float>& a, const LaMirrorArgs& mi)
+{
+    using T = float;
+    __shared__ __attribute__((aligned(16))) T s_wt[2 * kLaMaxObs * kLaWtLd];
+    __shared__ __attribute__((aligned(16))) T wrow[128];
+    __shared__ T s_xl[3 + 2 * kLaMaxObs];
+    __shared__ T s_coef[kLaMaxObs * 10];
+    __shared__ T s_pvv[9], s_g[2], s_e3[3];
+    __shared__ T s_d[2 * kLaMaxObs];
+    __shared__ T s_e[2 * kLaMaxObs * 3];
+    const int tid = threadIdx.x;
+    const int ra = a.ra, rb = a.rb, ma = ra >> 1;
+    int       b    = blockIdx.x;
+    int       type = 0, s = b; // 0 pose row, 1 row of a, 2 row of b vs a, 3 row of b vs b
+    if (b >= 3)
+    {
+        b -= 3;
+        type = (b < ra) ? 1 : ((b < ra + rb) ? 2 : 3);
+        s    = (type == 1) ? b : ((type == 2) ? b - ra : b - ra - rb);
+    }
+    // Everything the row needs from global memory is requested before the model is evaluated, in two rounds (the feature
+    // ids, then what they address), every load of a round back to back: unconditional loads from clamped addresses, the
+    // VALUE is selected afterwards -- a load inside a per-lane condition is waited for before the next one is issued.
+    const int* idf_r = (type <= 1) ? a.idf_a : a.idf_b;
+    const int* idf_c = (type == 3) ? a.idf_b : a.idf_a;
+    const int  nc    = (type == 3) ? rb : ra;
+    const int  pc = tid & 31, c0 = tid >> 5; // the mirror rows of the column slots: 32 pieces of 16 bytes per row, 8 rows per pass
+    auto       row_of = [&](int id, int slot) { return 3 + 2 * clamp_idf(id, a.n) - 2 + (slot & 1); };
+    // ---- round 1
+    int cs[8], idc[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+    {
+        cs[i]  = min(c0 + 8 * i, nc - 1); // (slots beyond nc: a copy of the last one, never read)
+        idc[i] = idf_c[cs[i] >> 1];
+    }
+    const int id_r = idf_r[s >> 1]; // (pose rows, type 0: slot s < 3 of update a stands in, nothing of it is used)
+    const int ct = min(tid, nc - 1), at = min(tid, ra - 1);
+    int       id_p = 1, id_a = 1;
+    T         warm[4] = {(T)0, (T)0, (T)0, (T)0};
+    if (tid < 64) // (whole waves: wave 0 forms the row, the other three only fetch mirror rows)
+    {
+        id_p = idf_c[ct >> 1];
+        id_a = a.idf_a[at >> 1];
+        // the four cache lines of the pose and the pose block, for thread 0's serial part below (which stays, word for
+        // word, the one of ekf_la_blocks_body: its arithmetic must compile to the same instructions)
+        warm[0] = a.X[0], warm[1] = a.Pv[0], warm[2] = a.Pv[(size_t)a.ldp], warm[3] = a.Pv[(size_t)2 * a.ldp];
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): every id has arrived, so that no load of the second round waits for another
+    // ---- round 2: the mirror rows first (all four waves), then what wave 0 alone needs
+    const int  row    = row_of(id_r, s);
+    const int  erow   = row_of(id_a, at), prow = row_of(id_p, ct);
+    const bool mirror = a.kp > 0 && type != 0;
+    float4     w0, w1, w2, w3, w4, w5, w6, w7, wown;
+    w0 = w1 = w2 = w3 = w4 = w5 = w6 = w7 = wown = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (mirror)
+    {
+        w0   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[0], cs[0]) * 128 + 4 * pc);
+        w1   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[1], cs[1]) * 128 + 4 * pc);
+        w2   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[2], cs[2]) * 128 + 4 * pc);
+        w3   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[3], cs[3]) * 128 + 4 * pc);
+        w4   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[4], cs[4]) * 128 + 4 * pc);
+        w5   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[5], cs[5]) * 128 + 4 * pc);
+        w6   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[6], cs[6]) * 128 + 4 * pc);
+        w7   = *reinterpret_cast<const float4*>(mi.WT + (size_t)row_of(idc[7], cs[7]) * 128 + 4 * pc);
+        wown = *reinterpret_cast<const float4*>(mi.WT + (size_t)row * 128 + 4 * pc); // own row: one coalesced read
+    }
+    T   pcell = (T)0, xa = (T)0, xr = (T)0;
+    T   e3[3] = {(T)0, (T)0, (T)0}, ee[3] = {(T)0, (T)0, (T)0};
+    if (tid < 64)
+    {
+        pcell = p_sym<T>(a.P, a.ldp, row, prow, a.lower);
+        xa    = a.X[erow];
+        xr    = a.X[row];
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+        {
+            e3[c] = a.Pv[(size_t)c * a.ldp + row];
+            ee[c] = a.Pv[(size_t)c * a.ldp + erow];
+        }
+    }
+    // what the rows kernel left for the chain kernel and the held wide kernel (requested here, stored at the end)
+    const bool keep = type == 2 && mi.idf_b_keep != nullptr;
+    T          zb   = (T)0;
+    int        ib   = 0;
+    if (keep)
+    {
+        zb = mi.Z_b[s];
+        ib = a.idf_b[s >> 1];
+    }
+    // ---- park them in LDS (every group of 32 threads holds the own row: the same values to the same place)
+    if (mirror)
+    {
+        float4* dst = reinterpret_cast<float4*>(&s_wt[c0 * kLaWtLd + 4 * pc]);
+        dst[0 * 2 * kLaWtLd] = w0;
+        dst[1 * 2 * kLaWtLd] = w1;
+        dst[2 * 2 * kLaWtLd] = w2;
+        dst[3 * 2 * kLaWtLd] = w3;
+        dst[4 * 2 * kLaWtLd] = w4;
+        dst[5 * 2 * kLaWtLd] = w5;
+        dst[6 * 2 * kLaWtLd] = w6;
+        dst[7 * 2 * kLaWtLd] = w7;
+        *reinterpret_cast<float4*>(&wrow[4 * pc]) = wown;
+    }
+    if (type != 0 && type != 3 && tid == 0 && (id_r < 1 || id_r > ((a.n - 3) >> 1)))
+    {
+        atomicOr(&mi.flags[0], kFlagBadIdf); // (device-resident feature ids cannot be checked by the host: clamped everywhere, flagged here)
+    }
+    if (tid < ra)
+    {
+        s_xl[3 + tid] = xa;
+    }
+    asm volatile("" : : "v"(warm[0]), "v"(warm[1]), "v"(warm[2]), "v"(warm[3])); // (keeps the four loads above)
+    if (tid == 0)
+    {
+        T pose_in[3] = {a.X[0], a.X[1], a.X[2]}, pvv_in[9], pose[3], g[2], pvv[9];
+        for (int e = 0; e < 9; e++)
+        {
+            pvv_in[e] = a.Pv[(size_t)(e / 3) * a.ldp + (e % 3)];
+        }
+        la_predict_pose<T>(a.pp_a, pose_in, pvv_in, pose, g, pvv);
+        s_xl[0] = pose[0], s_xl[1] = pose[1], s_xl[2] = pose[2];
+        s_g[0] = g[0], s_g[1] = g[1];
+        for (int e = 0; e < 9; e++)
+        {
+            s_pvv[e] = pvv[e];
+        }
+        if (type != 0)
+        {
+            la_predict_row<T>(a.pp_a, g[0], g[1], row, e3);
+            s_e3[0] = e3[0], s_e3[1] = e3[1], s_e3[2] = e3[2];
+        }
+    }
+    __syncthreads();
+    if (tid < ma)
+    {
+        T   v[2];
+        int fx;
+        observe_model_pose<T>(s_xl, 3 + ra, tid + 1, (T)0, (T)0, s_xl[0], s_xl[1], s_xl[2], &s_coef[tid * 10], v, &fx);
+    }
+    if (type == 0)
+    {
+        if (tid < ra)
+        {
+            la_predict_row<T>(a.pp_a, s_g[0], s_g[1], erow, ee);
+            s_e[tid * 3 + 0] = ee[0], s_e[tid * 3 + 1] = ee[1], s_e[tid * 3 + 2] = ee[2];
+        }
+    }
+    else if (tid < nc)
+    {
+        const T* wc  = s_wt + tid * kLaWtLd; // this thread's slot: its row of the pending panels, wc[q]
+        T        dot = (T)0;
+        int      q   = 0;
+#pragma unroll 4
+        for (; q + 4 <= a.kp; q += 4) // (16-byte LDS reads; the products are added in ascending q, as in the WR form)
+        {
+            const float4 v = *reinterpret_cast<const float4*>(wc + q);
+            const float4 w = *reinterpret_cast<const float4*>(&wrow[q]);
+            dot += w.x * v.x;
+            dot += w.y * v.y;
+            dot += w.z * v.z;
+            dot += w.w * v.w;
+        }
+        for (; q < a.kp; q++)
+        {
+            dot += wrow[q] * wc[q];
+        }
+        s_d[tid] = pcell - dot;
+    }
+    __syncthreads();
+    if (type == 0)
+    {
+        const int r = s; // pose row
+        if (tid < ma)
+        {
+            T v0, v1;
+            la_pht_pair<T>(&s_coef[tid * 10], s_pvv[r], s_pvv[r + 3], s_pvv[r + 6], s_e[(2 * tid) * 3 + r],
+                           s_e[(2 * tid + 1) * 3 + r], &v0, &v1);
+            a.sub_a[r * ra + 2 * tid]     = v0;
+            a.sub_a[r * ra + 2 * tid + 1] = v1;
+        }
+        if (r == 0)
+        {
+            LaModel<T>& mo = *a.model_a;
+            if (tid == 0)
+            {
+                mo.g02 = s_g[0];
+                mo.g12 = s_g[1];
+            }
+            if (tid < 3)
+            {
+                mo.pose[tid] = s_xl[tid];
+            }
+            if (tid < 9)
+            {
+                mo.pvv[tid] = s_pvv[tid];
+            }
+            for (int e = tid; e < ma * 10; e += 256)
+            {
+                mo.coef[e] = s_coef[e];
+            }
+            for (int e = tid; e < 3 + ra; e += 256)
+            {
+                a.xloc_a[e] = s_xl[e];
+            }
+            if (tid < kLaMaxObs)
+            {
+                a.idloc[tid] = tid + 1;
+            }
+        }
+    }
+    else if (type == 3)
+    {
+        if (tid < nc)
+        {
+            a.Dbb[(size_t)s * rb + tid] = s_d[tid];
+        }
+    }
+    else
+    {
+        if (tid < ma)
+        {
+            T v0, v1;
+            la_pht_pair<T>(&s_coef[tid * 10], s_e3[0], s_e3[1], s_e3[2], s_d[2 * tid], s_d[2 * tid + 1], &v0, &v1);
+            T* out           = (type == 1) ? (a.sub_a + (size_t)(3 + s) * ra) : (a.PH + (size_t)s * ra);
+            out[2 * tid]     = v0;
+            out[2 * tid + 1] = v1;
+        }
+        if (type == 2 && tid < 3)
+        {
+            a.PvLb[s * 3 + tid] = s_e3[tid];
+        }
+    }
+    if (type == 2 && tid == 0) // (each entry has ONE writer: slot s of update b)
+    {
+        mi.XLb[s] = xr;
+        if (keep)
+        {
+            mi.Z_b_keep[s] = zb;
+            if ((s & 1) == 0)
+            {
+                mi.idf_b_keep[s >> 1] = ib;
+            }
+        }
+    }
+    // this workgroup's rows are out: release them to the chain kernel, as ekf_la_blocks_body does (a.done == nullptr: the
+    // P-GEMM that follows on the stream gives the go-ahead)
+    if (a.done == nullptr)
+    {
+        return;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (tid == 0)
+    {
+        atomicAdd(a.done + 16 * (blockIdx.x & 15u), 1u);
+    }
 }
 
 template <typename T>
@@ -937,9 +1224,14 @@ __device__ __forceinline__ int la_q_of(int t, int r, int lh)
 // KFIX: 0, or the number of columns of BOTH updates' panels known at compile time (64: m = 32 observations per update, the
 // benchmark shape).  The operand reads of the three matrix products then have immediate LDS offsets and no range selects:
 // the gain and correction phases are ~600 vector instructions of address arithmetic and selects each otherwise.
-template <int PAIRS = 1, int KFIX = 0>
-__device__ __forceinline__ void ekf_la_wide_body(const LaWideArgs& a)
+// MIRROR (single filter, KFIX = 64): every row of W1_a and W1_b is ALSO stored row-major, wt[row * 128 + q] with q < 64
+// update a and 64 <= q < 128 update b -- the next window's blocks kernel reads the panel rows it needs from there, 512
+// contiguous bytes each, instead of 128 strided entries of the column-major panels (ekf_la_blocks_mirror_kernel).
+// wt: round_up(n, 128) x 128 floats.
+template <int PAIRS = 1, int KFIX = 0, int MIRROR = 0>
+__device__ __forceinline__ void ekf_la_wide_body(const LaWideArgs& a, float* wt = nullptr)
 {
+    static_assert(!MIRROR || (PAIRS == 1 && KFIX == 64), "the mirror belongs to the single filter's k = 64 kernel");
     // TWO waves per block of 32 rows.  Wave w owns column tile w (32 columns) of every product -- half the matrix-core
     // chain, half the operand reads -- and builds tile w of PHT; the halves meet through LDS (one 8 KB exchange area,
     // carved out of the G areas while they are not in use).  The wave's work is one dependent chain, so every global
@@ -1194,6 +1486,16 @@ __device__ __forceinline__ void ekf_la_wide_body(const LaWideArgs& a)
             }
         }
     };
+    // the row-major copy: registers 4g .. 4g + 3 of the tile are four consecutive columns of this lane's row
+    auto store_wt = [&](int q0) {
+        float* dst = wt + (size_t)row * 128 + q0 + 32 * wv + 4 * lh;
+#pragma unroll
+        for (int g = 0; g < 4; g++)
+        {
+            const float4 v = make_float4(w1[4 * g], w1[4 * g + 1], w1[4 * g + 2], w1[4 * g + 3]);
+            *reinterpret_cast<float4*>(dst + 8 * g) = (row < 3) ? make_float4(0.f, 0.f, 0.f, 0.f) : v;
+        }
+    };
     using U0 = std::integral_constant<int, 0>;
     using U1 = std::integral_constant<int, 1>;
 
@@ -1210,6 +1512,10 @@ __device__ __forceinline__ void ekf_la_wide_body(const LaWideArgs& a)
     gain(U0{}, ka);
     stamp();
     store_w1(a.W1a, ka, a.nu == 1);
+    if constexpr (MIRROR)
+    {
+        store_wt(0);
+    }
     const float* pred_last = s_model[0];
     if (a.nu == 2)
     {
@@ -1284,6 +1590,10 @@ __device__ __forceinline__ void ekf_la_wide_body(const LaWideArgs& a)
         gain(U1{}, kb);
         stamp();
         store_w1(a.W1b, kb, true);
+        if constexpr (MIRROR)
+        {
+            store_wt(64);
+        }
         pred_last = s_model[1];
     }
     __syncthreads(); // the row sums of the last update

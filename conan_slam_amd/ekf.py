@@ -138,6 +138,12 @@ class EKF:
         check(self._L.cslam_ekf_stage_launches(self._h, C.byref(w)))
         return w.value
 
+    def rows_launches(self) -> int:
+        """launches of the kernel that gathers pending-panel rows for a look-ahead window (cslam_ekf_rows_launches)"""
+        w = C.c_longlong(0)
+        check(self._L.cslam_ekf_rows_launches(self._h, C.byref(w)))
+        return w.value
+
     def landmarks(self, first: int = 1, count: int = None):
         """(x [c, 2], P [c, 2, 2], Pvl [c, 3, 2]) of landmarks first .. first + c - 1 (1-based; count None: to the
         last): means, marginal 2 x 2 blocks and pose-landmark blocks P[0:3, fx:fx+2], read without applying the pending

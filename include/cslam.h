@@ -181,6 +181,12 @@ int cslam_ekf_lookahead_windows(cslam_ekf_t h, long long* windows);
  * kernel carries the copy (CSLAM_LA_HOLD_WIDE=0: every window).  Lets a test confirm which of the two ran. */
 int cslam_ekf_stage_launches(cslam_ekf_t h, long long* launches);
 
+/* Launches of the kernel that gathers the rows of the pending panels for a look-ahead window's small blocks.  In a run of
+ * f32 windows of two 32-observation updates the preceding window's wide kernel leaves a row-major mirror of its panels
+ * and the blocks kernel reads that instead, so the count stays where it was; a window that starts from pending columns the
+ * mirror does not cover (or CSLAM_LA_MIRROR=0: every window) launches the rows kernel.  Lets a test confirm which ran. */
+int cslam_ekf_rows_launches(cslam_ekf_t h, long long* launches);
+
 /* Cap on the workgroups of the persistent covariance-downdate kernel (0 = default: two per compute unit, i.e. the
  * whole chip).  For several filter instances that run side by side on one GPU (Monte-Carlo runs, one stream each): with
  * the default every instance's P-GEMM occupies all compute units for its duration and the other instances' small

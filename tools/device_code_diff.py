@@ -35,6 +35,8 @@ def split(asm):
     """{symbol: text} for every function body and every kernel's descriptor + metadata entry"""
     asm = "\n".join(l for l in asm.split("\n") if "__hip_cuid_" not in l)
     asm = re.sub(r"\.LBB\d+_", ".LBB_", asm)
+    asm = re.sub(r"\bBB\d+_", "BB_", asm)  # (the same labels in the loop comments: "in Loop: Header=BB44_4", "Child Loop BB57_7")
+    asm = re.sub(r"[ \t]+;", " ;", asm)  # (comments are aligned with padding that depends on the label's width)
     asm = re.sub(r"\.L(func_end|func_begin|tmp)\d+", r".L\1", asm)
     parts = {}
     for m in re.finditer(r"^\t\.type\t(\S+),@function\n(.*?)^\t\.size\t\1,[^\n]*\n", asm, flags=re.S | re.M):

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Timeline of a rocprofv3 --kernel-trace CSV: for a window of dispatches in the steady state, each kernel's start and
-end relative to the first one, its stream/queue, and how much of it overlapped the covariance downdate (P-GEMM).
+end relative to the first one, its stream/queue, and how much of it overlapped the covariance downdate (P-GEMM); then, over everything after the skipped part, the duration
+statistics per kernel and the P-GEMM's start-to-start period.
 Usage: python tools/trace_timeline.py <kernel_trace.csv> [skip_fraction=0.5] [count=40]"""
 import csv
 import sys
@@ -44,6 +45,38 @@ def main():
         per = (dd[-1][0] - dd[0][0]) / (len(dd) - 1) / 1e3
         busy = sum(b - a for a, b in dd[:-1]) / (len(dd) - 1) / 1e3
         print(f"P-GEMM period {per:.1f} us, P-GEMM busy {busy:.1f} us per period ({100 * busy / per:.0f} %)")
+    stats(rows, int(len(rows) * skip), skip)
+
+
+def quantile(v, q):
+    """linear interpolation between order statistics (numpy's default)"""
+    v = sorted(v)
+    x = q * (len(v) - 1)
+    lo = int(x)
+    hi = min(lo + 1, len(v) - 1)
+    return v[lo] + (v[hi] - v[lo]) * (x - lo)
+
+
+def stats(rows, i0, skip):
+    rest = rows[i0:]
+    print(f"\nafter the first {skip:g} of the trace: {len(rest)} dispatches")
+    dur = {}
+    for r in rest:
+        dur.setdefault(short(r["Kernel_Name"])[:40], []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    for k, v in sorted(dur.items(), key=lambda kv: -sum(kv[1])):
+        print(f"  {k:40s} n={len(v):5d} median {quantile(v, 0.5):7.1f} min {min(v):7.1f} max {max(v):7.1f} us")
+    # (the k = 128 flushes of the steady state: the dominant instantiation of the downdate kernel)
+    names = [r["Kernel_Name"] for r in rest if "downdate" in r["Kernel_Name"]]
+    if names:
+        main_name = max(set(names), key=names.count)
+        st = [int(r["Start_Timestamp"]) for r in rest if r["Kernel_Name"] == main_name]
+        per = [(b - a) / 1e3 for a, b in zip(st, st[1:])]
+        if per:
+            print(f"  P-GEMM start to start: n={len(per)} median {quantile(per, 0.5):.1f} us, quartiles "
+                  f"[{quantile(per, 0.25):.1f}, {quantile(per, 0.5):.1f}, {quantile(per, 0.75):.1f}]")
+    count = lambda key: sum(1 for r in rows if key in r["Kernel_Name"])
+    print(f"  in the whole trace: rows kernels {count('ekf_la_rows_kernel')}, blocks kernels {count('ekf_la_blocks')}, "
+          f"wide kernels {count('ekf_la_wide')}, stage kernels {count('ekf_stage_obs')}")
 
 
 if __name__ == "__main__":
