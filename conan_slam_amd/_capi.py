@@ -49,7 +49,16 @@ _PROTOTYPES = {
     "cslam_sim_batch_set_table": [C.c_void_p, C.c_void_p],
     "cslam_ekf_batch_update_scan": [C.c_void_p, C.c_void_p, C.c_void_p],
     "cslam_ekf_batch_augment_scan": [C.c_void_p, C.c_void_p, C.c_void_p],
+    # the particle filter's read path: best particle, mixture moments, all features (single handle and sharded)
+    "cslam_pf_best_particle": [C.c_void_p, C.c_int, C.POINTER(C.c_int)] + [C.c_void_p] * 5,
+    "cslam_pf_estimate": [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)] + [C.c_void_p] * 4,
+    "cslam_pf_get_all_features": [C.c_void_p, C.c_void_p],
+    "cslam_pf_best_particle_sharded": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong)] + [C.c_void_p] * 5,
+    "cslam_pf_estimate_sharded": [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+                                 + [C.c_void_p] * 4,
 }
+PF_ESTIMATE_SYMBOLS = tuple(k for k in _PROTOTYPES if k.startswith("cslam_pf_"))
+PF_PICK_MAX, PF_PICK_MIN = 0, 1
 SIM_BATCH_SYMBOLS = tuple(k for k in _PROTOTYPES if "sim_batch" in k or k.endswith("_scan"))
 
 

@@ -18,6 +18,7 @@
 
 #include "cslam_common.hpp"
 #include "device_owners.hpp"
+#include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
 
 using namespace cslam;
@@ -362,6 +363,10 @@ struct PfBase
     virtual int get_particle(int i, void* w, void* Xv, void* Pv, void* XF, void* PF)          = 0;
     virtual int set_particle(int i, const void* w, const void* Xv, const void* Pv, const void* XF, const void* PF,
                              int nf)                                                          = 0;
+    // the read path (pf_estimate_kernels.hpp); c == nullptr: this handle alone
+    virtual int best_particle(Comm* c, int pick, long long* index, void* w, void* Xv, void* Pv, void* XF, void* PF) = 0;
+    virtual int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF)              = 0;
+    virtual int get_all_features(void* XF_all)                                                                      = 0;
 };
 
 template <typename T>
@@ -1415,6 +1420,218 @@ struct Pf : PfBase
         nf = nfeat; // every particle of the store carries the same number of features
         return CSLAM_OK;
     }
+
+    // ------------------------------------------------------------------------------------------------
+    // The read path: best particle, mixture moments, all features.  Every call queues its launches behind whatever is
+    // on the stream, brings ONE block back through hEst (pinned) and synchronises; the store is only read.
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<double>  dEstPart;               // per-chunk partials of passes 1 and 2
+    DevBuf<double>  dEstOut, dEstLocal;     // output block: kEstOutHdr doubles, then the T record [w, Xv, Pv, XF, PF]
+    DevBuf<double>  dEstSum, dEstSumAll;    // this rank's summary / every rank's (sharded estimate)
+    DevBuf<double>  dBestHdrAll;            // every rank's pick (sharded best particle)
+    DevBuf<T>       dBestRecAll, dEstFeat;  // every rank's picked record; the transposed features
+    PinnedBuf<char> hEst;
+
+    template <typename B>
+    int est_grow(B& buf, size_t count)
+    {
+        if (buf.count() >= count)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still uses the old buffer
+        B nb;
+        CSLAM_TRY(nb.alloc(count));
+        buf = std::move(nb);
+        return CSLAM_OK;
+    }
+    int est_chunks() const
+    {
+        return (np + kEstChunk - 1) / kEstChunk;
+    }
+    size_t est_out_doubles() const
+    {
+        return (size_t)kEstOutHdr + ((size_t)(13 + 6 * nf) * sizeof(T) + 7) / 8;
+    }
+    static T* est_rec(double* block)
+    {
+        return reinterpret_cast<T*>(block + kEstOutHdr);
+    }
+    // header + the first rec_len scalars of the record of `block` -> hEst, one copy, synchronised
+    int est_fetch(const double* block, size_t rec_len)
+    {
+        const size_t bytes = (size_t)kEstOutHdr * sizeof(double) + rec_len * sizeof(T);
+        CSLAM_HIP_TRY(hipMemcpyAsync(hEst.get(), block, bytes, hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+    void est_scatter(bool map, void* w, void* Xv, void* Pv, void* XF, void* PF) const
+    {
+        const T* rec = reinterpret_cast<const T*>(hEst.get() + (size_t)kEstOutHdr * sizeof(double));
+        if (w)
+        {
+            std::memcpy(w, rec, sizeof(T));
+        }
+        if (Xv)
+        {
+            std::memcpy(Xv, rec + 1, 3 * sizeof(T));
+        }
+        if (Pv)
+        {
+            std::memcpy(Pv, rec + 4, 9 * sizeof(T));
+        }
+        if (map && XF)
+        {
+            std::memcpy(XF, rec + 13, (size_t)2 * nf * sizeof(T));
+        }
+        if (map && PF)
+        {
+            std::memcpy(PF, rec + 13 + 2 * nf, (size_t)4 * nf * sizeof(T));
+        }
+    }
+    int est_comm_ok(Comm* c, const char* who)
+    {
+        if (c && !c->loop && !rccl())
+        {
+            return fail(CSLAM_ERR_HIP, "%s: librccl could not be loaded", who);
+        }
+        return CSLAM_OK;
+    }
+
+    int best_particle(Comm* c, int pick, long long* index, void* w, void* Xv, void* Pv, void* XF, void* PF) override
+    {
+        if (pick != kEstPickMax && pick != kEstPickMin)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_best_particle: pick %d is neither CSLAM_PF_PICK_MAX nor _MIN", pick);
+        }
+        int rc = use_device();
+        if (rc || (rc = est_comm_ok(c, "pf_best_particle_sharded")))
+        {
+            return rc;
+        }
+        const int    nch = est_chunks(), len = 13 + 6 * nf, world = c ? c->world : 1;
+        const size_t od  = est_out_doubles();
+        // (everything that can fail is allocated before the first collective)
+        if ((rc = est_grow(dEstPart, (size_t)nch * kEstP1)) || (rc = est_grow(dEstOut, od)) ||
+            (rc = est_grow(hEst, od * sizeof(double))))
+        {
+            return rc;
+        }
+        if (c && ((rc = est_grow(dEstLocal, od)) || (rc = est_grow(dBestHdrAll, (size_t)world * kEstOutHdr)) ||
+                  (rc = est_grow(dBestRecAll, (size_t)world * len))))
+        {
+            return rc;
+        }
+        double* local = c ? dEstLocal.get() : dEstOut.get();
+        hipLaunchKernelGGL(pf_est_pass1_kernel<T>, dim3(nch), dim3(256), 0, stream, store(), dEstPart.get());
+        CSLAM_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(pf_best_finish_kernel<T>, dim3(1), dim3(256), 0, stream, store(), dEstPart.get(), nch, pick,
+                           c ? (long long)c->rank * np : 0LL, local, est_rec(local));
+        CSLAM_HIP_TRY(hipGetLastError());
+        if (c)
+        {
+            const ncclDataType_t dt = (sizeof(T) == 4) ? ncclFloat : ncclDouble;
+            if ((rc = c->all_gather(local, dBestHdrAll.get(), (size_t)kEstOutHdr, ncclDouble, sizeof(double), stream)) ||
+                (rc = c->all_gather(est_rec(local), dBestRecAll.get(), (size_t)len, dt, sizeof(T), stream)))
+            {
+                return rc;
+            }
+            hipLaunchKernelGGL(pf_best_combine_kernel<T>, dim3(1), dim3(256), 0, stream, dBestHdrAll.get(),
+                               dBestRecAll.get(), world, len, pick, dEstOut.get(), est_rec(dEstOut.get()));
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        const bool map = nf > 0 && (XF || PF);
+        if ((rc = est_fetch(dEstOut.get(), map ? (size_t)len : 13)))
+        {
+            return rc;
+        }
+        if (index)
+        {
+            *index = (long long)reinterpret_cast<const double*>(hEst.get())[2];
+        }
+        est_scatter(map, w, Xv, Pv, XF, PF);
+        return CSLAM_OK;
+    }
+
+    int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF) override
+    {
+        int rc = use_device();
+        if (rc || (rc = est_comm_ok(c, "pf_estimate_sharded")))
+        {
+            return rc;
+        }
+        const bool   map = nf > 0 && (XF || PF);
+        const int    nch = est_chunks(), world = c ? c->world : 1;
+        const int    stride = kEstSumHdr + (map ? kEstSumFeat * nf : 0);
+        const size_t od     = est_out_doubles();
+        if ((rc = est_grow(dEstPart, (size_t)nch * (kEstP1 + kEstP2Pose + (map ? (size_t)kEstP2Feat * nf : 0)))) ||
+            (rc = est_grow(dEstOut, od)) || (rc = est_grow(hEst, od * sizeof(double))))
+        {
+            return rc;
+        }
+        if (c && ((rc = est_grow(dEstSum, (size_t)stride)) || (rc = est_grow(dEstSumAll, (size_t)world * stride))))
+        {
+            return rc;
+        }
+        double* p1 = dEstPart.get();
+        double* p2 = p1 + (size_t)nch * kEstP1;
+        double* pm = map ? p2 + (size_t)nch * kEstP2Pose : nullptr;
+        const int fgroups = map ? (nf + kEstFeatPerWg - 1) / kEstFeatPerWg : 0;
+        const int fblocks = map ? (nf + 255) / 256 : 0;
+        hipLaunchKernelGGL(pf_est_pass1_kernel<T>, dim3(nch), dim3(256), 0, stream, store(), p1);
+        CSLAM_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(pf_est_pass2_kernel<T>, dim3(nch, 1 + fgroups), dim3(256), 0, stream, store(), p1, nch, p2, pm);
+        CSLAM_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(pf_est_finish_kernel<T>, dim3(1 + fblocks), dim3(256), 0, stream, store(), p1, p2, pm, nch,
+                           c ? dEstSum.get() : nullptr, dEstOut.get(), est_rec(dEstOut.get()));
+        CSLAM_HIP_TRY(hipGetLastError());
+        if (c)
+        {
+            if ((rc = c->all_gather(dEstSum.get(), dEstSumAll.get(), (size_t)stride, ncclDouble, sizeof(double), stream)))
+            {
+                return rc;
+            }
+            hipLaunchKernelGGL(pf_est_combine_kernel<T>, dim3(1 + fblocks), dim3(256), 0, stream, dEstSumAll.get(), world,
+                               stride, nf, map ? 1 : 0, dEstOut.get(), est_rec(dEstOut.get()));
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        if ((rc = est_fetch(dEstOut.get(), map ? (size_t)(13 + 6 * nf) : 13)))
+        {
+            return rc;
+        }
+        const double* hdr = reinterpret_cast<const double*>(hEst.get());
+        if (w_sum)
+        {
+            *w_sum = hdr[0];
+        }
+        if (neff)
+        {
+            *neff = hdr[1];
+        }
+        est_scatter(map, nullptr, Xv, Pv, XF, PF);
+        return CSLAM_OK;
+    }
+
+    int get_all_features(void* XF_all) override
+    {
+        int rc = use_device();
+        if (rc || nf == 0 || !XF_all)
+        {
+            return rc;
+        }
+        const size_t count = (size_t)2 * nf * np;
+        if ((rc = est_grow(dEstFeat, count)) || (rc = est_grow(hEst, count * sizeof(T))))
+        {
+            return rc;
+        }
+        hipLaunchKernelGGL(pf_all_features_kernel<T>, dim3((np + 63) / 64, (2 * nf + 63) / 64), dim3(256), 0, stream,
+                           store(), dEstFeat.get());
+        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_HIP_TRY(hipMemcpyAsync(hEst.get(), dEstFeat.get(), count * sizeof(T), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        std::memcpy(XF_all, hEst.get(), count * sizeof(T));
+        return CSLAM_OK;
+    }
 };
 
 inline PfBase* B(cslam_pf_t h)
@@ -1791,6 +2008,52 @@ int cslam_pf_resample_sharded(cslam_pf_t h, cslam_comm_t comm, const void* selec
 {
     CSLAM_NEED(h);
     return B(h)->resample_sharded(reinterpret_cast<Comm*>(comm), select, n_effective, resample_status, neff, resampled);
+}
+
+int cslam_pf_best_particle(cslam_pf_t h, int pick, int* index, void* w, void* Xv, void* Pv, void* XF, void* PF)
+{
+    CSLAM_NEED(h);
+    long long i  = 0;
+    const int rc = B(h)->best_particle(nullptr, pick, &i, w, Xv, Pv, XF, PF);
+    if (rc == CSLAM_OK && index)
+    {
+        *index = (int)i;
+    }
+    return rc;
+}
+
+int cslam_pf_estimate(cslam_pf_t h, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF)
+{
+    CSLAM_NEED(h);
+    return B(h)->estimate(nullptr, w_sum, neff, Xv, Pv, XF, PF);
+}
+
+int cslam_pf_get_all_features(cslam_pf_t h, void* XF_all)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_all_features(XF_all);
+}
+
+int cslam_pf_best_particle_sharded(cslam_pf_t h, cslam_comm_t comm, int pick, long long* global_index, void* w, void* Xv,
+                                   void* Pv, void* XF, void* PF)
+{
+    CSLAM_NEED(h);
+    if (!comm)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pf_best_particle_sharded: null communicator");
+    }
+    return B(h)->best_particle(reinterpret_cast<Comm*>(comm), pick, global_index, w, Xv, Pv, XF, PF);
+}
+
+int cslam_pf_estimate_sharded(cslam_pf_t h, cslam_comm_t comm, double* w_sum, double* neff, void* Xv, void* Pv, void* XF,
+                              void* PF)
+{
+    CSLAM_NEED(h);
+    if (!comm)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pf_estimate_sharded: null communicator");
+    }
+    return B(h)->estimate(reinterpret_cast<Comm*>(comm), w_sum, neff, Xv, Pv, XF, PF);
 }
 
 } // extern "C"

@@ -22,6 +22,7 @@ world_size-2 gloo tests exercise with a numpy stand-in for the shard.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import List, Sequence, Tuple
 
 import numpy as np
@@ -180,6 +181,12 @@ class LoopbackComm:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._owner["L"].cslam_comm_destroy(self._h)
             self._h = C.c_void_p(None)
+
+
+# what the read path returns (arrays in the shard's dtype: Xv 3, Pv 3x3, XF 2 x nf, PF 4 x nf, column-major)
+BestParticle = namedtuple("BestParticle", "index w Xv Pv XF PF")
+Estimate = namedtuple("Estimate", "w_sum neff Xv Pv XF PF")  # XF / PF are None when the map was not asked for
+_PICKS = {"max": _capi.PF_PICK_MAX, "min": _capi.PF_PICK_MIN}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -393,6 +400,56 @@ class ParticleShard:
         check(self._L.cslam_pf_get_particle(self._h, C.c_int(i), _vp(w), _vp(Xv), _vp(Pv), _vp(XF) if nf else None,
                                             _vp(PF) if nf else None))
         return w[0], Xv, Pv, XF, PF
+
+    # ---- the estimate, read from the set in HBM (no per-particle downloads)
+    def _record(self, with_map: bool):
+        nf = self.n_features if with_map else 0
+        bufs = [np.zeros(3, self.dtype), np.zeros((3, 3), self.dtype, order="F"),
+                np.zeros((2, nf), self.dtype, order="F"), np.zeros((4, nf), self.dtype, order="F")]
+        ptrs = [_vp(bufs[0]), _vp(bufs[1]), _vp(bufs[2]) if nf else None, _vp(bufs[3]) if nf else None]
+        return bufs, ptrs
+
+    def best_particle(self, pick: str = "max") -> BestParticle:
+        """Slam::extractStatesFromParticles -- slam.h:493-511 -- with the whole record of the chosen particle.
+        pick="max": the maximum-weight particle; "min": the reference's own choice (slam.h:505-506)."""
+        bufs, ptrs = self._record(True)
+        w, idx = np.zeros(1, self.dtype), C.c_int(0)
+        check(self._L.cslam_pf_best_particle(self._h, C.c_int(_PICKS[pick]), C.byref(idx), _vp(w), *ptrs))
+        return BestParticle(idx.value, w[0], *bufs)
+
+    def best_particle_sharded(self, comm, pick: str = "max") -> BestParticle:
+        """best_particle over the set sharded across comm.world ranks; index is the GLOBAL index."""
+        bufs, ptrs = self._record(True)
+        w, idx = np.zeros(1, self.dtype), C.c_longlong(0)
+        check(self._L.cslam_pf_best_particle_sharded(self._h, comm._h, C.c_int(_PICKS[pick]), C.byref(idx), _vp(w), *ptrs))
+        return BestParticle(idx.value, w[0], *bufs)
+
+    def _estimate(self, comm, want_map: bool) -> Estimate:
+        bufs, ptrs = self._record(want_map)
+        ws, ne = C.c_double(0.0), C.c_double(0.0)
+        if comm is None:
+            check(self._L.cslam_pf_estimate(self._h, C.byref(ws), C.byref(ne), *ptrs))
+        else:
+            check(self._L.cslam_pf_estimate_sharded(self._h, comm._h, C.byref(ws), C.byref(ne), *ptrs))
+        if not want_map:
+            bufs[2:] = [None, None]
+        return Estimate(float(ws.value), float(ne.value), *bufs)
+
+    def estimate(self, want_map: bool = True) -> Estimate:
+        """Moments of the weighted mixture (cslam_pf_estimate): sum w, Neff, the pose mean (circular in the heading) and
+        covariance, and -- unless want_map is False -- every feature's mean and covariance."""
+        return self._estimate(None, want_map)
+
+    def estimate_sharded(self, comm, want_map: bool = True) -> Estimate:
+        """estimate over the set sharded across comm.world ranks: identical bits on every rank."""
+        return self._estimate(comm, want_map)
+
+    def all_features(self) -> np.ndarray:
+        """Slam::extractFeaturesFromParticles -- slam.h:513-539: 2 x (n_local * nf), particle p's block at column p * nf."""
+        out = np.zeros((2, self.n_local * self.n_features), self.dtype, order="F")
+        if out.size:
+            check(self._L.cslam_pf_get_all_features(self._h, _vp(out)))
+        return out
 
     def set_particle(self, i: int, w, Xv, Pv, XF, PF):
         XF = np.asfortranarray(np.asarray(XF, dtype=self.dtype).reshape(2, -1, order="F"))

@@ -418,6 +418,46 @@ int cslam_pf_get_particle(cslam_pf_t h, int index, void* w, void* Xv, void* Pv, 
 int cslam_pf_set_particle(cslam_pf_t h, int index, const void* w, const void* Xv, const void* Pv,
                           const void* XF, const void* PF, int nf);
 
+/* ---- reading the estimate out of the particle set held in HBM.  Every call below is ordered on the handle's stream
+ * behind whatever is queued, runs a few kernels, brings its results to the host with ONE copy, synchronises, and never
+ * modifies the store.  Outputs are scalars of the handle's dtype (as for cslam_pf_get_particle): Xv 3, Pv 9
+ * (column-major), XF 2*nf, PF 4*nf; any output pointer may be NULL, and with XF and PF both NULL (or nf = 0, which
+ * leaves them untouched) the map kernels are skipped.
+ *
+ * cslam_pf_best_particle replaces Slam::extractStatesFromParticles(particles)  -- slam.h:493-511, called once per
+ * iteration by the PF loop (test/main.cpp:330) -- and returns the chosen particle's whole record, not only its pose.
+ * pick = CSLAM_PF_PICK_MAX chooses the particle of maximum weight, which is what the reference meant;
+ * CSLAM_PF_PICK_MIN the one of minimum weight, which is what slam.h:505-506 does (`result.first` of
+ * std::minmax_element is the minimum).  Ties go to the lowest index (minmax_element's "first"), a
+ * NaN weight is never chosen, and if every weight is NaN the index is 0.
+ *
+ * cslam_pf_estimate has no counterpart in the reference: the moments of the mixture that the weighted particles form.
+ *   *w_sum = W = sum w, *neff = W^2 / sum w^2,
+ *   Xv = (sum w x / W, sum w y / W, atan2(sum w sin phi, sum w cos phi))           -- the heading mean is circular
+ *   Pv = sum w (Pv_p + d d^T) / W,  d = (x - xbar, y - ybar, pi2pi(phi - phibar))  -- pi2pi: slam.h:816-829
+ *   XF[f] = sum w XF_pf / W,  PF[f] = sum w (PF_pf + d d^T) / W,  d = XF_pf - XF[f],   for every feature f < nf
+ * accumulated in double in a fixed order (the same store gives the same bits) with centred second moments.  If W is
+ * zero, negative or not finite the call still returns CSLAM_OK: *w_sum is W as computed, *neff and every moment are NaN.
+ *
+ * cslam_pf_get_all_features replaces Slam::extractFeaturesFromParticles(particles)  -- slam.h:513-539: XF_all is the
+ * 2 x (n_particles * nf) column-major matrix that slam.h:531-536 assembles, particle p's 2 x nf block at column p * nf. */
+#define CSLAM_PF_PICK_MAX 0 /* what the reference meant        */
+#define CSLAM_PF_PICK_MIN 1 /* what slam.h:505-506 does        */
+int cslam_pf_best_particle(cslam_pf_t h, int pick, int* index, void* w, void* Xv, void* Pv, void* XF, void* PF);
+int cslam_pf_estimate(cslam_pf_t h, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF);
+int cslam_pf_get_all_features(cslam_pf_t h, void* XF_all);
+/* The same two reads (slam.h:493-511 and the mixture moments) over a set SHARDED as for cslam_pf_resample_sharded: rank r
+ * owns the global indices [r * n_particles, (r + 1) * n_particles).  Every rank makes the same call with the same pick
+ * and the same choice of NULL map pointers (from its own host thread on a loopback communicator).  Each rank reduces
+ * its particles to a summary -- per moment group W, the mean and the second moment centred on that mean; its best
+ * weight, global index and record --, one all-gather carries the summaries as doubles (one more, in the handle's dtype,
+ * the best records), and every rank merges them in rank order (a pairwise Chan update; the lowest global index wins
+ * ties), so that all ranks return identical bits.  A communicator of one rank gives the unsharded call's bits. */
+int cslam_pf_best_particle_sharded(cslam_pf_t h, cslam_comm_t comm, int pick, long long* global_index, void* w, void* Xv,
+                                   void* Pv, void* XF, void* PF);
+int cslam_pf_estimate_sharded(cslam_pf_t h, cslam_comm_t comm, double* w_sum, double* neff, void* Xv, void* Pv, void* XF,
+                              void* PF);
+
 /* ------------------------------------------------------------------------------------------------
  * Device-side observation generator and known-association table: the per-step host work of
  * the reference's driver (test/main.cpp:139-165) -- a visibility filter over all landmarks and a table lookup per

@@ -17,6 +17,9 @@
 //   HipPF::resampleParticles slam.h:871-872   PF.cpp:473-500         -> cslam_pf_resample_local / _sharded
 //   HipPF (particle-set forms of) predict / observeHeading / sampleProposal / featureUpdate / addOneNewFeature
 //                            slam.h:858-863, 796, 881-884, 549-552, 134; PF.cpp:419-471, 382-417, 502-544, 222-277, 9-60
+//   HipPF::extractStates     slam.h:493-511                          -> cslam_pf_best_particle
+//   HipPF::extractFeatures   slam.h:513-539                          -> cslam_pf_get_all_features
+//   HipPF::extractMap        (the mixture's feature means)           -> cslam_pf_estimate
 //
 // Ownership: the reference passes X and P by reference into every call; here the handle owns them in HBM.  X is
 // refreshed after every call (the driver reads it every iteration, test/main.cpp:136); P is refreshed on demand
@@ -346,6 +349,46 @@ class HipPF : public PF
     }
     float lastNeff() const { return lastNeff_; }
     bool  lastResampled() const { return lastResampled_; }
+
+    // ---- the estimate, read from the set held in HBM (no download())
+    /// slam.h:493-511 (the PF loop prints it on every iteration, test/main.cpp:330): the pose of the maximum-weight
+    /// particle, which is what the reference meant; referencePick = true takes the MINIMUM-weight particle, which is
+    /// what slam.h:505-506 does (`result.first` of std::minmax_element)
+    Eigen::VectorXf extractStates(bool referencePick = false)
+    {
+        Eigen::VectorXf X;
+        X.resize(3);
+        report(cslam_pf_best_particle(h_, referencePick ? CSLAM_PF_PICK_MIN : CSLAM_PF_PICK_MAX, nullptr, nullptr, X.data(),
+                                      nullptr, nullptr, nullptr),
+               "HipPF::extractStates");
+        return X;
+    }
+    /// slam.h:513-539: every particle's features side by side, 2 x (numParticles * nf), particle p's block at column p * nf
+    Eigen::MatrixXf extractFeatures()
+    {
+        int np = 0, nf = 0;
+        cslam_pf_get_counts(h_, &np, &nf);
+        Eigen::MatrixXf XF;
+        XF.resize(2, static_cast<long>(np) * nf);
+        if (nf > 0)
+        {
+            report(cslam_pf_get_all_features(h_, XF.data()), "HipPF::extractFeatures");
+        }
+        return XF;
+    }
+    /// the map the particle set stands for: the weighted mean of every feature over the particles, 2 x nf
+    Eigen::MatrixXf extractMap()
+    {
+        int np = 0, nf = 0;
+        cslam_pf_get_counts(h_, &np, &nf);
+        Eigen::MatrixXf XF;
+        XF.resize(2, nf);
+        if (nf > 0)
+        {
+            report(cslam_pf_estimate(h_, nullptr, nullptr, nullptr, nullptr, XF.data(), nullptr), "HipPF::extractMap");
+        }
+        return XF;
+    }
 
   private:
     cslam_pf_t      h_    = nullptr;
