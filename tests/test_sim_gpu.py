@@ -101,3 +101,40 @@ def test_device_resident_scan_feeds_the_engine(gpu_required):
     a.close()
     b.close()
     sim.close()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("N", [1023, 1024, 1025, 2049])
+def test_table_association_beyond_one_pass_of_the_workgroup(gpu_required, dtype, N):
+    """sim_associate_table_body walks the scan in passes of 1024 threads with two workgroup-wide scans per pass.  Every
+    landmark is in front of the pose and inside rmax, so scan position i holds tag i + 1; the preset table makes known
+    and new tags alternate in runs of 7 of which one covers positions 1018 .. 1024 and one starts at 2047 (the counts
+    carried from pass to pass change inside a run), with a shuffled state position for every known tag.  ZF, ZN, idf and
+    the table are copies and integers: bit for bit the oracle's sequential loop.  Then a second scan from another pose,
+    on the table the first one left."""
+    from conan_slam_amd import Simulator
+
+    rng = np.random.default_rng(N)
+    LM = np.asfortranarray(np.stack([rng.uniform(10.0, 300.0, size=N), rng.uniform(-200.0, 200.0, size=N)]).astype(dtype))
+    run = ((np.arange(2049) + 4) // 7) % 2 == 0              # the pattern at its full length, whatever N cuts off
+    assert len(set(run[1018:1025])) == 1 and run[1017] != run[1018] and run[2046] != run[2047] == run[2048]
+    known = run[:N]
+    table = np.zeros(N, dtype=np.int32)
+    nf = int(known.sum())
+    table[known] = rng.permutation(nf) + 1
+    o = Oracle(dtype)
+    sim = Simulator(LM, dtype=dtype)
+    sim.table = table
+    for xv in ([0.0, 0.0, 0.0], [-5.0, 3.0, 0.05]):
+        xv = np.array(xv, dtype=dtype)
+        Z, tags = sim.get_observations(xv, 1000.0)
+        assert np.array_equal(tags, np.arange(1, N + 1))
+        ZF, ZN, idf = sim.data_associate_table(nf)
+        ZFo, ZNo, idfo = o.data_associate_table(Z, tags, table, nf)     # (advances `table` in place)
+        assert np.array_equal(idf, idfo), (N, np.nonzero(idf != idfo)[0][:5] if idf.shape == idfo.shape else (idf.shape, idfo.shape))
+        assert ZF.shape == ZFo.shape and ZN.shape == ZNo.shape
+        assert np.array_equal(ZF, ZFo) and np.array_equal(ZN, ZNo)
+        assert np.array_equal(sim.table, table)
+        nf += ZN.shape[1]
+    assert nf == N and ZN.shape[1] == 0 and np.array_equal(np.sort(table), np.arange(1, N + 1))
+    sim.close()
