@@ -61,6 +61,23 @@ PF_ESTIMATE_SYMBOLS = tuple(k for k in _PROTOTYPES if k.startswith("cslam_pf_"))
 PF_PICK_MAX, PF_PICK_MIN = 0, 1
 SIM_BATCH_SYMBOLS = tuple(k for k in _PROTOTYPES if "sim_batch" in k or k.endswith("_scan"))
 
+# The score of a Monte-Carlo study kept on the device (cslam_ekf_batch_score_*): indices into one instance's totals, in the
+# order of the enum in include/cslam.h, and the prototypes.
+SCORE_FIELD_NAMES = ("POSE_N", "POSE_BAD", "POSE_IN", "POSE_ERR2", "POSE_EPHI2", "POSE_NEES",
+                     "LM_N", "LM_BAD", "LM_IN", "LM_ERR2", "LM_NEES")
+(SCORE_POSE_N, SCORE_POSE_BAD, SCORE_POSE_IN, SCORE_POSE_ERR2, SCORE_POSE_EPHI2, SCORE_POSE_NEES,
+ SCORE_LM_N, SCORE_LM_BAD, SCORE_LM_IN, SCORE_LM_ERR2, SCORE_LM_NEES) = range(len(SCORE_FIELD_NAMES))
+SCORE_FIELDS = len(SCORE_FIELD_NAMES)
+_PROTOTYPES.update({
+    "cslam_ekf_batch_score_reset": [C.c_void_p, C.c_int, C.c_double, C.c_double],
+    "cslam_ekf_batch_score_set_truth": [C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_ekf_batch_score": [C.c_void_p, C.c_void_p],
+    "cslam_ekf_batch_score_scan": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "cslam_ekf_batch_get_scores": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                   C.POINTER(C.c_longlong)],
+})
+SCORE_SYMBOLS = tuple(k for k in _PROTOTYPES if "_score" in k)
+
 
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""

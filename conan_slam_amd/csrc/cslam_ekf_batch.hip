@@ -33,6 +33,7 @@
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_pose_kernels.hpp"
+#include "ekf_score_kernels.hpp"
 #include "sim_scan_view.hpp"
 
 using namespace cslam;
@@ -157,6 +158,18 @@ struct cslam_ekf_batch
     long long                                    prof_seen  = 0;
     std::vector<std::pair<Event, Event>>           prof_ev;
     size_t                                       prof_used = 0;
+
+    // the score (cslam_ekf_batch_score_*, ekf_score_kernels.hpp): everything is allocated by the first score call or by
+    // score_reset, nothing per call.  The call count lives on the host: a call's series record index is a kernel argument.
+    DevBuf<double> dScore;      // totals [I][CSLAM_SCORE_FIELDS]
+    DevBuf<double> dScoreParts; // [I][score_blocks()][kScoreParts]: the workgroups' partial sums of one call
+    DevBuf<float>  dSeries;     // [series_cap][I][4]
+    DevBuf<float>  dTruth;      // [max_landmarks][2]; NaN: no truth for this feature
+    int            series_cap = 0;
+    long long      score_calls = 0;
+    double         gate_pose = 7.8147, gate_lm = 5.9915; // the 95 % chi-square points of 3 and 2 degrees of freedom
+    int            truth_count = 0; // features scored: rows given by set_truth, or the batch's features in scan mode
+    int            truth_scan  = 0; // rows the truth gather of score_scan has filled
 
     static constexpr int kWcols = 128; // columns per instance and region: one window's panels
 
@@ -540,6 +553,51 @@ struct cslam_ekf_batch
 
     int predict_width() const { return std::max((quirks & CSLAM_Q_PREDICT_NM4) ? (n - 4) : (n - 3), 0); }
 
+    // ---------------------------------------------------------------- the score
+    int max_landmarks() const { return (ncap - 3) / 2; }
+    int score_blocks() const { return (std::max(max_landmarks(), 1) + 255) / 256; }
+
+    // the buffers every score call needs; all-or-nothing (device_owners.hpp)
+    int ensure_score()
+    {
+        if (dScore.get())
+        {
+            return CSLAM_OK;
+        }
+        DevBuf<double> t, p;
+        DevBuf<float>  tr;
+        const size_t   rows = (size_t)std::max(max_landmarks(), 1);
+        int            rc   = t.alloc_zeroed((size_t)I * CSLAM_SCORE_FIELDS, stream);
+        if (rc || (rc = p.alloc((size_t)I * score_blocks() * kScoreParts)) || (rc = tr.alloc(2 * rows)))
+        {
+            return rc;
+        }
+        CSLAM_HIP_TRY(hipMemsetAsync(tr.get(), 0xFF, 2 * rows * sizeof(float), stream)); // (all bits set: a NaN)
+        dScore      = std::move(t);
+        dScoreParts = std::move(p);
+        dTruth      = std::move(tr);
+        return CSLAM_OK;
+    }
+
+    // one score step of what is on the main stream now; the caller has drained the queue
+    int score_launch(const float* xv)
+    {
+        const int count  = std::min(truth_count, (n - 3) / 2);
+        const int blocks = (count + 255) / 256;
+        if (count > 0)
+        {
+            hipLaunchKernelGGL(ekf_score_landmarks_batch, dim3(blocks, I), dim3(256), 0, stream, dX.get(), dPv.get(),
+                               dP.get(), ldp, wregion(wcur), (long)sW(), kp, count, dTruth.get(), gate_lm,
+                               dScoreParts.get());
+        }
+        const int record = score_calls < (long long)series_cap ? (int)score_calls : -1;
+        hipLaunchKernelGGL(ekf_score_finish_batch, dim3(I), dim3(64), 0, stream, dX.get(), dPv.get(), ldp,
+                           dScoreParts.get(), blocks, xv[0], xv[1], xv[2], gate_pose, dScore.get(), dSeries.get(), record, I);
+        CSLAM_HIP_TRY(hipGetLastError());
+        score_calls++;
+        return CSLAM_OK;
+    }
+
     // one window: updates a (and b when nu == 2) of every instance, with their held predicts
     int window(const LaBatchWin& w0)
     {
@@ -890,6 +948,123 @@ int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, flo
         CSLAM_HIP_TRY(hipMemcpyAsync(pvl, opvl, 6 * c * sizeof(float), hipMemcpyDeviceToHost, h->stream));
     }
     CSLAM_HIP_TRY(hipStreamSynchronize(h->stream));
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_score_reset(cslam_ekf_batch_t h, int series_capacity, double gate_pose, double gate_lm)
+{
+    if (!h || series_capacity < 0 || gate_pose != gate_pose || gate_lm != gate_lm)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_score_reset: bad arguments (series_capacity %d)", series_capacity);
+    }
+    int rc = h->use_device();
+    if (rc || (rc = h->ensure_score()))
+    {
+        return rc;
+    }
+    if ((size_t)series_capacity * h->I * 4 > h->dSeries.count())
+    {
+        DevBuf<float> sr;
+        if ((rc = sr.alloc((size_t)series_capacity * h->I * 4)))
+        {
+            return rc;
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(h->stream)); // (a score kernel in flight may still write the old series)
+        h->dSeries = std::move(sr);
+    }
+    // behind the score kernels already on the stream
+    CSLAM_HIP_TRY(hipMemsetAsync(h->dScore.get(), 0, (size_t)h->I * CSLAM_SCORE_FIELDS * sizeof(double), h->stream));
+    if (series_capacity > 0)
+    {
+        CSLAM_HIP_TRY(hipMemsetAsync(h->dSeries.get(), 0, (size_t)series_capacity * h->I * 4 * sizeof(float), h->stream));
+    }
+    h->series_cap  = series_capacity;
+    h->score_calls = 0;
+    h->gate_pose   = gate_pose > 0.0 ? gate_pose : 7.8147;
+    h->gate_lm     = gate_lm > 0.0 ? gate_lm : 5.9915;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_score_set_truth(cslam_ekf_batch_t h, const float* lm_true, int count)
+{
+    if (!h || count < 0 || (count > 0 && !lm_true) || count > h->max_landmarks())
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_score_set_truth: bad arguments (count %d, max_landmarks %d)", count,
+                    h ? h->max_landmarks() : 0);
+    }
+    int rc = h->use_device();
+    if (rc || (rc = h->ensure_score()))
+    {
+        return rc;
+    }
+    const size_t rows = (size_t)std::max(h->max_landmarks(), 1);
+    if (count > 0)
+    {
+        CSLAM_HIP_TRY(hipMemcpyAsync(h->dTruth.get(), lm_true, 2 * (size_t)count * sizeof(float), hipMemcpyHostToDevice,
+                                     h->stream));
+    }
+    if ((size_t)count < rows)
+    {
+        CSLAM_HIP_TRY(hipMemsetAsync(h->dTruth.get() + 2 * (size_t)count, 0xFF, 2 * (rows - count) * sizeof(float), h->stream));
+    }
+    CSLAM_HIP_TRY(hipStreamSynchronize(h->stream)); // (lm_true is pageable host memory: consumed before the call returns)
+    h->truth_count = count;
+    h->truth_scan  = 0;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_score(cslam_ekf_batch_t h, const float* xv_true)
+{
+    if (!h || !xv_true)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_score: bad arguments");
+    }
+    int rc = h->use_device();
+    if (rc || (rc = h->ensure_score()) || (rc = h->drain()))
+    {
+        return rc;
+    }
+    return h->score_launch(xv_true);
+}
+
+int cslam_ekf_batch_get_scores(cslam_ekf_batch_t h, double* totals, float* series, int capacity_records, int* records,
+                               long long* calls)
+{
+    if (!h || capacity_records < 0)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_get_scores: bad arguments");
+    }
+    int rc = h->use_device();
+    if (rc || (rc = h->drain()) || (rc = h->sync()))
+    {
+        return rc;
+    }
+    const int held = (int)std::min<long long>(h->score_calls, h->series_cap);
+    if (totals)
+    {
+        if (h->dScore.get())
+        {
+            CSLAM_HIP_TRY(hipMemcpy(totals, h->dScore.get(), (size_t)h->I * CSLAM_SCORE_FIELDS * sizeof(double),
+                                    hipMemcpyDeviceToHost));
+        }
+        else // (never scored)
+        {
+            std::fill(totals, totals + (size_t)h->I * CSLAM_SCORE_FIELDS, 0.0);
+        }
+    }
+    const int take = std::min(held, capacity_records);
+    if (series && take > 0)
+    {
+        CSLAM_HIP_TRY(hipMemcpy(series, h->dSeries.get(), (size_t)take * h->I * 4 * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (records)
+    {
+        *records = held;
+    }
+    if (calls)
+    {
+        *calls = h->score_calls;
+    }
     return CSLAM_OK;
 }
 
@@ -1322,6 +1497,42 @@ int cslam_ekf_batch_augment_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const
     }
     CSLAM_HIP_TRY(hipEventRecord(v.consumed, b->stream));
     return sim_batch_mark(s, kScanAugmented, true);
+}
+
+// The score of an observation step with the truth from the generator: the map and the table are resident, so the rows of
+// the truth buffer the batch has grown into since the last call are gathered on the main stream (the table is ordered by
+// the host: cslam_sim_batch_scan has waited for its kernels), then the score kernels run as for cslam_ekf_batch_score.
+int cslam_ekf_batch_score_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* xv_true)
+{
+    SimScanView v;
+    int         rc = scan_view_for("ekf_batch_score_scan", b, s, &v);
+    if (rc)
+    {
+        return rc;
+    }
+    if (!xv_true)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_score_scan: null pose");
+    }
+    if ((rc = b->use_device()) || (rc = b->ensure_score()) || (rc = b->drain()))
+    {
+        return rc;
+    }
+    const int nf = (b->n - 3) / 2;
+    if (b->truth_scan < nf && v.nlm > 0)
+    {
+        hipLaunchKernelGGL(ekf_score_gather_truth, dim3((v.nlm + 255) / 256), dim3(256), 0, b->stream, v.LM, v.table, v.nlm,
+                           b->truth_scan, nf, b->dTruth.get());
+        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_HIP_TRY(hipEventRecord(v.consumed, b->stream)); // (the generator's destructor waits for its readers)
+        if ((rc = sim_batch_mark(s, 0, true)))
+        {
+            return rc;
+        }
+        b->truth_scan = nf;
+    }
+    b->truth_count = nf;
+    return b->score_launch(xv_true);
 }
 
 } // extern "C"

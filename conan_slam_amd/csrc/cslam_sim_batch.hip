@@ -304,6 +304,9 @@ int sim_batch_current(cslam_sim_batch_t s, SimScanView* v)
     v->idftab    = s->dIdftab.get() + (size_t)s->cur * s->I;
     v->ZN        = s->zn(s->cur);
     v->consumed  = k.ev.get();
+    v->LM        = s->dLM.get();
+    v->table     = s->dTable.get();
+    v->nlm       = s->nlm;
     return CSLAM_OK;
 }
 

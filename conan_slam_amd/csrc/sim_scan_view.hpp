@@ -23,6 +23,9 @@ struct SimScanView
     const int* const*   idftab; // device [instances]: the common idf (mf)
     const float*        ZN;     // device: instance i's ZN (2 x mn) at ZN + i * kScanStride
     hipEvent_t          consumed; // to be recorded behind the last kernel that reads the slot
+    const float*        LM;       // device [nlm][2]: the true map (read by the score's truth gather)
+    const int*          table;    // device [nlm]: tag t -> state feature table[t - 1], 0: not seen yet
+    int                 nlm;
 };
 
 enum

@@ -413,6 +413,44 @@ class EKFBatch:
         R = np.asfortranarray(R, dtype=np.float32)
         check(self._L.cslam_ekf_batch_augment_scan(self._h, sim._h, _vp(R)))
 
+    # ------------------------------------------------------------------ the score, kept on the device
+    def score_reset(self, series_capacity: int = 0, gate_pose: float = 0.0, gate_lm: float = 0.0):
+        """Zeroes the totals, the series (room for `series_capacity` records, one per score call) and the call count.  A
+        gate <= 0 is the 95 % chi-square point (7.8147 for the pose, 5.9915 for a landmark)."""
+        check(self._L.cslam_ekf_batch_score_reset(self._h, C.c_int(int(series_capacity)), C.c_double(gate_pose),
+                                                  C.c_double(gate_lm)))
+        self._series_capacity = int(series_capacity)
+
+    def score_set_truth(self, lm_true):
+        """lm_true [count, 2]: the true position of state feature j + 1 in row j.  Features beyond count are not scored."""
+        t = np.ascontiguousarray(lm_true, dtype=np.float32).reshape(-1, 2)
+        check(self._L.cslam_ekf_batch_score_set_truth(self._h, _vp(t) if t.size else None, C.c_int(t.shape[0])))
+
+    def score(self, xv_true):
+        """One score step against the true pose (x, y, phi): pose error and NEES, map error and landmark NEES of every
+        instance enter the totals on the device.  Launches what is queued as landmarks() does; does not synchronise, copies
+        nothing back and leaves the run bit for bit as without the call (cslam_ekf_batch_score)."""
+        xv = np.ascontiguousarray(xv_true, dtype=np.float32).reshape(3)
+        check(self._L.cslam_ekf_batch_score(self._h, _vp(xv)))
+
+    def score_scan(self, sim, xv_true):
+        """score() with the true positions taken from a BatchSimulator's map through its association table."""
+        xv = np.ascontiguousarray(xv_true, dtype=np.float32).reshape(3)
+        check(self._L.cslam_ekf_batch_score_scan(self._h, sim._h, _vp(xv)))
+
+    def scores(self):
+        """-> (totals [I, SCORE_FIELDS] float64, series [records, I, 4] float32, calls).  Synchronises.  The columns of
+        totals are _capi.SCORE_FIELD_NAMES; a series record holds pose err^2, pose NEES, mean landmark err^2 and mean
+        landmark NEES of one call (NaN where there is none)."""
+        I = self.instances
+        cap = getattr(self, "_series_capacity", 0)
+        totals = np.zeros((I, _capi.SCORE_FIELDS), dtype=np.float64)
+        series = np.zeros((max(cap, 1), I, 4), dtype=np.float32)
+        rec, calls = C.c_int(0), C.c_longlong(0)
+        check(self._L.cslam_ekf_batch_get_scores(self._h, _vp(totals), _vp(series), C.c_int(cap), C.byref(rec),
+                                                 C.byref(calls)))
+        return totals, series[: min(rec.value, cap)].copy(), calls.value
+
     def flush(self):
         check(self._L.cslam_ekf_batch_flush(self._h))
 

@@ -273,6 +273,48 @@ int cslam_ekf_batch_get_poses(cslam_ekf_batch_t h, float* x, float* pvv);
  * the run continues bit for bit as without the read.  For Monte-Carlo scoring of the map (landmark error and NEES,
  * e^T P_jj^-1 e) in place of get_state (test/main.cpp:107-108; the blocks EKF.cpp:131-144 reads).  Synchronises. */
 int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, float* x, float* pll, float* pvl);
+
+/* ---- the score of a Monte-Carlo study, kept on the device (conan_slam_amd/csrc/ekf_score_kernels.hpp).  The reference
+ *      has no scorer: these calls replace the host-side scoring a study does with get_poses and get_landmarks after every
+ *      observation step -- the pose test/main.cpp:136 prints against the true pose, and the blocks EKF.cpp:131-144 reads
+ *      against a true position per state feature.  All error and NEES arithmetic is f64 on the device from the f32
+ *      state; the sums are formed in a fixed order without atomics, so the totals of a run are reproducible bit for
+ *      bit.  f32 batch only: the single handle, the f64 engine and the particle filter have no scorer.
+ * Indices into one instance's totals (doubles): */
+enum { CSLAM_SCORE_POSE_N, CSLAM_SCORE_POSE_BAD, CSLAM_SCORE_POSE_IN, CSLAM_SCORE_POSE_ERR2 /* sum ex^2+ey^2 */,
+       CSLAM_SCORE_POSE_EPHI2 /* sum wrapped heading error^2 */, CSLAM_SCORE_POSE_NEES /* sum e^T Pvv^-1 e */,
+       CSLAM_SCORE_LM_N, CSLAM_SCORE_LM_BAD, CSLAM_SCORE_LM_IN, CSLAM_SCORE_LM_ERR2, CSLAM_SCORE_LM_NEES,
+       CSLAM_SCORE_FIELDS };
+/* Zeroes the totals, the series and the call count (replaces scoring state kept on the host beside test/main.cpp:136).
+ * series_capacity >= 0 records of [instances][4] floats (0: totals only).  A gate <= 0 selects the 95 % chi-square
+ * point: 7.8147 for the pose (3 degrees of freedom), 5.9915 for a landmark (2).  The truth rows are kept.  A score call
+ * without a prior reset behaves as after score_reset(h, 0, 0, 0).  A handle that never calls a score function allocates
+ * nothing for it. */
+int cslam_ekf_batch_score_reset(cslam_ekf_batch_t h, int series_capacity, double gate_pose, double gate_lm);
+/* The true position of state feature j + 1 is row j of lm_true (host, [count][2]; the features of EKF.cpp:131-144),
+ * copied into a device buffer sized for max_landmarks before the call returns.  Features beyond `count` are not scored.
+ * count > max_landmarks: CSLAM_ERR_BAD_ARG, nothing changed. */
+int cslam_ekf_batch_score_set_truth(cslam_ekf_batch_t h, const float* lm_true /* host [count][2] */, int count);
+/* One score step against the true pose xv_true (host [3], consumed before the call returns; the pose of
+ * test/main.cpp:136 and the blocks of EKF.cpp:131-144).  Launches what is queued exactly as get_landmarks does (no
+ * covariance downdate: the pending columns stay pending and the run continues bit for bit as without the call), then
+ * the score kernels on the main stream, and returns when the work is enqueued: no synchronise, no device-to-host copy.
+ *   pose      e = (x - xt, y - yt, wrap(phi - phit)) with the heading error wrapped to (-pi, pi]; NEES = e^T Pvv^-1 e by
+ *             a 3 x 3 Cholesky.  A pivot <= 0 or anything non-finite: POSE_BAD += 1, nothing enters the sums.  Otherwise
+ *             POSE_N, ERR2, EPHI2, NEES accumulate and POSE_IN += (NEES <= gate_pose).
+ *   landmark  e = x_j - truth_j, NEES = (p11 e0^2 - 2 p10 e0 e1 + p00 e1^2) / det over the 2 x 2 marginal get_landmarks
+ *             would return.  p00 <= 0, det <= 0 or anything non-finite (a truth row included): LM_BAD += 1.  Otherwise
+ *             as the pose, with gate_lm.
+ *   series    while there is room, one record per call and instance: pose err^2, pose NEES, mean landmark err^2, mean
+ *             landmark NEES over this call's valid landmarks; NaN where there is none. */
+int cslam_ekf_batch_score(cslam_ekf_batch_t h, const float* xv_true /* host [3] */);
+/* Launches what is queued, synchronises, and copies the totals [instances][CSLAM_SCORE_FIELDS] and up to
+ * capacity_records series records [records][instances][4] (the read-out that replaces a get_poses / get_landmarks pair
+ * per step: test/main.cpp:136, EKF.cpp:131-144).  *records = min(calls, series_capacity) is the number of records held
+ * (at most capacity_records of them are copied), *calls counts every score call since the reset (calls beyond the
+ * series capacity still enter the totals).  Any output pointer may be NULL. */
+int cslam_ekf_batch_get_scores(cslam_ekf_batch_t h, double* totals /* [I][CSLAM_SCORE_FIELDS] */,
+                               float* series /* [records][I][4] */, int capacity_records, int* records, long long* calls);
 /* Slam::observeHeading (slam.h:788, EKF.cpp:328-352, josephUpdate slam.h:700-725) on every instance.  phi is common,
  * as in the reference driver, which observes the true heading.  Deliberate difference from the single handle: an
  * instance whose S = P22 + R is <= 0 or non-finite (an indefinite P; a healthy filter never has one) skips the heading
@@ -525,6 +567,15 @@ int cslam_sim_batch_set_table(cslam_sim_batch_t h, const int* table);
  * (n - 3) / 2 is not the nf the scan was split against, a scan consumed twice, the wrong order, no current scan. */
 int cslam_ekf_batch_update_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* R);
 int cslam_ekf_batch_augment_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* R);
+/* cslam_ekf_batch_score with the truth taken from the generator (the map and the table of test/main.cpp:139-165, the
+ * blocks of EKF.cpp:131-144): for every tag t with table[t - 1] = p, 1 <= p <= (n - 3) / 2 of the batch, feature p's true
+ * position is LM[:, t - 1].  A position is assigned once and never changes, so a gather kernel fills the rows of the
+ * truth buffer not filled yet, and every feature of the batch is scored (a feature the table does not hold has no truth
+ * and counts in LM_BAD).  Positions beyond the batch's feature count are ignored: the table may run a scan ahead.
+ * cslam_sim_batch_scan has waited for its kernels when it returns, so the table is ordered by the host.  Replaces rows
+ * given with score_set_truth.  CSLAM_ERR_BAD_ARG with nothing changed: different instance counts or devices, no current
+ * scan. */
+int cslam_ekf_batch_score_scan(cslam_ekf_batch_t b, cslam_sim_batch_t s, const float* xv_true /* host [3] */);
 
 #ifdef __cplusplus
 }

@@ -21,8 +21,17 @@ BatchSimulator for all instances, consumed with EKFBatch.update_scan / augment_s
 an observation step is made: `late` right before it is consumed, `early` right after the previous scan was consumed
 (the table depends only on the sequence of scans), while that window is still running.
 
+--score says who scores.  `host` (the default): the separate accuracy pass described above, poses() and landmarks() after
+every observation step and numpy on the host.  `device`: EKFBatch.score (tape) / score_scan (generator) at the same
+points INSIDE a timed pass -- the totals and the series stay on the device until the pass ends -- and the same four
+summary keys from them (pose_rmse_m, mean_nees, map_rmse_m from the totals; mean_landmark_nees keeps its meaning, the
+mean over observation steps of the step's mean, from the series; pooled_landmark_nees is LM_NEES / LM_N), plus the
+fraction inside each 95 % gate and per observation step the run-averaged pose NEES.  `both`: both, with the largest
+relative difference of the four numbers between them (the host scorer is then given the f32 truth the device holds).
+scored_steps_per_s is the rate of the pass that scores, for either scorer.
+
     python tools/mc_demo.py [--instances 8] [--steps 2400] [--seed 1000] [--quirks textbook|ref_exact]
-                            [--generator tape|device] [--placement late|early|both]
+                            [--generator tape|device] [--placement late|early|both] [--score host|device|both]
 """
 import argparse
 import json
@@ -166,6 +175,72 @@ def pack(recs):
             torch.from_numpy(np.ascontiguousarray(ids)).cuda())
 
 
+class HostScorer:
+    """score(step, b) on the host: pose error and NEES from poses(), map error and landmark NEES from landmarks()."""
+
+    def __init__(self, I, truth, lm_true):
+        self.I, self.truth, self.lm_true = I, truth, lm_true
+        self.err2, self.nees = [[] for _ in range(I)], [[] for _ in range(I)]
+        self.merr2, self.mnees = [[] for _ in range(I)], [[] for _ in range(I)]
+
+    def __call__(self, step, b):
+        I = self.I
+        x, pvv = b.poses()
+        xt = self.truth[step - 1]
+        for i in range(I):
+            e = x[i].astype(np.float64) - xt
+            e[2] = (e[2] + np.pi) % (2 * np.pi) - np.pi
+            self.err2[i].append(float(e[0] ** 2 + e[1] ** 2))
+            try:
+                self.nees[i].append(float(e @ np.linalg.solve(pvv[i].astype(np.float64), e)))
+            except np.linalg.LinAlgError:
+                self.nees[i].append(float("nan"))
+        xl, pll, _ = b.landmarks()
+        e = xl.astype(np.float64) - self.lm_true[None, : xl.shape[1]]
+        for i in range(I):
+            self.merr2[i].extend((e[i] ** 2).sum(axis=1).tolist())
+            try:
+                self.mnees[i].append(float(np.mean(np.einsum("ja,ja->j", e[i], np.linalg.solve(
+                    pll[i].astype(np.float64), e[i][:, :, None])[:, :, 0]))))
+            except np.linalg.LinAlgError:
+                self.mnees[i].append(float("nan"))
+
+    def summary(self):
+        return {"pose_rmse_m": [float(np.sqrt(np.mean(e))) for e in self.err2],
+                "mean_nees": [float(np.nanmean(v)) for v in self.nees],
+                "map_rmse_m": [float(np.sqrt(np.mean(e))) for e in self.merr2],
+                "mean_landmark_nees": [float(np.nanmean(v)) for v in self.mnees]}
+
+
+SUMMARY_DIGITS = {"pose_rmse_m": 4, "mean_nees": 3, "map_rmse_m": 4, "mean_landmark_nees": 3}
+
+
+def rounded(summary):
+    return {k: [round(v, SUMMARY_DIGITS[k]) for v in summary[k]] for k in SUMMARY_DIGITS}
+
+
+def device_summary(totals, series):
+    """The four summary keys and the consistency figures from EKFBatch.scores()."""
+    from conan_slam_amd import _capi as c
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        T = totals
+        four = {"pose_rmse_m": np.sqrt(T[:, c.SCORE_POSE_ERR2] / T[:, c.SCORE_POSE_N]).tolist(),
+                "mean_nees": (T[:, c.SCORE_POSE_NEES] / T[:, c.SCORE_POSE_N]).tolist(),
+                "map_rmse_m": np.sqrt(T[:, c.SCORE_LM_ERR2] / T[:, c.SCORE_LM_N]).tolist(),
+                "mean_landmark_nees": np.nanmean(series[:, :, 3].astype(np.float64), axis=0).tolist()}
+        more = {"pooled_landmark_nees": [round(float(v), 3) for v in T[:, c.SCORE_LM_NEES] / T[:, c.SCORE_LM_N]],
+                "pose_in_gate": [round(float(v), 4) for v in T[:, c.SCORE_POSE_IN] / T[:, c.SCORE_POSE_N]],
+                "landmark_in_gate": [round(float(v), 4) for v in T[:, c.SCORE_LM_IN] / T[:, c.SCORE_LM_N]],
+                "bad_blocks": [int(v) for v in T[:, c.SCORE_POSE_BAD] + T[:, c.SCORE_LM_BAD]],
+                "pose_nees_by_step": [round(float(v), 3) for v in np.nanmean(series[:, :, 1].astype(np.float64), axis=1)]}
+    return four, more
+
+
+def max_rel_diff(dev, host):
+    return {k: float(max(abs(d - h) / abs(h) for d, h in zip(dev[k], host[k]))) for k in SUMMARY_DIGITS}
+
+
 def drive_batch(b, recs, dz, di, score=None):
     """The recorded calls through one EKFBatch.  score(step, b): called after every observation step."""
     I = len(recs)
@@ -276,6 +351,7 @@ def main():
     ap.add_argument("--quirks", choices=["textbook", "ref_exact"], default="textbook")
     ap.add_argument("--generator", choices=["tape", "device"], default="tape")
     ap.add_argument("--placement", choices=["late", "early", "both"], default="both")
+    ap.add_argument("--score", choices=["host", "device", "both"], default="host")
     args = ap.parse_args()
     quirks = Q_TEXTBOOK if args.quirks == "textbook" else Q_REF_EXACT
     I = args.instances
@@ -301,36 +377,39 @@ def main():
         for h in hs:
             h.close()
 
-    # accuracy: pose error and NEES at every observation step, from poses(); map error and landmark NEES from
-    # landmarks() (the features seen so far, truth through the association table)
-    err2, nees = [[] for _ in range(I)], [[] for _ in range(I)]
+    # accuracy: pose error and NEES at every observation step, map error and landmark NEES of the features seen so far
+    # (truth through the association table)
     lm_true = map_truth(args.steps)
-    merr2, mnees = [[] for _ in range(I)], [[] for _ in range(I)]
-
-    def score(step, b):
-        x, pvv = b.poses()
-        xt = truth[step - 1]
-        for i in range(I):
-            e = x[i].astype(np.float64) - xt
-            e[2] = (e[2] + np.pi) % (2 * np.pi) - np.pi
-            err2[i].append(float(e[0] ** 2 + e[1] ** 2))
-            try:
-                nees[i].append(float(e @ np.linalg.solve(pvv[i].astype(np.float64), e)))
-            except np.linalg.LinAlgError:
-                nees[i].append(float("nan"))
-        xl, pll, _ = b.landmarks()
-        e = xl.astype(np.float64) - lm_true[None, : xl.shape[1]]
-        for i in range(I):
-            merr2[i].extend((e[i] ** 2).sum(axis=1).tolist())
-            try:
-                mnees[i].append(float(np.mean(np.einsum("ja,ja->j", e[i], np.linalg.solve(pll[i].astype(np.float64),
-                                                                                            e[i][:, :, None])[:, :, 0]))))
-            except np.linalg.LinAlgError:
-                mnees[i].append(float("nan"))
-
-    b = EKFBatch(I, n_landmarks=0, max_landmarks=64, quirks=quirks)
-    drive_batch(b, recs, dz, di, score)
-    b.close()
+    out, dev, host = {}, None, None
+    if args.score in ("device", "both"):
+        lm32 = lm_true.astype(np.float32)
+        n_calls = sum(1 for c in recs[0] if c[0] == "A")
+        for timed in (False, True):
+            b = EKFBatch(I, n_landmarks=0, max_landmarks=64, quirks=quirks)
+            b.score_reset(n_calls)
+            b.score_set_truth(lm32)
+            t0 = time.perf_counter()
+            drive_batch(b, recs, dz, di, lambda step, b: b.score(truth[step - 1]))
+            t_scored = time.perf_counter() - t0
+            totals, series, _ = b.scores()
+            b.close()
+        dev, more = device_summary(totals, series)
+        out.update(more)
+        if args.score == "both":
+            lm_true = lm32.astype(np.float64)
+    if args.score in ("host", "both"):
+        score = HostScorer(I, truth, lm_true)
+        b = EKFBatch(I, n_landmarks=0, max_landmarks=64, quirks=quirks)
+        t0 = time.perf_counter()
+        drive_batch(b, recs, dz, di, score)
+        t_host = time.perf_counter() - t0
+        b.close()
+        host = score.summary()
+    if args.score == "both":
+        out["host_scored_steps_per_s"] = round(steps / t_host, 1)
+        out["host_summary"] = rounded(host)
+        out["score_max_rel_diff"] = max_rel_diff(dev, host)
+    out["scored_steps_per_s"] = round(steps / (t_host if args.score == "host" else t_scored), 1)
     print(json.dumps({
         "workload": "mc_demo", "generator": "tape", "instances": I, "steps": steps, "quirks": args.quirks,
         "updates": sum(1 for c in recs[0] if c[0] == "U"),
@@ -338,11 +417,8 @@ def main():
         "batch_steps_per_s": round(steps / t_batch, 1),
         "handles_steps_per_s": round(steps / t_handles, 1),
         "speedup": round(t_handles / t_batch, 3),
-        "pose_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in err2],
-        "mean_nees": [round(float(np.nanmean(v)), 3) for v in nees],
-        "map_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in merr2],
-        "mean_landmark_nees": [round(float(np.nanmean(v)), 3) for v in mnees],
-        "factor_status": flags,
+        **rounded(host if args.score == "host" else dev),
+        "factor_status": flags, "score": args.score, **out,
     }))
 
 
@@ -361,12 +437,20 @@ def main_device(args, quirks):
     vn, swan = control_noise(seeds, np.arange(1, steps + 1), cfg.velocity, np.array([s[1] for s in script], np.float32), Q)
     vn, swan = vn.astype(np.float64), swan.astype(np.float64)
 
-    def run(early, score=None):
+    truth = [s[0].astype(np.float64) for s in script]
+    scores = {}
+
+    def run(early, score=None, device_score=False):
         gen = BatchSimulator(LM, I, seeds)
         b = EKFBatch(I, n_landmarks=0, max_landmarks=64, quirks=quirks)
+        if device_score:
+            b.score_reset(sum(1 for s in script if s[2]))
+            score = lambda step, b: b.score_scan(gen, truth[step - 1])  # noqa: E731
         t0 = time.perf_counter()
         counts = drive_device(b, gen, cfg, script, vn, swan, QE, R, RE, early, score)
         t = time.perf_counter() - t0
+        if device_score:
+            scores["device"] = b.scores()
         flags = b.factor_status()
         b.close()
         gen.close()
@@ -382,42 +466,31 @@ def main_device(args, quirks):
     best = {p: min(v) for p, v in times.items() if v}
     place = min(best, key=best.get)
 
-    truth = [s[0].astype(np.float64) for s in script]
     lm_true = map_truth(args.steps)
-    err2, nees = [[] for _ in range(I)], [[] for _ in range(I)]
-    merr2, mnees = [[] for _ in range(I)], [[] for _ in range(I)]
-
-    def score(step, b):
-        x, pvv = b.poses()
-        for i in range(I):
-            e = x[i].astype(np.float64) - truth[step - 1]
-            e[2] = (e[2] + np.pi) % (2 * np.pi) - np.pi
-            err2[i].append(float(e[0] ** 2 + e[1] ** 2))
-            try:
-                nees[i].append(float(e @ np.linalg.solve(pvv[i].astype(np.float64), e)))
-            except np.linalg.LinAlgError:
-                nees[i].append(float("nan"))
-        xl, pll, _ = b.landmarks()
-        e = xl.astype(np.float64) - lm_true[None, : xl.shape[1]]
-        for i in range(I):
-            merr2[i].extend((e[i] ** 2).sum(axis=1).tolist())
-            try:
-                mnees[i].append(float(np.mean(np.einsum("ja,ja->j", e[i], np.linalg.solve(pll[i].astype(np.float64),
-                                                                                            e[i][:, :, None])[:, :, 0]))))
-            except np.linalg.LinAlgError:
-                mnees[i].append(float("nan"))
-
-    _, counts, flags = run(place == "early", score)
+    out, dev, host = {}, None, None
+    if args.score in ("device", "both"):
+        run(place == "early", device_score=True)  # (untimed: the score kernels' code objects and buffers)
+        t_scored, counts, flags = run(place == "early", device_score=True)
+        dev, more = device_summary(scores["device"][0], scores["device"][1])
+        out.update(more)
+        if args.score == "both":
+            lm_true = lm_true.astype(np.float32).astype(np.float64)
+    if args.score in ("host", "both"):
+        score = HostScorer(I, truth, lm_true)
+        t_host, counts, flags = run(place == "early", score)
+        host = score.summary()
+    if args.score == "both":
+        out["host_scored_steps_per_s"] = round(steps / t_host, 1)
+        out["host_summary"] = rounded(host)
+        out["score_max_rel_diff"] = max_rel_diff(dev, host)
+    out["scored_steps_per_s"] = round(steps / (t_host if args.score == "host" else t_scored), 1)
     print(json.dumps({
         "workload": "mc_demo", "generator": "device", "instances": I, "steps": steps, "quirks": args.quirks,
         "updates": int(counts[1]), "max_m": int(counts[2]), "scans": int(counts[0]),
         "batch_steps_per_s": round(steps / best[place], 1), "placement": place,
         "steps_per_s_by_placement": {p: round(steps / t, 1) for p, t in best.items()},
-        "pose_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in err2],
-        "mean_nees": [round(float(np.nanmean(v)), 3) for v in nees],
-        "map_rmse_m": [round(float(np.sqrt(np.mean(e))), 4) for e in merr2],
-        "mean_landmark_nees": [round(float(np.nanmean(v)), 3) for v in mnees],
-        "factor_status": flags,
+        **rounded(host if args.score == "host" else dev),
+        "factor_status": flags, "score": args.score, **out,
     }))
 
 
