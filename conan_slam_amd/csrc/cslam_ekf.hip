@@ -31,8 +31,11 @@
 #include "ekf_kernels_fast.hpp"
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
+#include "ekf_options.hpp"
+#include "ekf_pending_store.hpp"
 #include "ekf_pgemm_limbs.hpp"
 #include "ekf_pose_kernels.hpp"
+#include "ekf_staging.hpp"
 #include "host_linalg.hpp"
 
 namespace cslam
@@ -118,16 +121,14 @@ namespace
 // (CSLAM_LOOKAHEAD=1), and then with stream events only (ev_raw / ev_fb): a plain dependency graph, no waiting kernels.
 std::atomic<int>& g_engines = ::cslam::live_engines();
 
-constexpr int    kStagingSlots = 64;
 constexpr size_t kLdsBudget    = 150 * 1024; // of the 160 KiB per CU, leave room for the small arrays
 
 struct EkfBase
 {
+    explicit EkfBase(const EkfOptions& o) : opt(o) {}
     virtual ~EkfBase() {}
+    const EkfOptions opt; // the engine switches, as the environment had them at cslam_ekf_create (ekf_options.hpp)
     int         dtype    = CSLAM_F32;
-    int         fuse_f64 = 1; // the f64 MFMA kernels take a held predict too (env CSLAM_FUSE_F64=0: its own launch)
-    int         pgemm_limbs_req = -1, limbs_kmin_req = -1; // env CSLAM_PGEMM_LIMBS / CSLAM_LIMBS_KMIN (-1: default)
-    int         xcd_queues_req = -1;                       // env CSLAM_XCD_QUEUES
     int         device   = 0;
     int         quirks   = CSLAM_Q_REF_EXACT;
     int         nmax     = 0; // max landmarks
@@ -135,13 +136,7 @@ struct EkfBase
     int         ldp      = 0; // padded leading dimension / column count
     int         n        = 3;
     int         sync_mode = 1;
-    int         seq_defer     = 1; // sequential update(): one P-GEMM per call (env CSLAM_SEQ_DEFER=0 restores m passes)
-    int         lower         = 0; // block-lower storage of P (f32 default; env CSLAM_STORAGE=full|lower)
-    int         pipeline      = 0; // P-GEMM of update t on stream B under the chain of update t+1 (env CSLAM_PIPELINE)
-    int         pgemm_spare   = 16; // pipelined: workgroups the persistent P-GEMM grid leaves out (env CSLAM_PGEMM_SPARE)
-    int         gather_corr_wide = 1; // a pending batch panel (<= 64 columns) corrected for inside the gather kernel (env CSLAM_GATHER_WIDE)
     int         pgemm_wgs     = 0;  // > 0: cap on the persistent P-GEMM grid (cslam_ekf_set_pgemm_workgroups: co-running instances)
-    int         lookahead     = -1; // look-ahead windows (ekf_lookahead.hpp): -1 where they pay, env CSLAM_LOOKAHEAD=1 / 0 forces
     // (the owners live in the base, so they are destroyed after every buffer and event of Ekf<T>)
     Stream      stream_own, stream_b_own, stream_f_own;
     hipStream_t stream   = nullptr; // A: everything except the P-GEMM (= stream_own.get())
@@ -168,7 +163,6 @@ struct EkfBase
     virtual int set_deferred(int max_cols)                                                     = 0;
     virtual int do_flush()                                                                     = 0;
     virtual int resolve_predict()                                                              = 0;
-    virtual void set_fuse_predict(int on)                                                      = 0;
     virtual int sync_all()                                                                     = 0;
     virtual int la_drain()                                                                     = 0;
 };
@@ -176,16 +170,13 @@ struct EkfBase
 template <typename T>
 struct Ekf : EkfBase
 {
+    using EkfBase::EkfBase;
     DevBuf<T>   dX, dP;
     DevBuf<T>   dPv;       // pose stripe: columns 0..2 of P (always current; see p_get in ekf_kernels.hpp)
     DevBuf<int> dPoseDone; // ticket counters: [0] ekf_pose_step_kernel, [1] ekf_pose_downdate_kernel
     DevBuf<int> dSign;     // per region: wcap column signs (heading columns with S < 0), then [2*wcap + r] their count
     DevBuf<T>   dLm;       // landmark read outputs: 12 scalars per landmark of capacity (allocated by the first read)
-    int  hd_cols[2] = {0, 0}; // heading columns appended to each region since it became the pending store
-    // the pending W1 store is two regions of wcap columns: `wcur` collects pending columns, the other one may still be
-    // read by a P-GEMM in flight on stream B
-    int        wcur = 0;
-    unsigned   inflight_mask = 0; // regions an unfinished P-GEMM reads (cleared when stream A has waited for it)
+    PendingCols pend;    // the pending W1 store's bookkeeping (ekf_pending_store.hpp); its buffers are dW1 and dSign
     Event      ev_a2b, ev_pgemm;
     T*         last_slot = nullptr; // W1 of the last update
     // update workspace for batches of up to kcap rows of H: one set, replaced as a whole by ensure_k
@@ -215,9 +206,7 @@ struct Ekf : EkfBase
     };
     Workspace ws;
     int       kcap = 0;
-    DevBuf<T> dW1;      // pending W1 panels, two regions of ldp x wcap
-    int       wcap = 0; // columns per region of dW1
-    int       kp   = 0; // pending columns (downdates not applied to P yet)
+    DevBuf<T> dW1;      // pending W1 panels, two regions of ldp x pend.wcap
     int       defer_max = 0; // > 0: keep up to this many pending columns across calls (cslam_ekf_set_deferred)
     bool m_valid = false; // the last factor launch produced dM
     bool g_from_gt  = false; // the last factor launch wrote only G^T (ekf_factor_mfma_f32): debug transposes it
@@ -226,25 +215,10 @@ struct Ekf : EkfBase
     PinnedBuf<int> hFlags; // pinned mirror
     // heading scratch: w, cp2, rrow (ldp each) + 2 scalars
     DevBuf<T> dHead;
-    // observation staging: pinned host ring + one device buffer
-    int         mcap   = 0;
-    PinnedBuf<unsigned char> hStage;
-    DevBuf<unsigned char>    dStage;
-    Event                    stage_ev[kStagingSlots]; // created by the first call that takes the slot, recorded by every one
-    int         stage_next = 0;
+    StageRing<T> ring; // observation staging (ekf_staging.hpp)
     // tile list of the persistent symmetric downdate
     DevBuf<int> dTicket; // two tile-ticket counters used alternately by successive P-GEMM launches
-    // f32 P-GEMM on the bf16 matrix cores (ekf_pgemm_limbs.hpp): limb pairs per product (9 exact, 6, 0 = the f32 MFMA
-    // kernel; env CSLAM_PGEMM_LIMBS), from how many columns on (env CSLAM_LIMBS_KMIN), the limb store and its size.
-    // Off by default: correct and as accurate as the f32 MFMA kernel (tests), but measured no faster -- 120 - 132 us
-    // against 115 at k = 128, N = 5000 -- see DESIGN.md 8.
-    int        pgemm_limbs = 0;
-    // the f32 P-GEMM draws its tiles from one queue per XCD over a Morton-ordered list (env CSLAM_XCD_QUEUES=1).  Off by
-    // default: it cuts the HBM fetch traffic of a launch by a sixth (k = 64: 487 -> 435 MB, 1.04x the algorithmic bytes;
-    // k = 128: 584 -> 483 MB) but not its time (81.7 vs 80.9 us, 115.3 vs 114.6 us), and the loops built on it came out
-    // 0 - 4 % slower (profiles/r02_pmc_xcd_queues.txt)
-    int        xcd_queues  = 0;
-    int        limbs_kmin  = 65;
+    // the limb store of the bf16-limb P-GEMM (opt.pgemm_limbs) and its size
     DevBuf<uint4> dWb;
     size_t        wb_bytes = 0;
     DevBuf<int2>  dTilesM;  // the tile list in Morton order, cut into eight segments (one per XCD) ...
@@ -253,7 +227,6 @@ struct Ekf : EkfBase
     int        tilesM_built = 0;
     int        limb_parity = 0;
     unsigned   launch_parity = 0;
-    int        psym_nt = -1; // CSLAM_PSYM_NT=0|1: non-temporal P accesses in the P-GEMM (-1: by footprint)
     DevBuf<int2> dTiles;
     int   tiles_built = 0;
     int   n_sym_tiles = 0;
@@ -262,13 +235,7 @@ struct Ekf : EkfBase
     int sticky_host = 0; // flags raised by host-side decisions (FALLBACK/SKIPPED)
     int last_k      = 0;
     int kp_call_limit = 0; // pending columns a sequential update() may accumulate within the call
-    // profiling
-    int                     profiling = 0;
-    unsigned                prof_count = 0;
-    bool                    prof_sampled = false;
-    std::vector<Event>      ev_pool;
-    std::vector<int>        ev_stage; // stage id of interval [2i, 2i+1]
-    size_t                  ev_used = 0;
+    StageProfiler prof; // ekf_staging.hpp
 
     ~Ekf() override
     {
@@ -288,7 +255,9 @@ struct Ekf : EkfBase
         }
     }
 
-    T* wbase(int region) const { return dW1.get() + (size_t)region * wcap * ldp; }
+    T* wbase(int region) const { return dW1.get() + (size_t)region * pend.wcap * ldp; }
+    int* signs(int region) const { return dSign.get() + (size_t)region * pend.wcap; }
+    int* sign_count(int region) const { return dSign.get() + (size_t)2 * pend.wcap + region; }
 
     int use_device() { CSLAM_HIP_TRY(hipSetDevice(device)); return CSLAM_OK; }
 
@@ -299,19 +268,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        if (xcd_queues_req >= 0)
-        {
-            xcd_queues = xcd_queues_req;
-        }
-        if (pgemm_limbs_req >= 0)
-        {
-            pgemm_limbs = (pgemm_limbs_req == 6 || pgemm_limbs_req == 9) ? pgemm_limbs_req : 0;
-        }
-        if (limbs_kmin_req >= 0)
-        {
-            limbs_kmin = std::max(57, limbs_kmin_req); // (at least four chunks of 16: k8 >= 57 rounds to 64)
-        }
-        if (pipeline)
+        if (opt.pipeline)
         {
             // the chain (A) outranks the P-GEMM (B): its small kernels must get in while the P-GEMM fills the chip
             int lo = 0, hi = 0;
@@ -365,26 +322,6 @@ struct Ekf : EkfBase
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
         CSLAM_TRY(dTicket.alloc_zeroed(2, stream));
-        if (const char* sv = getenv("CSLAM_LA_K64"))
-        {
-            la_k64 = atoi(sv) ? 1 : 0;
-        }
-        if (const char* sv = getenv("CSLAM_LA_WG_SIGNAL"))
-        {
-            la_wg_signal = atoi(sv) ? 1 : 0;
-        }
-        if (const char* sv = getenv("CSLAM_LA_HOLD_WIDE"))
-        {
-            la_hold_wide = atoi(sv) ? 1 : 0;
-        }
-        if (const char* sv = getenv("CSLAM_LA_MIRROR"))
-        {
-            la_mirror = atoi(sv) ? 1 : 0;
-        }
-        if (const char* sv = getenv("CSLAM_PSYM_NT"))
-        {
-            psym_nt = atoi(sv) ? 1 : 0;
-        }
         rc = ensure_k(64);
         if (rc)
         {
@@ -414,7 +351,7 @@ struct Ekf : EkfBase
         int newk = round_up(std::max(k, 2 * kcap), 8);
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         Workspace nw;
-        CSLAM_TRY(nw.alloc(ldp, newk, wcap, stream));
+        CSLAM_TRY(nw.alloc(ldp, newk, pend.wcap, stream));
         ws   = std::move(nw);
         kcap = newk;
         return CSLAM_OK;
@@ -424,7 +361,7 @@ struct Ekf : EkfBase
     int ensure_w(int cols)
     {
         cols = round_up(cols, 8);
-        if (cols <= wcap)
+        if (cols <= pend.wcap)
         {
             return CSLAM_OK;
         }
@@ -433,7 +370,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        int neww = round_up(std::max(cols, 2 * wcap), 8);
+        int neww = round_up(std::max(cols, 2 * pend.wcap), 8);
         DevBuf<T>   w1, y;
         DevBuf<int> sign;
         if ((rc = w1.alloc_zeroed((size_t)2 * ldp * neww, stream)) || (rc = y.alloc((size_t)std::max(kcap, 8) * neww)) ||
@@ -444,10 +381,7 @@ struct Ekf : EkfBase
         dW1   = std::move(w1);
         ws.dY = std::move(y);
         dSign = std::move(sign);
-        hd_cols[0] = hd_cols[1] = 0;
-        wcap      = neww;
-        wcur      = 0;
-        la_mirror_cols = 0;
+        pend.regrown(neww);
         last_slot = nullptr;
         return CSLAM_OK;
     }
@@ -468,7 +402,7 @@ struct Ekf : EkfBase
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream_f));
         }
-        inflight_mask = 0;
+        pend.waited();
         return CSLAM_OK;
     }
 
@@ -476,18 +410,18 @@ struct Ekf : EkfBase
     // writes Ps, or writes a W1 region such a P-GEMM reads
     int wait_pgemm()
     {
-        if (inflight_mask != 0 && stream_b != stream)
+        if (pend.in_flight() && stream_b != stream)
         {
             CSLAM_HIP_TRY(hipStreamWaitEvent(stream, ev_pgemm.get(), 0));
         }
-        inflight_mask = 0;
+        pend.waited();
         return CSLAM_OK;
     }
 
     // before stream A writes into W1 region r
     int own_region(int r)
     {
-        return (inflight_mask & (1u << r)) ? wait_pgemm() : CSLAM_OK;
+        return pend.in_flight(r) ? wait_pgemm() : CSLAM_OK;
     }
 
     // launch the P-GEMM of every pending column (slam.h:260 is linear in the panels: ONE pass with k = kp) on stream B,
@@ -499,7 +433,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        if (kp == 0)
+        if (pend.kp == 0)
         {
             return CSLAM_OK;
         }
@@ -507,53 +441,47 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        T*        W   = wbase(wcur);
-        const int kp8 = round_up(kp, 8);
+        T*        W   = wbase(pend.wcur);
+        const int kp8 = round_up(pend.kp, 8);
         // (the shipped f32 P-GEMM bounds its W1 buffer resource at kp columns: the hardware returns zeros beyond, no
         // padding needed; the other kernels read whole blocks of 8 columns)
-        if (kp8 > kp && !psym4_takes(kp8))
+        if (kp8 > pend.kp && !psym4_takes(kp8))
         {
-            CSLAM_HIP_TRY(hipMemset2DAsync(W + (size_t)kp * ldp, (size_t)ldp * sizeof(T), 0,
-                                           (size_t)round_up(n, kTile) * sizeof(T), (size_t)(kp8 - kp), stream));
+            CSLAM_HIP_TRY(hipMemset2DAsync(W + (size_t)pend.kp * ldp, (size_t)ldp * sizeof(T), 0,
+                                           (size_t)round_up(n, kTile) * sizeof(T), (size_t)(kp8 - pend.kp), stream));
         }
         if (stream_b != stream)
         {
             CSLAM_HIP_TRY(hipEventRecord(ev_a2b.get(), stream));
             CSLAM_HIP_TRY(hipStreamWaitEvent(stream_b, ev_a2b.get(), 0));
         }
-        if (hd_cols[wcur] > 0) // exceptional heading columns (S < 0) enter with the opposite sign: exits at once otherwise
+        if (pend.hd_cols[pend.wcur] > 0) // exceptional heading columns (S < 0) enter with the opposite sign: exits at once otherwise
         {
-            if ((rc = launch_negcol_fix(W, kp, stream_b)))
+            if ((rc = launch_negcol_fix(W, pend.kp, stream_b)))
             {
                 return rc;
             }
         }
-        if ((rc = prof_begin(CSLAM_STAGE_DOWNDATE, stream_b)) || (rc = launch_downdate(W, kp, stream_b)) ||
-            (rc = prof_end(CSLAM_STAGE_DOWNDATE, stream_b)))
+        if ((rc = prof.begin(CSLAM_STAGE_DOWNDATE, stream_b)) || (rc = launch_downdate(W, pend.kp, stream_b)) ||
+            (rc = prof.end(CSLAM_STAGE_DOWNDATE, stream_b)))
         {
             return rc;
         }
         if (stream_b != stream)
         {
             CSLAM_HIP_TRY(hipEventRecord(ev_pgemm.get(), stream_b));
-            inflight_mask |= 1u << wcur;
+            pend.pgemm_on_second_stream();
         }
-        wcur ^= 1;
-        kp = 0;
-        la_mirror_cols = 0; // (the mirror described the columns that have just been applied)
+        const bool clear_signs = pend.applied(); // its column signs belong to columns that have been applied
         // the other region becomes the pending store: a still older P-GEMM may be reading it
-        if ((rc = own_region(wcur)))
+        if ((rc = own_region(pend.wcur)))
         {
             return rc;
         }
-        if (hd_cols[wcur] > 0) // its column signs belong to columns that have been applied
+        if (clear_signs && stream_b != stream) // (single stream: ekf_negcol_fix_kernel clears them itself when it had work)
         {
-            if (stream_b != stream) // (single stream: ekf_negcol_fix_kernel clears them itself when it had work)
-            {
-                CSLAM_HIP_TRY(hipMemsetAsync(dSign.get() + (size_t)wcur * wcap, 0, (size_t)wcap * sizeof(int), stream));
-                CSLAM_HIP_TRY(hipMemsetAsync(dSign.get() + (size_t)2 * wcap + wcur, 0, sizeof(int), stream));
-            }
-            hd_cols[wcur] = 0;
+            CSLAM_HIP_TRY(hipMemsetAsync(signs(pend.wcur), 0, (size_t)pend.wcap * sizeof(int), stream));
+            CSLAM_HIP_TRY(hipMemsetAsync(sign_count(pend.wcur), 0, sizeof(int), stream));
         }
         return CSLAM_OK;
     }
@@ -618,26 +546,26 @@ struct Ekf : EkfBase
     // k8 columns go through ekf_downdate_psym4_f32 (see launch_downdate)
     bool psym4_takes(int k8) const
     {
-        return sizeof(T) == 4 && (k8 <= 128 || limbs_take(k8)) && lower && ldp < 32768;
+        return sizeof(T) == 4 && (k8 <= 128 || limbs_take(k8)) && opt.lower && ldp < 32768;
     }
     // ... or through ekf_downdate_psym5_bf16 (which pads its own limb store)
     bool limbs_take(int k8) const
     {
-        return sizeof(T) == 4 && pgemm_limbs > 0 && k8 >= limbs_kmin && k8 <= 256 && lower && ldp < 32768;
+        return sizeof(T) == 4 && opt.pgemm_limbs > 0 && k8 >= opt.limbs_kmin && k8 <= 256 && opt.lower && ldp < 32768;
     }
 
     int launch_negcol_fix(T* W, int kcols, hipStream_t st)
     {
         const int tiles = round_up(n, kTile) / kTile;
         int       rc    = CSLAM_OK;
-        if (lower && (rc = ensure_tile_list(tiles)))
+        if (opt.lower && (rc = ensure_tile_list(tiles)))
         {
             return rc;
         }
-        const int nt = lower ? n_sym_tiles : tiles * tiles;
+        const int nt = opt.lower ? n_sym_tiles : tiles * tiles;
         hipLaunchKernelGGL(ekf_negcol_fix_kernel<T>, dim3(std::min(nt, 2 * num_cus)), dim3(256), 0, st, dP.get(), ldp,
-                           n, W, ldp, kcols, dSign.get() + (size_t)wcur * wcap, dSign.get() + (size_t)2 * wcap + wcur,
-                           lower ? dTiles.get() : (const int2*)nullptr, nt, tiles, dPoseDone.get() + 2,
+                           n, W, ldp, kcols, signs(pend.wcur), sign_count(pend.wcur),
+                           opt.lower ? dTiles.get() : (const int2*)nullptr, nt, tiles, dPoseDone.get() + 2,
                            (stream_b == stream) ? 1 : 0);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
@@ -650,23 +578,13 @@ struct Ekf : EkfBase
         return rc ? rc : wait_pgemm();
     }
 
-    size_t slot_bytes(int mc) const { return (size_t)mc * (2 * sizeof(T) + sizeof(int)); }
-
-    // the next slot of the ring (ensure_m(m) has been called)
-    int stage_take_slot()
-    {
-        const int slot = stage_next;
-        stage_next     = (stage_next + 1) % kStagingSlots;
-        return slot;
-    }
-
+    // room in the staging ring for m observations per slot
     int ensure_m(int m)
     {
-        if (m <= mcap)
+        if (m <= ring.mcap)
         {
             return CSLAM_OK;
         }
-        int newm = std::max(m, 2 * mcap);
         if (int rc = la_drain()) // (queued updates read the ring that is about to move)
         {
             return rc;
@@ -676,59 +594,14 @@ struct Ekf : EkfBase
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream_f));
         }
-        // (a device slot per host slot: queued look-ahead updates read their inputs up to two calls later; a slot comes round
-        // again kStagingSlots calls later, stream-ordered behind every kernel that read it)
-        PinnedBuf<unsigned char> hs;
-        DevBuf<unsigned char>    ds;
-        int                      rc = hs.alloc(slot_bytes(newm) * kStagingSlots);
-        if (rc || (rc = ds.alloc(slot_bytes(newm) * kStagingSlots)))
-        {
-            return rc;
-        }
-        hStage = std::move(hs);
-        dStage = std::move(ds);
-        mcap = newm;
-        return CSLAM_OK;
+        return ring.grow(m);
     }
 
-    // copies (Z, idf) of one call into the next slot of the ring on the main stream; returns device pointers.  Host
-    // inputs go through the slot's pinned buffer (H2D copy); device inputs (on_device) are copied by one small kernel.
+    // copies (Z, idf) of one call into the next slot of the ring on the main stream; returns device pointers
     int stage_obs(const void* Z, const int* idf, int m, bool on_device, const T** dZ, const int** dIdf)
     {
         int rc = ensure_m(m);
-        if (rc)
-        {
-            return rc;
-        }
-        int slot = stage_take_slot();
-        if (stage_ev[slot])
-        {
-            CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[slot].get()));
-        }
-        else if ((rc = stage_ev[slot].create(hipEventDisableTiming)))
-        {
-            return rc;
-        }
-        size_t         zb = (size_t)m * 2 * sizeof(T);
-        unsigned char* ds = dStage.get() + slot_bytes(mcap) * slot;
-        if (on_device)
-        {
-            hipLaunchKernelGGL(ekf_stage_obs_kernel<T>, dim3((3 * m + 255) / 256), dim3(256), 0, stream,
-                               static_cast<const T*>(Z), idf, m, reinterpret_cast<T*>(ds), reinterpret_cast<int*>(ds + zb));
-            CSLAM_HIP_TRY(hipGetLastError());
-            stage_launches++;
-        }
-        else
-        {
-            unsigned char* hs = hStage.get() + slot_bytes(mcap) * slot;
-            memcpy(hs, Z, zb);
-            memcpy(hs + zb, idf, (size_t)m * sizeof(int));
-            CSLAM_HIP_TRY(hipMemcpyAsync(ds, hs, zb + (size_t)m * sizeof(int), hipMemcpyHostToDevice, stream));
-        }
-        CSLAM_HIP_TRY(hipEventRecord(stage_ev[slot].get(), stream));
-        *dZ   = reinterpret_cast<const T*>(ds);
-        *dIdf = reinterpret_cast<const int*>(ds + zb);
-        return CSLAM_OK;
+        return rc ? rc : ring.stage(Z, idf, m, on_device, stream, stage_launches, dZ, dIdf);
     }
 
     // ---------------------------------------------------------------- state transfer
@@ -750,14 +623,11 @@ struct Ekf : EkfBase
         CSLAM_HIP_TRY(hipMemcpyAsync(dPv.get(), dP.get(), (size_t)3 * ldp * sizeof(T), hipMemcpyDeviceToDevice,
                                      stream));
         // panels: rows beyond the new n must read as zero (the tuned gain kernel relies on it)
-        kp        = 0; // a new state discards updates that were never applied
-        wcur      = 0;
-        la_mirror_cols = 0;
+        pend.discarded(); // a new state discards updates that were never applied
         last_slot = nullptr;
-        hd_cols[0] = hd_cols[1] = 0;
-        CSLAM_HIP_TRY(hipMemsetAsync(dSign.get(), 0, ((size_t)2 * wcap + 2) * sizeof(int), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(dSign.get(), 0, ((size_t)2 * pend.wcap + 2) * sizeof(int), stream));
         CSLAM_HIP_TRY(hipMemsetAsync(ws.dPHT.get(), 0, (size_t)ldp * kcap * sizeof(T), stream));
-        CSLAM_HIP_TRY(hipMemsetAsync(dW1.get(), 0, (size_t)2 * ldp * wcap * sizeof(T), stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(dW1.get(), 0, (size_t)2 * ldp * pend.wcap * sizeof(T), stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         n = nn;
         return CSLAM_OK;
@@ -784,7 +654,7 @@ struct Ekf : EkfBase
         }
         if (P)
         {
-            if (lower)
+            if (opt.lower)
             {
                 const int g = (n + 31) / 32;
                 hipLaunchKernelGGL(ekf_mirror_upper_kernel<T>, dim3(g, g), dim3(256), 0, stream, dP.get(), ldp, n);
@@ -827,9 +697,9 @@ struct Ekf : EkfBase
         }
         const size_t c  = (size_t)count;
         T*           ox = dLm.get(), *opll = dLm.get() + 2 * c, *opvl = dLm.get() + 6 * c;
-        const int*   sg = (kp > 0 && hd_cols[wcur] > 0) ? dSign.get() + (size_t)wcur * wcap : (const int*)nullptr;
+        const int*   sg = (pend.kp > 0 && pend.hd_cols[pend.wcur] > 0) ? signs(pend.wcur) : (const int*)nullptr;
         hipLaunchKernelGGL(ekf_landmark_read_kernel<T>, dim3((count + 255) / 256), dim3(256), 0, stream, dX.get(),
-                           dPv.get(), dP.get(), ldp, lower, (const T*)wbase(wcur), ldp, kp, sg, first, count,
+                           dPv.get(), dP.get(), ldp, opt.lower, (const T*)wbase(pend.wcur), ldp, pend.kp, sg, first, count,
                            x ? ox : (T*)nullptr, pll ? opll : (T*)nullptr, pvl ? opvl : (T*)nullptr);
         CSLAM_HIP_TRY(hipGetLastError());
         if (x)
@@ -879,62 +749,7 @@ struct Ekf : EkfBase
         return CSLAM_OK;
     }
 
-    // ---------------------------------------------------------------- profiling
-    // mode 1: every stage; 2: every P-GEMM launch; 3: one P-GEMM launch in sixteen (an event pair costs about 11 us of
-    // stream time around the kernel it brackets -- rocprofv3 trace: 5.9 us before, 5.6 us after -- so the timed region
-    // of the bench samples instead of bracketing every launch)
-    bool prof_skip(int stage, bool begin)
-    {
-        if (!profiling)
-        {
-            return true;
-        }
-        if (profiling >= 2 && stage != CSLAM_STAGE_DOWNDATE)
-        {
-            return true;
-        }
-        if (profiling == 3 || profiling == 4)
-        {
-            if (begin)
-            {
-                prof_sampled = (prof_count++ % (profiling == 3 ? 16u : 4u)) == 0;
-            }
-            return !prof_sampled;
-        }
-        return false;
-    }
-    int prof_begin(int stage, hipStream_t st = nullptr)
-    {
-        st = st ? st : stream;
-        if (prof_skip(stage, true))
-        {
-            return CSLAM_OK;
-        }
-        if (ev_used + 2 > ev_pool.size())
-        {
-            for (int i = 0; i < 2; i++)
-            {
-                Event e;
-                CSLAM_TRY(e.create(hipEventDefault));
-                ev_pool.push_back(std::move(e));
-            }
-        }
-        ev_stage.resize(ev_pool.size() / 2);
-        ev_stage[ev_used / 2] = stage;
-        CSLAM_HIP_TRY(hipEventRecord(ev_pool[ev_used].get(), st));
-        return CSLAM_OK;
-    }
-    int prof_end(int stage, hipStream_t st = nullptr)
-    {
-        st = st ? st : stream;
-        if (prof_skip(stage, false))
-        {
-            return CSLAM_OK;
-        }
-        CSLAM_HIP_TRY(hipEventRecord(ev_pool[ev_used + 1].get(), st));
-        ev_used += 2;
-        return CSLAM_OK;
-    }
+    // ---------------------------------------------------------------- profiling (StageProfiler, ekf_staging.hpp)
     int set_profiling(int on) override
     {
         if (int rc = la_drain())
@@ -945,9 +760,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        profiling  = on;
-        ev_used    = 0;
-        prof_count = 0;
+        prof.set_mode(on);
         return CSLAM_OK;
     }
     int get_stage_times(double* ms, int* launches) override
@@ -964,20 +777,7 @@ struct Ekf : EkfBase
         {
             return rc;
         }
-        for (int s = 0; s < CSLAM_N_STAGES; s++)
-        {
-            ms[s]       = 0.0;
-            launches[s] = 0;
-        }
-        for (size_t i = 0; i + 1 < ev_used; i += 2)
-        {
-            float t = 0.f;
-            CSLAM_HIP_TRY(hipEventElapsedTime(&t, ev_pool[i].get(), ev_pool[i + 1].get()));
-            int s = ev_stage[i / 2];
-            ms[s] += (double)t;
-            launches[s] += 1;
-        }
-        return CSLAM_OK;
+        return prof.times(ms, launches);
     }
 
     // ---------------------------------------------------------------- data association (EKF.cpp:131-144, 235-326)
@@ -1028,7 +828,7 @@ struct Ekf : EkfBase
         if (nf > 0)
         {
             hipLaunchKernelGGL(ekf_assoc_feature_kernel<T>, dim3((nf + 255) / 256), dim3(256), 0, stream, dX.get(),
-                               dP.get(), dPv.get(), ldp, n, R[0], R[1], R[2], R[3], lower, dAssoc.get());
+                               dP.get(), dPv.get(), ldp, n, R[0], R[1], R[2], R[3], opt.lower, dAssoc.get());
             CSLAM_HIP_TRY(hipGetLastError());
         }
         hipLaunchKernelGGL(ekf_assoc_scan_kernel<T>, dim3(m), dim3(64), 0, stream, dAssoc.get(), nf, dZ, m, (T)g1,
@@ -1056,7 +856,6 @@ struct Ekf : EkfBase
     PoseSeq<T>     seq{};
     DevBuf<T>      dPred; // 16 scalars: factor kernel -> gain kernel (see FactorArgs::pred_out)
     bool           fuse_now = false; // the batch in flight consumes pp
-    int            fuse_predict = 1;
 
     int predict(double v, double swa, const void* Qv, double wb, double dt) override
     {
@@ -1076,14 +875,12 @@ struct Ekf : EkfBase
             w = (quirks & CSLAM_Q_PREDICT_NM4) ? (n - 4) : (n - 3);
         }
         pp = PredictArgs<T>{1, (T)v, (T)swa, Q[0], Q[1], Q[2], Q[3], (T)wb, (T)dt, std::max(w, 0)};
-        if (!fuse_predict)
+        if (!opt.fuse_predict)
         {
             return resolve_predict();
         }
         return CSLAM_OK;
     }
-
-    void set_fuse_predict(int on) override { fuse_predict = on; }
 
     // append one control step (predict and / or heading) to the pose queue
     int queue_step(const PredictArgs<T>& p, const HeadingArgs<T>& hd)
@@ -1101,20 +898,19 @@ struct Ekf : EkfBase
         if (hd.valid && n > 3)
         {
             // the rank-1 downdate -p p^T / S of the map block is one more pending column
-            if (kp + 1 > wcap)
+            if (pend.kp + 1 > pend.wcap)
             {
                 if ((rc = launch_pose_queue()) || (rc = flush()))
                 {
                     return rc;
                 }
             }
-            if ((rc = own_region(wcur)))
+            if ((rc = own_region(pend.wcur)))
             {
                 return rc;
             }
-            col = kp;
-            kp += 1;
-            hd_cols[wcur] += 1;
+            col = pend.kp;
+            pend.appended(1, true);
         }
         const int s = seq.count++;
         seq.pp[s]   = p;
@@ -1140,8 +936,8 @@ struct Ekf : EkfBase
         }
         const int n_pad = round_up(n, kTile);
         hipLaunchKernelGGL(ekf_pose_step_kernel<T>, dim3((n_pad + 255) / 256), dim3(256), 0, stream, dX.get(),
-                           dPv.get(), ldp, n, n_pad, seq, wbase(wcur), ldp, dHead.get(),
-                           dSign.get() + (size_t)wcur * wcap, dSign.get() + (size_t)2 * wcap + wcur, dPoseDone.get());
+                           dPv.get(), ldp, n, n_pad, seq, wbase(pend.wcur), ldp, dHead.get(),
+                           signs(pend.wcur), sign_count(pend.wcur), dPoseDone.get());
         CSLAM_HIP_TRY(hipGetLastError());
         seq.count = 0;
         return CSLAM_OK;
@@ -1329,10 +1125,10 @@ struct Ekf : EkfBase
         }
         // a few pending columns (heading observations) are corrected for inside the gather kernel: the fast path stays
         // ... and so is one deferred batch panel (up to kGatherCorrMax columns), by the kernel's wider form
-        const bool small_corr = kp > 0 && kp <= (gather_corr_wide ? kGatherCorrMax : kGatherCorr) && !pipeline;
-        const bool wide_corr  = small_corr && kp > kGatherCorr;
+        const bool small_corr = pend.kp > 0 && pend.kp <= (opt.gather_corr_wide ? kGatherCorrMax : kGatherCorr) && !opt.pipeline;
+        const bool wide_corr  = small_corr && pend.kp > kGatherCorr;
         // a pending predict() rides along when this batch takes the (non-pipelined) fast path
-        fuse_now = pp.valid && (sizeof(T) == 4 || fuse_f64) && !pipeline && !keep_pending && k > 16 && k <= 64;
+        fuse_now = pp.valid && (sizeof(T) == 4 || opt.fuse_f64) && !opt.pipeline && !keep_pending && k > 16 && k <= 64;
         if ((rc = fuse_now ? launch_pose_queue() : resolve_predict())) // (queued control steps come first either way)
         {
             return rc;
@@ -1350,12 +1146,12 @@ struct Ekf : EkfBase
         }
         // Pipelined: the pending columns' P-GEMM starts right behind this update's gather and runs under its chain.
         // It is held back while an explicit deferral window (cslam_ekf_set_deferred) still has room for this panel.
-        const bool overlap = pipeline && !keep_pending && kp > 0 && (defer_max == 0 || kp + k > defer_max);
+        const bool overlap = opt.pipeline && !keep_pending && pend.kp > 0 && (defer_max == 0 || pend.kp + k > defer_max);
         // pending columns stay pending through this update while they fit the window: the explicit deferral window, the
         // sequential call's own columns, else the store (e.g. heading columns in immediate mode: applied together with
         // this update's panel by the flush below)
-        const int window = std::min(wcap, defer_max > 0 ? defer_max : (kp_call_limit > 0 ? kp_call_limit : wcap));
-        if (!overlap && kp > 0 && (kp + k > window || kp + k8w > wcap))
+        const int window = std::min(pend.wcap, defer_max > 0 ? defer_max : (kp_call_limit > 0 ? kp_call_limit : pend.wcap));
+        if (!overlap && pend.kp > 0 && (pend.kp + k > window || pend.kp + k8w > pend.wcap))
         {
             if ((rc = flush())) // no room to keep them pending: apply them first
             {
@@ -1368,42 +1164,42 @@ struct Ekf : EkfBase
         }
         last_k = k;
         dbgS = dbgGt = dbgV = nullptr; // (debug_last_update reads the handle's own workspace again)
-        if ((rc = prof_begin(CSLAM_STAGE_GATHER)))
+        if ((rc = prof.begin(CSLAM_STAGE_GATHER, stream)))
         {
             return rc;
         }
         const dim3 ggrid((n + 255) / 256, (m + kGatherObs - 1) / kGatherObs);
         // the compact H-rows block for the MFMA factor kernel (f32, 16 < k <= 64, no pending panels to correct)
-        sub_valid = (k > 16 && k <= 64 && (kp == 0 || small_corr) && ws.dSub.get() != nullptr);
+        sub_valid = (k > 16 && k <= 64 && (pend.kp == 0 || small_corr) && ws.dSub.get() != nullptr);
         PredictArgs<T> pnone{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
         {
             T*             sub  = sub_valid ? ws.dSub.get() : nullptr;
             PredictArgs<T> pa   = fuse_now ? pp : pnone;
             T*             pred = fuse_now ? dPred.get() : (T*)nullptr;
-            const T*       Wg   = (kp > 0 && !pipeline) ? (const T*)wbase(wcur) : (const T*)nullptr;
-            const int      kg   = pipeline ? 0 : kp;
+            const T*       Wg   = (pend.kp > 0 && !opt.pipeline) ? (const T*)wbase(pend.wcur) : (const T*)nullptr;
+            const int      kg   = opt.pipeline ? 0 : pend.kp;
             const int*     sg =
-                (kp > 0 && !pipeline && hd_cols[wcur] > 0) ? dSign.get() + (size_t)wcur * wcap : (const int*)nullptr;
-            T* yout = (kp > 0 && !small_corr && !pipeline) ? ws.dY.get() : (T*)nullptr;
+                (pend.kp > 0 && !opt.pipeline && pend.hd_cols[pend.wcur] > 0) ? signs(pend.wcur) : (const int*)nullptr;
+            T* yout = (pend.kp > 0 && !small_corr && !opt.pipeline) ? ws.dY.get() : (T*)nullptr;
             if (wide_corr)
             {
                 const dim3 wgrid((n + 255) / 256, (m + kGatherObsWide - 1) / kGatherObsWide);
                 hipLaunchKernelGGL((ekf_gather_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream,
-                                   dX.get(), dP.get(), dPv.get(), ldp, n, dZ, dIdf, m, ws.dPHT.get(), ldp, lower, sub,
+                                   dX.get(), dP.get(), dPv.get(), ldp, n, dZ, dIdf, m, ws.dPHT.get(), ldp, opt.lower, sub,
                                    pa, pred, Wg, ldp, kg, sg, dFlags.get(), yout);
             }
             else
             {
                 hipLaunchKernelGGL(ekf_gather_kernel<T>, ggrid, dim3(256), 0, stream, dX.get(), dP.get(), dPv.get(),
-                                   ldp, n, dZ, dIdf, m, ws.dPHT.get(), ldp, lower, sub, pa, pred, Wg, ldp, kg, sg,
+                                   ldp, n, dZ, dIdf, m, ws.dPHT.get(), ldp, opt.lower, sub, pa, pred, Wg, ldp, kg, sg,
                                    dFlags.get(), yout);
             }
         }
         CSLAM_HIP_TRY(hipGetLastError());
         // the panels this update's P*H^T must be corrected with, and where its own W1 goes
-        const T*  Wc        = wbase(wcur);
-        const int kc        = kp;
-        const int rc_region = wcur;
+        const T*  Wc        = wbase(pend.wcur);
+        const int kc        = pend.kp;
+        const int rc_region = pend.wcur;
         if (overlap)
         {
             if ((rc = flush())) // P-GEMM of the pending columns on stream B, behind the gather; store -> other region
@@ -1411,18 +1207,18 @@ struct Ekf : EkfBase
                 return rc;
             }
         }
-        T* slot = wbase(wcur) + (size_t)kp * ldp;
-        if ((rc = own_region(wcur)))
+        T* slot = wbase(pend.wcur) + (size_t)pend.kp * ldp;
+        if ((rc = own_region(pend.wcur)))
         {
             return rc;
         }
         if (kc > 0 && !small_corr) // PHT -= Wp * (H*Wp)^T : the pending panels' share of P*H^T (their pose rows are zero)
         {
-            if (pipeline) // (single stream: the gather kernel has published Y = H*Wp already)
+            if (opt.pipeline) // (single stream: the gather kernel has published Y = H*Wp already)
             {
                 hipLaunchKernelGGL(ekf_pending_y_kernel<T>, dim3(m, (kc + 255) / 256), dim3(256), 0, stream, dX.get(), n, dZ, dIdf,
                                    m, Wc, ldp, kc, ws.dY.get(),
-                                   hd_cols[rc_region] > 0 ? dSign.get() + (size_t)rc_region * wcap : (const int*)nullptr);
+                                   pend.hd_cols[rc_region] > 0 ? signs(rc_region) : (const int*)nullptr);
                 CSLAM_HIP_TRY(hipGetLastError());
             }
             if (!launch_corr_fast(k, Wc, kc))
@@ -1432,9 +1228,9 @@ struct Ekf : EkfBase
             }
             CSLAM_HIP_TRY(hipGetLastError());
         }
-        if ((rc = prof_end(CSLAM_STAGE_GATHER)) || (rc = prof_begin(CSLAM_STAGE_FACTOR)) ||
-            (rc = launch_factor(dZ, dIdf, m, R)) || (rc = prof_end(CSLAM_STAGE_FACTOR)) ||
-            (rc = prof_begin(CSLAM_STAGE_GAIN)) || (rc = launch_gain(k, slot)) || (rc = prof_end(CSLAM_STAGE_GAIN)))
+        if ((rc = prof.end(CSLAM_STAGE_GATHER, stream)) || (rc = prof.begin(CSLAM_STAGE_FACTOR, stream)) ||
+            (rc = launch_factor(dZ, dIdf, m, R)) || (rc = prof.end(CSLAM_STAGE_FACTOR, stream)) ||
+            (rc = prof.begin(CSLAM_STAGE_GAIN, stream)) || (rc = launch_gain(k, slot)) || (rc = prof.end(CSLAM_STAGE_GAIN, stream)))
         {
             return rc;
         }
@@ -1444,8 +1240,8 @@ struct Ekf : EkfBase
             fuse_now = false;
         }
         last_slot = slot;
-        kp += k;
-        const bool deferring = keep_pending || pipeline || defer_max > 0;
+        pend.appended(k);
+        const bool deferring = keep_pending || opt.pipeline || defer_max > 0;
         if (!deferring && (rc = flush()))
         {
             return rc;
@@ -1461,7 +1257,7 @@ struct Ekf : EkfBase
         }
         // explicit deferral without pipelining: once the window is full, apply it now rather than at the start of
         // the next update
-        if (!pipeline && !keep_pending && defer_max > 0 && kp >= defer_max && (rc = flush()))
+        if (!opt.pipeline && !keep_pending && defer_max > 0 && pend.kp >= defer_max && (rc = flush()))
         {
             return rc;
         }
@@ -1506,7 +1302,7 @@ struct Ekf : EkfBase
         }
         CSLAM_HIP_TRY(hipMemcpyAsync(ws.dU.get(), u.data(), u.size() * sizeof(T), hipMemcpyHostToDevice, stream));
         int rc;
-        if ((rc = own_region(wcur)))
+        if ((rc = own_region(pend.wcur)))
         {
             return rc;
         }
@@ -1580,7 +1376,6 @@ struct Ekf : EkfBase
         float*     wt = nullptr; // != nullptr: the k = 64 kernel that also writes the row-major mirror
     };
     LaHeld      la_held;
-    int         la_hold_wide = 1; // CSLAM_LA_HOLD_WIDE=0: every window launches its own wide kernel at once (A/B)
     LaUpd       la_q[2];
     int         la_n = 0;
     LaSet       la;
@@ -1594,21 +1389,12 @@ struct Ekf : EkfBase
     // != 0: the next P-GEMM launch (ekf_downdate_psym4_f32) adds this to la_done[0] -- the chain's go-ahead, in place of a
     // release fence + atomic in every workgroup of the blocks kernel (8.8 -> 6.6 us per window); see la_launch_window
     unsigned    la_sig_add = 0;
-    int         la_k64 = 1;       // CSLAM_LA_K64=0: the general wide kernel for m = 32 too (A/B)
-    int         la_wg_signal = 0; // CSLAM_LA_WG_SIGNAL=1: always the blocks kernel's own release (A/B: the first form)
     // The row-major mirror of the pending panels (f32; written by ekf_la_wide_f32_k64m, read by the NEXT window's
     // ekf_la_blocks_mirror_kernel, which precedes the next wide kernel on the main stream: one buffer suffices).
-    // la_mirror_cols: how many leading columns of the current pending store it covers, for a state of la_mirror_n rows.
-    // A window takes the mirror path only when that is all kp of them: whatever else adds columns to the store (the
-    // classic path, heading columns, sequential updates, the general wide kernel, CSLAM_LA_FUSED=0) leaves kp larger, and
-    // whatever applies or discards the store (flush, set_state, a store that grows) sets the count to 0.
+    // What it covers is part of the pending store's bookkeeping (PendingCols::mirror_covers): a window takes the mirror
+    // path only when that is all kp pending columns.
     DevBuf<float> la_WT;
     int           la_wt_rows     = 0;
-    int           la_mirror_cols = 0;
-    int           la_mirror_n    = 0;
-    int           la_mirror      = 1; // CSLAM_LA_MIRROR=0: rows + blocks kernels for every window, no mirror stores (A/B)
-
-    int         la_fused   = 1; // env CSLAM_LA_FUSED=0: gather + gain per update instead of the one wide launch (A/B)
     // what debug_last_update reads (the handle's workspace, or the factor slot of a window's last update)
     const T *dbgS = nullptr, *dbgGt = nullptr, *dbgV = nullptr;
 
@@ -1651,13 +1437,9 @@ struct Ekf : EkfBase
                 (rc = nl.Dbb.alloc((size_t)KM * KM)) || (rc = nl.Y.alloc((size_t)KM * KM)) ||
                 (rc = nl.model.alloc(2)) || (rc = nl.idf_keep.alloc(kLaMaxObs)) ||
                 (rc = nl.z_keep.alloc(2 * kLaMaxObs)) ||
-                (getenv("CSLAM_LA_STAMPS") && (rc = nl.stamps.alloc_zeroed_blocking(32))))
+                (opt.la_stamps && (rc = nl.stamps.alloc_zeroed_blocking(32))))
             {
                 return rc;
-            }
-            if (const char* fv = getenv("CSLAM_LA_FUSED"))
-            {
-                la_fused = atoi(fv) ? 1 : 0;
             }
             stream_f_own = std::move(sf);
             stream_f     = stream_f_own.get();
@@ -1677,7 +1459,7 @@ struct Ekf : EkfBase
             la_WR   = std::move(wr);
             la_kpad = kpad;
         }
-        if (la_mirror && std::is_same<T, float>::value && round_up(n, kTile) > la_wt_rows)
+        if (opt.la_mirror && std::is_same<T, float>::value && round_up(n, kTile) > la_wt_rows)
         {
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream_f));
@@ -1686,7 +1468,7 @@ struct Ekf : EkfBase
             CSLAM_TRY(wt.alloc((size_t)rows * 128)); // [rows][128 columns]
             la_WT          = std::move(wt);
             la_wt_rows     = rows;
-            la_mirror_cols = 0;
+            pend.mirror_void();
         }
         return CSLAM_OK;
     }
@@ -1698,10 +1480,10 @@ struct Ekf : EkfBase
         // lookahead: 1 on, 0 off, -1 (default) where it pays: f32 and a P-GEMM long enough to hide the factor chain
         // (~70 us) underneath it -- about N >= 3500 landmarks; a short P-GEMM leaves the chain on the critical path
         // (measured: f64 N = 1000 12.9 k steps/s with windows against 15.8 k without)
-        const bool on = lookahead > 0 || (lookahead < 0 && sizeof(T) == 4 && n >= 7000 && g_engines.load() == 1);
-        return on && !sync_mode && !pipeline && profiling != 1 && k > 16 && k <= 2 * kLaMaxObs && gather_corr_wide &&
-               fuse_predict && (sizeof(T) == 4 || fuse_f64) && defer_max >= k + (la_n ? 2 * la_q[0].m : k) &&
-               wcap >= k + (la_n ? 2 * la_q[0].m : k) && seq.count == 0 && hd_cols[0] == 0 && hd_cols[1] == 0 && n > 3 &&
+        const bool on = opt.lookahead > 0 || (opt.lookahead < 0 && sizeof(T) == 4 && n >= 7000 && g_engines.load() == 1);
+        return on && !sync_mode && !opt.pipeline && prof.mode != 1 && k > 16 && k <= 2 * kLaMaxObs && opt.gather_corr_wide &&
+               opt.fuse_predict && (sizeof(T) == 4 || opt.fuse_f64) && defer_max >= k + (la_n ? 2 * la_q[0].m : k) &&
+               pend.wcap >= k + (la_n ? 2 * la_q[0].m : k) && seq.count == 0 && pend.hd_cols[0] == 0 && pend.hd_cols[1] == 0 && n > 3 &&
                kp_call_limit == 0;
     }
 
@@ -1774,10 +1556,10 @@ struct Ekf : EkfBase
         // no wide is held -- the first window after a drain, a predecessor on the classic path, several engines alive,
         // CSLAM_LA_HOLD_WIDE=0 -- does ekf_stage_obs_kernel run (cslam_ekf_stage_launches counts those).  (The stage
         // kernel on stream F with an event wait on the main stream instead measured no faster: DESIGN.md.)
-        //   The ring slot of a carried snapshot needs no event.  stage_ev[slot] protects the slot's PINNED HOST half, which
+        //   The ring slot of a carried snapshot needs no event.  ring.ev[slot] protects the slot's PINNED HOST half, which
         // the CPU rewrites outside any stream; a carried copy does not touch it (a later host-staged use of the slot still
         // waits for the event of the slot's last host-staged use).  The DEVICE half is protected by stream order alone, as
-        // it always was: a slot comes round again kStagingSlots stages -- at least 31 windows -- later; its readers were
+        // it always was: a slot comes round again StageRing::kSlots stages -- at least 31 windows -- later; its readers were
         // the rows, blocks and wide kernels of its window on the main stream and that window's chain kernel on stream F,
         // which the window's wide kernel waits for (in the kernel, or behind ev_fb) before it ends; and the writer, this
         // window's predecessor's wide kernel, is enqueued on the main stream behind all of them.
@@ -1792,7 +1574,7 @@ struct Ekf : EkfBase
             {
                 if (la_held.valid)
                 {
-                    unsigned char* ds = dStage.get() + slot_bytes(mcap) * stage_take_slot();
+                    unsigned char* ds = ring.dev_slot(ring.take_slot());
                     LaSnapJob      job;
                     job.Z       = dZ;
                     job.idf     = dIdf;
@@ -1881,19 +1663,19 @@ struct Ekf : EkfBase
         PredictArgs<T> pnone{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
         PredictArgs<T> pa   = fuse_now ? pp : pnone;
         T*             pred = fuse_now ? dPred.get() : (T*)nullptr;
-        const T*       Wg   = kp > 0 ? (const T*)wbase(wcur) : (const T*)nullptr;
-        if (kp > kGatherCorr)
+        const T*       Wg   = pend.kp > 0 ? (const T*)wbase(pend.wcur) : (const T*)nullptr;
+        if (pend.kp > kGatherCorr)
         {
             const dim3 wgrid((n + 255) / 256, (u.m + kGatherObsWide - 1) / kGatherObsWide);
             hipLaunchKernelGGL((ekf_gather_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream,
-                               dX.get(), dP.get(), dPv.get(), ldp, n, u.dZ, u.dIdf, u.m, ws.dPHT.get(), ldp, lower,
-                               (T*)nullptr, pa, pred, Wg, ldp, kp, (const int*)nullptr, dFlags.get(), (T*)nullptr);
+                               dX.get(), dP.get(), dPv.get(), ldp, n, u.dZ, u.dIdf, u.m, ws.dPHT.get(), ldp, opt.lower,
+                               (T*)nullptr, pa, pred, Wg, ldp, pend.kp, (const int*)nullptr, dFlags.get(), (T*)nullptr);
         }
         else
         {
             const dim3 ggrid((n + 255) / 256, (u.m + kGatherObs - 1) / kGatherObs);
             hipLaunchKernelGGL(ekf_gather_kernel<T>, ggrid, dim3(256), 0, stream, dX.get(), dP.get(), dPv.get(), ldp, n,
-                               u.dZ, u.dIdf, u.m, ws.dPHT.get(), ldp, lower, (T*)nullptr, pa, pred, Wg, ldp, kp,
+                               u.dZ, u.dIdf, u.m, ws.dPHT.get(), ldp, opt.lower, (T*)nullptr, pa, pred, Wg, ldp, pend.kp,
                                (const int*)nullptr, dFlags.get(), (T*)nullptr);
         }
         CSLAM_HIP_TRY(hipGetLastError());
@@ -1901,7 +1683,7 @@ struct Ekf : EkfBase
         {
             CSLAM_HIP_TRY(hipStreamWaitEvent(stream, ev_factor, 0));
         }
-        T*  slot = wbase(wcur) + (size_t)kp * ldp;
+        T*  slot = wbase(pend.wcur) + (size_t)pend.kp * ldp;
         rc       = launch_gain(k, slot, f.Gt.get(), f.U.get(), f.M.get());
         if (rc)
         {
@@ -1910,7 +1692,7 @@ struct Ekf : EkfBase
         pp.valid  = 0;
         fuse_now  = false;
         last_slot = slot;
-        kp += k;
+        pend.appended(k);
         dbgS      = f.S.get();
         dbgGt     = f.Gt.get();
         dbgV      = f.V.get();
@@ -1919,81 +1701,199 @@ struct Ekf : EkfBase
         return CSLAM_OK;
     }
 
+    // A window is updates ua and ub; ub is ua again when the window has only one (nu == 1: nothing reads b's share).
+    // hold: the wide launch waits for the next call (la_launch_held_wide); update b's caller buffers are then read by the
+    // rows and blocks kernels only, the chain kernel and the wide kernel read the copies those keep.
+    // The builders of the five argument structs of a window (ekf_lookahead.hpp).  They assign fields and nothing else: no
+    // allocation, no HIP call, so none of them can fail (la_launch_window relies on it).
+    LaChainArgs<T> la_chain_args(const LaUpd& ua, const LaUpd& ub, int nu, bool hold, unsigned target, unsigned seq)
+    {
+        LaChainArgs<T> ch;
+        ch.fa = la_factor_args(ua, la.fo[0]);
+        ch.fb = la_factor_args(ub, la.fo[1]);
+        if (hold)
+        {
+            ch.fb.Z = la.z_keep.get();
+        }
+        ch.du_a       = la.fo[0].U.get();
+        ch.du_b       = la.fo[1].U.get();
+        ch.nu         = nu;
+        ch.done       = la.done.get();
+        ch.target     = target;
+        ch.timeout    = 20000000ull; // 0.2 s of s_memrealtime ticks
+        ch.chain_done = la.done.get() + 256;
+        ch.seq        = seq;
+        LaCarryArgs<T>& ca = ch.ca;
+        ca.n       = n;
+        ca.m_a     = ua.m;
+        ca.m_b     = nu == 2 ? ub.m : 0;
+        ca.idf_b   = hold ? la.idf_keep.get() : ub.dIdf;
+        ca.pp_b    = ub.pp;
+        ca.PH      = la.PH.get();
+        ca.Dbb     = la.Dbb.get();
+        ca.PvLb    = la.PvLb.get();
+        ca.XLb     = la.XL.get() + 2 * ua.m;
+        ca.model_a = la.model.get();
+        ca.Gt_a    = la.fo[0].Gt.get();
+        ca.u_a     = la.fo[0].U.get();
+        ca.M_a     = la.fo[0].M.get();
+        ca.sub_a   = la.fo[0].sub.get();
+        ca.sub_b   = la.fo[1].sub.get();
+        ca.xloc_b  = la.fo[1].xloc.get();
+        ca.model_b = la.model.get() + 1;
+        ca.Y_b     = la.Y.get();
+        return ch;
+    }
+    LaRowsArgs<T> la_rows_args(const LaUpd& ua, const LaUpd& ub, int nu, bool hold)
+    {
+        LaRowsArgs<T> ra;
+        ra.X     = dX.get();
+        ra.Pv    = dPv.get();
+        ra.ldp   = ldp;
+        ra.n     = n;
+        ra.idf_a = ua.dIdf;
+        ra.ra    = 2 * ua.m;
+        ra.idf_b = ub.dIdf;
+        ra.rb    = nu == 2 ? 2 * ub.m : 0;
+        ra.Wp    = wbase(pend.wcur);
+        ra.ldw   = ldp;
+        ra.kp    = pend.kp;
+        ra.kpad  = la_kpad;
+        ra.XL    = la.XL.get();
+        ra.PvL   = la.PvL.get();
+        ra.WR    = la_WR.get();
+        ra.flags = dFlags.get();
+        ra.idf_b_keep = hold ? la.idf_keep.get() : (int*)nullptr;
+        ra.Z_b        = ub.dZ;
+        ra.Z_b_keep   = hold ? la.z_keep.get() : (T*)nullptr;
+        return ra;
+    }
+    // pg_signal: the P-GEMM launch that follows releases the chain, not the blocks kernel's own workgroups
+    LaPrepArgs<T> la_prep_args(const LaUpd& ua, const LaUpd& ub, int nu, bool hold, bool pg_signal)
+    {
+        LaPrepArgs<T> pa;
+        pa.P       = dP.get();
+        pa.ldp     = ldp;
+        pa.n       = n;
+        pa.lower   = opt.lower;
+        pa.X       = dX.get();
+        pa.Pv      = dPv.get();
+        pa.idf_a   = ua.dIdf;
+        pa.idf_b   = ub.dIdf;
+        pa.ra      = 2 * ua.m;
+        pa.rb      = nu == 2 ? 2 * ub.m : 0;
+        pa.pp_a    = ua.pp;
+        pa.XL      = la.XL.get();
+        pa.PvL     = la.PvL.get();
+        pa.WR      = la_WR.get();
+        pa.kp      = pend.kp;
+        pa.kpad    = la_kpad;
+        pa.sub_a   = la.fo[0].sub.get();
+        pa.PH      = la.PH.get();
+        pa.Dbb     = la.Dbb.get();
+        pa.PvLb    = la.PvLb.get();
+        pa.model_a = la.model.get();
+        pa.xloc_a  = la.fo[0].xloc.get();
+        pa.idloc   = la.fo[0].idloc.get();
+        pa.done    = pg_signal ? (unsigned*)nullptr : la.done.get();
+        return pa;
+    }
+    // (f32 only, as the two builders below: what the mirror form of the blocks kernel does in the rows kernel's place)
+    LaMirrorArgs la_mirror_args(const LaUpd& ua, const LaUpd& ub, int nu, bool hold)
+    {
+        LaMirrorArgs mi;
+        mi.WT         = la_WT.get();
+        mi.XLb        = la.XL.get() + 2 * ua.m;
+        mi.flags      = dFlags.get();
+        mi.idf_b_keep = hold ? la.idf_keep.get() : (int*)nullptr;
+        mi.Z_b        = ub.dZ;
+        mi.Z_b_keep   = hold ? la.z_keep.get() : (float*)nullptr;
+        return mi;
+    }
+    // (the window's panels go behind the pend.kp pending columns; la_seq is the window's chain kernel)
+    LaWideArgs la_wide_args(const LaUpd& ua, const LaUpd& ub, int nu, bool hold)
+    {
+        LaWideArgs wa;
+        wa.chain_done = la.done.get() + 256; // (waits for the chain kernel in the kernel: a stream event costs ~6 us here)
+        wa.seq        = la_seq;
+        wa.timeout    = 20000000ull;
+        wa.flags      = dFlags.get();
+        wa.stamps     = la.stamps.get() ? la.stamps.get() + 16 : nullptr;
+        wa.wg_times   = nullptr;
+        wa.P       = dP.get();
+        wa.ldp     = ldp;
+        wa.n       = n;
+        wa.lower   = opt.lower;
+        wa.X       = dX.get();
+        wa.Pv      = dPv.get();
+        wa.nu      = nu;
+        wa.idf_a   = ua.dIdf;
+        wa.idf_b   = hold ? la.idf_keep.get() : ub.dIdf;
+        wa.ma      = ua.m;
+        wa.mb      = nu == 2 ? ub.m : 0;
+        wa.valid_a = ua.pp.valid;
+        wa.valid_b = nu == 2 ? ub.pp.valid : 0;
+        wa.w_a     = ua.pp.w;
+        wa.w_b     = nu == 2 ? ub.pp.w : 0;
+        wa.model_a = la.model.get();
+        wa.model_b = la.model.get() + 1;
+        wa.Gt_a    = la.fo[0].Gt.get();
+        wa.u_a     = la.fo[0].U.get();
+        wa.M_a     = la.fo[0].M.get();
+        wa.sub_a   = la.fo[0].sub.get();
+        wa.Gt_b    = la.fo[1].Gt.get();
+        wa.u_b     = la.fo[1].U.get();
+        wa.M_b     = la.fo[1].M.get();
+        wa.sub_b   = la.fo[1].sub.get();
+        wa.Y_b     = la.Y.get();
+        wa.W1a     = wbase(pend.wcur) + (size_t)pend.kp * ldp;
+        wa.W1b     = wa.W1a + (size_t)2 * ua.m * ldp;
+        wa.ldw     = ldp;
+        wa.wv_out  = ws.dWv.get();
+        wa.snap    = LaSnapJob{nullptr, nullptr, nullptr, nullptr, 0};
+        return wa;
+    }
+
     // may_hold: the caller is the update that completes the window (la_enqueue), so the wide launch may wait for the next call
     int la_launch_window(bool may_hold = false)
     {
-        const int nu = la_n;
-        if (nu == 0)
+        if (la_n == 0)
         {
             return CSLAM_OK;
         }
+        const int   nu = la_n;
+        const LaUpd ua = la_q[0], ub = la_q[nu - 1]; // (one update: b is a again, and nothing reads b's share)
+        const int   ka = 2 * ua.m, kb = nu == 2 ? 2 * ub.m : 0;
         la_n = 0; // (no wide launch is held here: the call that queued update a has submitted it)
-        const LaUpd ua = la_q[0], ub = la_q[1];
         const PredictArgs<T> held = pp; // a predict accepted AFTER the queued updates stays held
         int rc = use_device();
         if (rc)
         {
             return rc;
         }
-        const int ka = 2 * ua.m, kb = nu == 2 ? 2 * ub.m : 0;
-        if (kp > 256 && (rc = flush())) // (the blocks kernel stages one row of at most 256 pending columns)
+        if (pend.kp > 256 && (rc = flush())) // (the blocks kernel stages one row of at most 256 pending columns)
         {
             return rc;
         }
-        if ((rc = ensure_k(2 * kLaMaxObs)) || (rc = ensure_w(ka + kb)) || (rc = la_ensure(kp)))
+        if ((rc = ensure_k(2 * kLaMaxObs)) || (rc = ensure_w(ka + kb)) || (rc = la_ensure(pend.kp)))
         {
             return rc;
         }
         // (the P-GEMM's tile list is (re)built here, not inside the launch below: building it waits for both streams, and
         // from the chain launch on stream F waits for a go-ahead that only that P-GEMM launch delivers)
-        if (lower && (rc = ensure_tile_list(round_up(n, kTile) / kTile)))
+        if (opt.lower && (rc = ensure_tile_list(round_up(n, kTile) / kTile)))
         {
             return rc;
         }
         // 1. the factor chain of the window on stream F, ONE launch, submitted first: it takes a compute unit for itself
         //    and waits there (on a counter) for the blocks kernel below.  (safe: several engines alive -- the chain kernel is
         //    launched behind the blocks kernel's event instead, see g_engines)
-        const bool     safe     = g_engines.load() > 1;
+        const bool safe = g_engines.load() > 1;
         const unsigned n_blocks = (unsigned)(3 + ka + 2 * kb);
-        // hold: the wide launch waits for the next call (la_launch_held_wide).  Update b's caller buffers are then read by
-        // the rows and blocks kernels only; the chain kernel and the wide kernel read the copies those keep.
-        const bool hold = may_hold && la_hold_wide && la_fused && !safe && nu == 2 && std::is_same<T, float>::value &&
-                          !la.stamps.get();
+        const bool hold = may_hold && opt.la_hold_wide && opt.la_fused && !safe && nu == 2 && std::is_same<T, float>::value &&
+                 !la.stamps.get();
         auto launch_chain = [&]() -> int {
-            LaChainArgs<T> ch;
-            ch.fa   = la_factor_args(ua, la.fo[0]);
-            ch.fb   = la_factor_args(nu == 2 ? ub : ua, la.fo[1]);
-            if (hold)
-            {
-                ch.fb.Z = la.z_keep.get();
-            }
-            ch.du_a = la.fo[0].U.get();
-            ch.du_b = la.fo[1].U.get();
-            ch.nu   = nu;
-            ch.done = la.done.get();
-            ch.target  = la_target + n_blocks;
-            ch.timeout = 20000000ull; // 0.2 s of s_memrealtime ticks
-            ch.chain_done = la.done.get() + 256;
-            ch.seq        = ++la_seq;
-            LaCarryArgs<T>& ca = ch.ca;
-            ca.n       = n;
-            ca.m_a     = ua.m;
-            ca.m_b     = nu == 2 ? ub.m : 0;
-            ca.idf_b   = hold ? la.idf_keep.get() : (nu == 2 ? ub.dIdf : ua.dIdf);
-            ca.pp_b    = nu == 2 ? ub.pp : ua.pp;
-            ca.PH      = la.PH.get();
-            ca.Dbb     = la.Dbb.get();
-            ca.PvLb    = la.PvLb.get();
-            ca.XLb     = la.XL.get() + ka;
-            ca.model_a = la.model.get();
-            ca.Gt_a    = la.fo[0].Gt.get();
-            ca.u_a     = la.fo[0].U.get();
-            ca.M_a     = la.fo[0].M.get();
-            ca.sub_a   = la.fo[0].sub.get();
-            ca.sub_b   = la.fo[1].sub.get();
-            ca.xloc_b  = la.fo[1].xloc.get();
-            ca.model_b = la.model.get() + 1;
-            ca.Y_b     = la.Y.get();
+            const LaChainArgs<T> ch = la_chain_args(ua, ub, nu, hold, la_target + n_blocks, ++la_seq);
             if (std::max(ka, kb) <= 32)
             {
                 hipLaunchKernelGGL((ekf_la_chain_kernel<T, 32>), dim3(1), dim3(256), la_chain_lds<T>(32), stream_f, ch);
@@ -2012,87 +1912,35 @@ struct Ekf : EkfBase
         }
         // 2. what the chain needs of the current covariance P = Ps - Wp Wp^T (before Ps changes): rows of the pending
         //    panels, then one workgroup per row of the small blocks; update a's compact block sub_a comes out of it ready
-        //    for the factor step.  (From here to the blocks launch nothing may fail: the chain kernel is waiting.)
-        const T* Wp = wbase(wcur);
-        LaRowsArgs<T> ra;
-        ra.X     = dX.get();
-        ra.Pv    = dPv.get();
-        ra.ldp   = ldp;
-        ra.n     = n;
-        ra.idf_a = ua.dIdf;
-        ra.ra    = ka;
-        ra.idf_b = nu == 2 ? ub.dIdf : ua.dIdf;
-        ra.rb    = kb;
-        ra.Wp    = Wp;
-        ra.ldw   = ldp;
-        ra.kp    = kp;
-        ra.kpad  = la_kpad;
-        ra.XL    = la.XL.get();
-        ra.PvL   = la.PvL.get();
-        ra.WR    = la_WR.get();
-        ra.flags = dFlags.get();
-        ra.idf_b_keep = hold ? la.idf_keep.get() : (int*)nullptr;
-        ra.Z_b        = ub.dZ;
-        ra.Z_b_keep   = hold ? la.z_keep.get() : (T*)nullptr;
-        // (the mirror form of the blocks kernel needs no rows kernel: when the mirror covers every pending column, or
-        // there is none)
+        //    for the factor step.  The chain kernel is waiting: nothing may fail from here to the blocks launch, and
+        //    nothing can -- only argument builders stand in between.
+        //    The mirror form of the blocks kernel needs no rows kernel: when the mirror covers every pending column, or
+        //    there is none.
         bool use_mirror = false;
         if constexpr (std::is_same<T, float>::value)
         {
-            use_mirror = la_mirror && (kp == 0 || (la_mirror_cols == kp && la_mirror_n == n && kp <= 128 && kp % 4 == 0));
+            use_mirror = opt.la_mirror &&
+                         (pend.kp == 0 || (pend.mirror_covers(pend.kp, n) && pend.kp <= 128 && pend.kp % 4 == 0));
         }
-        if (!use_mirror)
-        {
-            hipLaunchKernelGGL(ekf_la_rows_kernel<T>, dim3(ka + kb), dim3(128), 0, stream, ra);
-            rows_launches++;
-        }
-        LaPrepArgs<T> pa;
-        pa.P       = dP.get();
-        pa.ldp     = ldp;
-        pa.n       = n;
-        pa.lower   = lower;
-        pa.X       = dX.get();
-        pa.Pv      = dPv.get();
-        pa.idf_a   = ua.dIdf;
-        pa.idf_b   = nu == 2 ? ub.dIdf : ua.dIdf;
-        pa.ra      = ka;
-        pa.rb      = kb;
-        pa.pp_a    = ua.pp;
-        pa.XL      = la.XL.get();
-        pa.PvL     = la.PvL.get();
-        pa.WR      = la_WR.get();
-        pa.kp      = kp;
-        pa.kpad    = la_kpad;
-        pa.sub_a   = la.fo[0].sub.get();
-        pa.PH      = la.PH.get();
-        pa.Dbb     = la.Dbb.get();
-        pa.PvLb    = la.PvLb.get();
-        pa.model_a = la.model.get();
-        pa.xloc_a  = la.fo[0].xloc.get();
-        pa.idloc   = la.fo[0].idloc.get();
         // the P-GEMM that follows signals the chain when it is the plain single-stream psym4 launch (always in the steady state);
         // otherwise the blocks kernel's workgroups release their rows themselves
-        const int  k8f      = round_up(kp, 8);
-        const bool pg_signal = !la_wg_signal && !safe && kp > 0 && seq.count == 0 && sizeof(T) == 4 && k8f <= 128 && lower && ldp < 32768 &&
-                               !limbs_take(k8f) && stream_b == stream && hd_cols[wcur] == 0;
-        pa.done    = pg_signal ? (unsigned*)nullptr : la.done.get();
+        const int  k8f       = round_up(pend.kp, 8);
+        const bool pg_signal = !opt.la_wg_signal && !safe && pend.kp > 0 && seq.count == 0 && sizeof(T) == 4 && k8f <= 128 &&
+                               opt.lower && ldp < 32768 && !limbs_take(k8f) && stream_b == stream &&
+                               pend.hd_cols[pend.wcur] == 0;
         if constexpr (std::is_same<T, float>::value)
         {
             if (use_mirror)
             {
-                LaMirrorArgs mi;
-                mi.WT         = la_WT.get();
-                mi.XLb        = la.XL.get() + ka;
-                mi.flags      = dFlags.get();
-                mi.idf_b_keep = ra.idf_b_keep;
-                mi.Z_b        = ra.Z_b;
-                mi.Z_b_keep   = ra.Z_b_keep;
-                hipLaunchKernelGGL(ekf_la_blocks_mirror_kernel, dim3(n_blocks), dim3(256), 0, stream, pa, mi);
+                hipLaunchKernelGGL(ekf_la_blocks_mirror_kernel, dim3(n_blocks), dim3(256), 0, stream,
+                                   la_prep_args(ua, ub, nu, hold, pg_signal), la_mirror_args(ua, ub, nu, hold));
             }
         }
         if (!use_mirror)
         {
-            hipLaunchKernelGGL(ekf_la_blocks_kernel<T>, dim3(n_blocks), dim3(64), 0, stream, pa);
+            hipLaunchKernelGGL(ekf_la_rows_kernel<T>, dim3(ka + kb), dim3(128), 0, stream, la_rows_args(ua, ub, nu, hold));
+            rows_launches++;
+            hipLaunchKernelGGL(ekf_la_blocks_kernel<T>, dim3(n_blocks), dim3(64), 0, stream, la_prep_args(ua, ub, nu, hold, pg_signal));
         }
         CSLAM_HIP_TRY(hipGetLastError());
         if (safe)
@@ -2123,54 +1971,15 @@ struct Ekf : EkfBase
         bool fused = false;
         if constexpr (std::is_same<T, float>::value)
         {
-            if (la_fused)
+            if (opt.la_fused)
             {
                 fused = true;
                 // (several engines alive: la_launch_held_wide puts the wait for ev_fb in front of the launch)
-                LaWideArgs wa;
-                wa.chain_done = la.done.get() + 256; // (waits for the chain kernel in the kernel: a stream event costs ~6 us here)
-                wa.seq        = la_seq;
-                wa.timeout    = 20000000ull;
-                wa.flags      = dFlags.get();
-                wa.stamps     = la.stamps.get() ? la.stamps.get() + 16 : nullptr;
-                wa.wg_times   = nullptr;
-                wa.P       = dP.get();
-                wa.ldp     = ldp;
-                wa.n       = n;
-                wa.lower   = getenv("CSLAM_LA_TIMING_DIRECT") ? 0 : lower; // (timing experiment only: wrong results)
-                wa.X       = dX.get();
-                wa.Pv      = dPv.get();
-                wa.nu      = nu;
-                wa.idf_a   = ua.dIdf;
-                wa.idf_b   = hold ? la.idf_keep.get() : (nu == 2 ? ub.dIdf : ua.dIdf);
-                wa.ma      = ua.m;
-                wa.mb      = nu == 2 ? ub.m : 0;
-                wa.valid_a = ua.pp.valid;
-                wa.valid_b = nu == 2 ? ub.pp.valid : 0;
-                wa.w_a     = ua.pp.w;
-                wa.w_b     = nu == 2 ? ub.pp.w : 0;
-                wa.model_a = la.model.get();
-                wa.model_b = la.model.get() + 1;
-                wa.Gt_a    = la.fo[0].Gt.get();
-                wa.u_a     = la.fo[0].U.get();
-                wa.M_a     = la.fo[0].M.get();
-                wa.sub_a   = la.fo[0].sub.get();
-                wa.Gt_b    = la.fo[1].Gt.get();
-                wa.u_b     = la.fo[1].U.get();
-                wa.M_b     = la.fo[1].M.get();
-                wa.sub_b   = la.fo[1].sub.get();
-                wa.Y_b     = la.Y.get();
-                wa.W1a     = wbase(wcur) + (size_t)kp * ldp;
-                wa.W1b     = wa.W1a + (size_t)ka * ldp;
-                wa.ldw     = ldp;
-                wa.wv_out  = ws.dWv.get();
-                wa.snap    = LaSnapJob{nullptr, nullptr, nullptr, nullptr, 0};
-                la_held.wa    = wa;
-                la_held.k64   = la_k64 && ua.m == 32 && (nu == 1 || ub.m == 32);
+                la_held.wa  = la_wide_args(ua, ub, nu, hold);
+                la_held.k64 = opt.la_k64 && ua.m == 32 && ub.m == 32;
                 // (the mirror's column q is the store's column q: the panels must start at column 0 of the store)
-                la_held.wt     = (la_mirror && la_held.k64 && kp == 0) ? la_WT.get() : nullptr;
-                la_mirror_cols = la_held.wt ? ka + kb : 0;
-                la_mirror_n    = n;
+                la_held.wt = (opt.la_mirror && la_held.k64 && pend.kp == 0) ? la_WT.get() : nullptr;
+                pend.mirror_written(la_held.wt ? ka + kb : 0, n);
                 la_held.grid  = (unsigned)(round_up(n, kTile) / 32);
                 la_held.valid = true;
                 if (!hold && (rc = la_launch_held_wide(nullptr)))
@@ -2179,28 +1988,30 @@ struct Ekf : EkfBase
                 }
                 last_slot = nullptr; // (PHT is not materialised on this path: nothing for debug_last_update)
                 last_k    = 0;
-                kp += ka + kb;
+                pend.appended(ka + kb);
                 sub_valid = false;
             }
         }
-        if (!fused && ((rc = la_wide(ua, la.fo[0], la.ev_fb.get())) || (nu == 2 && (rc = la_wide(ub, la.fo[1],
-                                                                                                 nullptr)))))
+        if (!fused && ((rc = la_wide(ua, la.fo[0], la.ev_fb.get())) || (nu == 2 && (rc = la_wide(ub, la.fo[1], nullptr)))))
         {
             return rc;
         }
         pp = held;
         la_windows++;
-        if (la.stamps.get() && la_windows == 300)
-        {
-            long long h[32];
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            CSLAM_HIP_TRY(hipMemcpy(h, la.stamps.get(), sizeof(h), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[cslam la wide stamps, 10 ns ticks] ids+columns issue:%lld poll+DMA wait:%lld pht_a:%lld gain_a:%lld store+share W1_a:%lld pht_b+corr:%lld share+G_b:%lld gain_b:%lld store_b:%lld\n",
-                    h[17] - h[16], h[18] - h[17], h[19] - h[18], h[20] - h[19], h[21] - h[20], h[22] - h[21], h[23] - h[22],
-                    h[24] - h[23], h[25] - h[24]);
-            fprintf(stderr, "[cslam la stamps, cycles] load+observe:%lld sums:%lld symmetrise:%lld cholesky:%lld (first half %lld) inverse:%lld outputs:%lld total:%lld\n",
-                    h[6] - h[0], h[7] - h[6], h[1] - h[7], h[2] - h[1], h[5] ? h[5] - h[1] : 0, h[3] - h[2], h[4] - h[3], h[4] - h[0]);
-        }
+        return (la.stamps.get() && la_windows == 300) ? la_report_stamps() : CSLAM_OK;
+    }
+
+    // CSLAM_LA_STAMPS: where factor(a) and the wide kernel spent their time, once, after 300 windows
+    int la_report_stamps()
+    {
+        long long h[32];
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        CSLAM_HIP_TRY(hipMemcpy(h, la.stamps.get(), sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "[cslam la wide stamps, 10 ns ticks] ids+columns issue:%lld poll+DMA wait:%lld pht_a:%lld gain_a:%lld store+share W1_a:%lld pht_b+corr:%lld share+G_b:%lld gain_b:%lld store_b:%lld\n",
+                h[17] - h[16], h[18] - h[17], h[19] - h[18], h[20] - h[19], h[21] - h[20], h[22] - h[21], h[23] - h[22],
+                h[24] - h[23], h[25] - h[24]);
+        fprintf(stderr, "[cslam la stamps, cycles] load+observe:%lld sums:%lld symmetrise:%lld cholesky:%lld (first half %lld) inverse:%lld outputs:%lld total:%lld\n",
+                h[6] - h[0], h[7] - h[6], h[1] - h[7], h[2] - h[1], h[5] ? h[5] - h[1] : 0, h[3] - h[2], h[4] - h[3], h[4] - h[0]);
         return CSLAM_OK;
     }
 
@@ -2260,29 +2071,29 @@ struct Ekf : EkfBase
         // EKF.cpp:457-479: m successive rank-2 updates, relinearised on the updated state each time.  Their m
         // rank-2 downdates stay pending and are applied by ONE P-GEMM with k = 2m: each observation reads the columns
         // it needs as Ps[:,c] - Wp*Wp[c,:]^T.
-        if (seq_defer)
+        if (opt.seq_defer)
         {
             // (every rank-2 slot is written as a block of 8 columns: the last one reaches column kp + 2m + 6)
             if ((rc = ensure_w(2 * m + 8)))
             {
                 return rc;
             }
-            if (kp + 2 * m + 6 > wcap && (rc = flush()))
+            if (pend.kp + 2 * m + 6 > pend.wcap && (rc = flush()))
             {
                 return rc;
             }
         }
-        kp_call_limit = seq_defer ? kp + 2 * m : 0;
+        kp_call_limit = opt.seq_defer ? pend.kp + 2 * m : 0;
         for (int i = 0; i < m; i++)
         {
-            if ((rc = batch_on_device(dZ + 2 * i, dIdf + i, 1, R, seq_defer != 0)))
+            if ((rc = batch_on_device(dZ + 2 * i, dIdf + i, 1, R, opt.seq_defer != 0)))
             {
                 kp_call_limit = 0;
                 return rc;
             }
         }
         kp_call_limit = 0;
-        if (!pipeline && defer_max == 0 && (rc = flush()))
+        if (!opt.pipeline && defer_max == 0 && (rc = flush()))
         {
             return rc;
         }
@@ -2316,7 +2127,7 @@ struct Ekf : EkfBase
             // (pending panels: their rows for the new feature are zero, which is right -- the kernel writes values of
             // the true P, built from the pose stripe)
             hipLaunchKernelGGL(ekf_augment_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, dX.get(), dP.get(),
-                               dPv.get(), ldp, n, Z[2 * i], Z[2 * i + 1], R[0], R[1], R[2], R[3], lower);
+                               dPv.get(), ldp, n, Z[2 * i], Z[2 * i + 1], R[0], R[1], R[2], R[3], opt.lower);
             CSLAM_HIP_TRY(hipGetLastError());
             n += 2;
         }
@@ -2333,7 +2144,7 @@ struct Ekf : EkfBase
         // float sigmaPhi = 0.01F * pi / 180.0F; R = pow(sigmaPhi, 2)
         T   sigma = (T)(((double)0.01f * kPi) / 180.0);
         int rc    = queue_step(pp, HeadingArgs<T>{1, (T)phi, sigma * sigma}); // with the held predict, if any
-        if (rc || fuse_predict)
+        if (rc || opt.fuse_predict)
         {
             return rc;
         }
@@ -2513,12 +2324,12 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
     // while this P-GEMM fills the chip.
     // (two-stream mode: a few CUs keep one workgroup; look-ahead windows: the main stream's queue mask excludes the
     // compute units of the factor chain's stream, see la_ensure)
-    int G = std::min(n_sym_tiles, std::max(1, 2 * (num_cus - la_cus) - (pipeline ? pgemm_spare : 0)));
+    int G = std::min(n_sym_tiles, std::max(1, 2 * (num_cus - la_cus) - (opt.pipeline ? opt.pgemm_spare : 0)));
     if (pgemm_wgs > 0)
     {
         G = std::min(G, pgemm_wgs);
     }
-    const bool nt = psym_nt >= 0 ? psym_nt != 0 : (size_t)n_sym_tiles * 65536 > ((size_t)230 << 20);
+    const bool nt = opt.psym_nt >= 0 ? opt.psym_nt != 0 : (size_t)n_sym_tiles * 65536 > ((size_t)230 << 20);
     if (limbs_take(k8))
     {
         // f32 products as exact bf16 limb products on the bf16 matrix cores (ekf_pgemm_limbs.hpp)
@@ -2560,7 +2371,7 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
 #define CSLAM_LAUNCH_PSYM5R(NCH, RR)                                                                                   \
     do                                                                                                                 \
     {                                                                                                                  \
-        if (pgemm_limbs == 6)                                                                                          \
+        if (opt.pgemm_limbs == 6)                                                                                          \
         {                                                                                                              \
             if (nt) { CSLAM_LAUNCH_PSYM5(1, NCH, 6, RR); } else { CSLAM_LAUNCH_PSYM5(0, NCH, 6, RR); }                 \
         }                                                                                                              \
@@ -2580,14 +2391,14 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
 #undef CSLAM_LAUNCH_PSYM5R
 #undef CSLAM_LAUNCH_PSYM5
     }
-    else if (k8 <= 128 && lower && ldp < 32768)
+    else if (k8 <= 128 && opt.lower && ldp < 32768)
     {
         // the shipped P-GEMM: every memory operation interleaved with the MFMA loop; two chunks of 32 columns (k <= 64),
         // four of 24 (k <= 96) or four of 32 (k <= 128)
         launch_parity++;
         // per-XCD tile queues (see the kernel): env CSLAM_XCD_QUEUES (every queue needs workgroups: small grids stay on
         // the single queue)
-        const bool xq = xcd_queues != 0 && G >= 64;
+        const bool xq = opt.xcd_queues != 0 && G >= 64;
         if (xq)
         {
             if ((rc = ensure_tiles_morton(tiles, stream)))
@@ -2618,7 +2429,7 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
 #undef CSLAM_LAUNCH_PSYM4
         la_sig_add = 0; // (delivered)
     }
-    else if (lower)
+    else if (opt.lower)
     {
         // any k, block-lower storage: the unpipelined persistent symmetric kernel (windows beyond 128 columns)
         hipLaunchKernelGGL((ekf_downdate_psym_f32<64, true, false>), dim3(G), block, 0, stream, dP.get(), ldp, W, ldp,
@@ -2685,31 +2496,20 @@ template <>
 int Ekf<double>::launch_downdate(const double* W, int k, hipStream_t stream)
 {
     const int tiles_r = round_up(n, kTile) / kTile;
-    // columns of W1 staged per pass: 16, register-staged and double-buffered (see the kernel).  The synchronous staging
-    // loop (other values of CSLAM_F64_KCM) measured at N = 1000, k = 64: 8 / 16 / 32 -> 22.8 / 21.9 / 22.9 us, 64 (the whole
-    // panel at once, 96 KB of LDS, one workgroup per CU) -> 30.5 us.
-    int kcm = 16;
-    if (const char* e = getenv("CSLAM_F64_KCM"))
-    {
-        kcm = std::max(4, std::min(64, round_up(atoi(e), 4)));
-    }
-    // tile width: 64 columns, or 32 for small states where the launch would not fill the chip (CSLAM_F64_CB overrides)
-    int cb = (tiles_r * (round_up(n, kTile) / 64) < 4 * num_cus) ? 2 : 4;
-    if (const char* e = getenv("CSLAM_F64_CB"))
-    {
-        cb = (atoi(e) == 2) ? 2 : 4;
-    }
+    const int kcm = opt.f64_kcm; // columns of W1 staged per pass
+    // tile width: 64 columns, or 32 for small states where the launch would not fill the chip (opt.f64_cb overrides)
+    const int cb = opt.f64_cb ? opt.f64_cb : ((tiles_r * (round_up(n, kTile) / 64) < 4 * num_cus) ? 2 : 4);
     const int tiles_c = round_up(n, kTile) / (16 * cb);
     const size_t lds  = (size_t)(kcm == 16 ? 2 : 1) * kcm * (128 + 16 * cb) * sizeof(double); // (16: two buffers)
     if (cb == 2)
     {
         hipLaunchKernelGGL(ekf_downdate_f64<2>, dim3(tiles_r * tiles_c), dim3(256), lds, stream, dP.get(), ldp, W, ldp,
-                           k, tiles_r, lower, kcm);
+                           k, tiles_r, opt.lower, kcm);
     }
     else
     {
         hipLaunchKernelGGL(ekf_downdate_f64<4>, dim3(tiles_r * tiles_c), dim3(256), lds, stream, dP.get(), ldp, W, ldp,
-                           k, tiles_r, lower, kcm);
+                           k, tiles_r, opt.lower, kcm);
     }
     CSLAM_HIP_TRY(hipGetLastError());
     return CSLAM_OK;
@@ -2777,14 +2577,15 @@ int cslam_ekf_create(int max_landmarks, int dtype, int device, int quirks, cslam
     {
         return fail(CSLAM_ERR_BAD_ARG, "ekf_create: device %d of %d", device, c);
     }
-    EkfBase* b = nullptr;
+    const EkfOptions opt = EkfOptions::from_env(); // (the only read of the environment: ekf_options.hpp)
+    EkfBase*         b   = nullptr;
     if (dtype == CSLAM_F32)
     {
-        b = new (std::nothrow) Ekf<float>();
+        b = new (std::nothrow) Ekf<float>(opt);
     }
     else
     {
-        b = new (std::nothrow) Ekf<double>();
+        b = new (std::nothrow) Ekf<double>(opt);
     }
     if (!b)
     {
@@ -2797,58 +2598,6 @@ int cslam_ekf_create(int max_landmarks, int dtype, int device, int quirks, cslam
     b->ncap   = 3 + 2 * max_landmarks;
     b->ldp    = round_up(b->ncap, kTile);
     b->n      = 3;
-    if (const char* sd = getenv("CSLAM_SEQ_DEFER"))
-    {
-        b->seq_defer = atoi(sd);
-    }
-    if (const char* ff = getenv("CSLAM_FUSE_F64"))
-    {
-        b->fuse_f64 = atoi(ff) ? 1 : 0;
-    }
-    if (const char* fp = getenv("CSLAM_FUSE_PREDICT"))
-    {
-        b->set_fuse_predict(atoi(fp));
-    }
-    // Block-lower storage (default): only the 128x128 tiles on / below the tile diagonal of the symmetric P are maintained
-    // (the P-GEMM writes each tile once).  CSLAM_STORAGE=full keeps both triangles (mirror stores in the P-GEMM).
-    b->lower = 1;
-    if (const char* sv = getenv("CSLAM_STORAGE"))
-    {
-        b->lower = strcmp(sv, "full") ? 1 : 0;
-    }
-    // two-stream pipelining (see the top of this file) is an option, not the default: measured at N = 5000, k = 64
-    // (profiles/r02_*): the kernels of update t+1 that touch memory crawl underneath the persistent P-GEMM (its waves
-    // are older and keep ~24 KB of requests in flight each: the pending-panel correction takes 65 us instead of 5.5)
-    // and every cross-stream hand-over costs ~6 us, so the period is 138 us against 112 us on one stream.
-    b->pipeline = 0;
-    if (const char* pv = getenv("CSLAM_PIPELINE"))
-    {
-        b->pipeline = atoi(pv) ? 1 : 0;
-    }
-    if (const char* xv = getenv("CSLAM_XCD_QUEUES"))
-    {
-        b->xcd_queues_req = atoi(xv) ? 1 : 0;
-    }
-    if (const char* lv = getenv("CSLAM_PGEMM_LIMBS"))
-    {
-        b->pgemm_limbs_req = atoi(lv);
-    }
-    if (const char* lk = getenv("CSLAM_LIMBS_KMIN"))
-    {
-        b->limbs_kmin_req = atoi(lk);
-    }
-    if (const char* lv = getenv("CSLAM_LOOKAHEAD"))
-    {
-        b->lookahead = atoi(lv) > 0 ? 1 : (atoi(lv) < 0 ? -1 : 0);
-    }
-    if (const char* gw = getenv("CSLAM_GATHER_WIDE"))
-    {
-        b->gather_corr_wide = atoi(gw) ? 1 : 0;
-    }
-    if (const char* sp = getenv("CSLAM_PGEMM_SPARE"))
-    {
-        b->pgemm_spare = std::max(0, atoi(sp));
-    }
     int rc    = b->init();
     if (rc)
     {

@@ -32,6 +32,7 @@
 #include "ekf_kernels_fast.hpp"
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
+#include "ekf_options.hpp"
 #include "ekf_pose_kernels.hpp"
 #include "ekf_score_kernels.hpp"
 #include "sim_scan_view.hpp"
@@ -149,10 +150,8 @@ struct cslam_ekf_batch
     int           wcur = 0, kp = 0; // pending region and its columns
     unsigned      target = 0, seq = 0;
     long long     windows = 0;
-    // A/B switches (env CSLAM_BATCH_WG_SIGNAL=1, CSLAM_BATCH_WIDE_PAIRS=1): the first forms of two stages, kept measurable
-    int wg_signal = 0, wide_pairs = 2;
-    int la_k64 = 1; // CSLAM_LA_K64=0: the general wide kernel for m = 32 too (A/B)
-    DevBuf<long long> dStamps; // CSLAM_BATCH_STAMPS=1: see LaBatchWin::stamps (printed after 300 windows)
+    const EkfBatchOptions opt; // the engine switches, as the environment had them at create (ekf_options.hpp)
+    DevBuf<long long> dStamps; // opt.stamps: see LaBatchWin::stamps (printed after 300 windows)
     // bench support: HIP events around one P-GEMM launch in `prof_every` (an event pair costs ~11 us of stream time)
     int                                          prof_every = 0;
     long long                                    prof_seen  = 0;
@@ -182,6 +181,8 @@ struct cslam_ekf_batch
         return CSLAM_OK;
     }
 
+    explicit cslam_ekf_batch(const EkfBatchOptions& o) : opt(o) {}
+
     ~cslam_ekf_batch()
     {
         (void)hipSetDevice(device);
@@ -202,19 +203,7 @@ struct cslam_ekf_batch
         {
             return rc;
         }
-        if (const char* e = getenv("CSLAM_BATCH_WG_SIGNAL"))
-        {
-            wg_signal = atoi(e) ? 1 : 0;
-        }
-        if (const char* e = getenv("CSLAM_LA_K64"))
-        {
-            la_k64 = atoi(e) ? 1 : 0;
-        }
-        if (const char* e = getenv("CSLAM_BATCH_WIDE_PAIRS"))
-        {
-            wide_pairs = atoi(e) == 1 ? 1 : 2;
-        }
-        if (getenv("CSLAM_BATCH_STAMPS"))
+        if (opt.stamps)
         {
             // 32 phase stamps, then {start, end} of up to 128 wide-kernel workgroups per instance
             CSLAM_TRY(dStamps.alloc_zeroed_blocking(32 + (size_t)I * 256));
@@ -623,8 +612,8 @@ struct cslam_ekf_batch
         w.kp       = kp;
         w.target   = target + n_blocks;
         w.seq      = ++seq;
-        w.wg_signal = wg_signal;
-        w.wide_direct = getenv("CSLAM_BATCH_TIMING_DIRECT") ? 1 : 0;
+        w.wg_signal = opt.wg_signal;
+        w.wide_direct = 0;
         w.stamps      = dStamps.get();
         w.timeout  = 20000000ull; // 0.2 s of s_memrealtime ticks: a stuck wait raises CSLAM_FACTOR_INTERNAL instead of hanging
         // 1. the factor chains first: each takes a compute unit and waits there for its instance's blocks
@@ -648,7 +637,7 @@ struct cslam_ekf_batch
         target += n_blocks;
         // 3. the P-GEMM of the previous window's panels: its first workgroup gives the chains their go-ahead (the blocks
         //    kernel has finished by then), and they run underneath it
-        int rc = flush(wg_signal ? 0u : n_blocks);
+        int rc = flush(opt.wg_signal ? 0u : n_blocks);
         if (rc)
         {
             return rc;
@@ -656,13 +645,13 @@ struct cslam_ekf_batch
         // 4. the wide half of both updates (waits in the kernel for its instance's chain); its W1 panels become the pending
         //    columns of the region the P-GEMM has just left
         w.Wn = wregion(wcur);
-        if (wide_pairs == 1)
+        if (opt.wide_pairs == 1)
         {
             hipLaunchKernelGGL(ekf_la_wide_batch1, dim3(round_up(n, kTile) / 32, I), dim3(128), 0, stream, w);
         }
         else
         {
-            if (la_k64 && w.ma == 32 && (w.nu == 1 || w.mb == 32))
+            if (opt.la_k64 && w.ma == 32 && (w.nu == 1 || w.mb == 32))
             {
                 hipLaunchKernelGGL(ekf_la_wide_batch_k64, dim3(round_up(n, kTile) / 64, I), dim3(256), 0, stream, w);
             }
@@ -685,7 +674,7 @@ struct cslam_ekf_batch
             std::vector<long long> wt((size_t)I * 256);
             CSLAM_HIP_TRY(hipMemcpy(wt.data(), dStamps.get() + 32, wt.size() * sizeof(long long),
                                     hipMemcpyDeviceToHost));
-            const int nwg = std::min(128, round_up(n, kTile) / (32 * wide_pairs));
+            const int nwg = std::min(128, round_up(n, kTile) / (32 * opt.wide_pairs));
             long long t0  = wt[0];
             for (int i = 0; i < I; i++)
             {
@@ -755,7 +744,7 @@ int cslam_ekf_batch_create_capacity(int instances, int max_landmarks, int n_land
         return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_create: %d instances x %d landmarks exceed the 4 GiB covariance slab", instances,
                     max_landmarks);
     }
-    cslam_ekf_batch* b = new (std::nothrow) cslam_ekf_batch();
+    cslam_ekf_batch* b = new (std::nothrow) cslam_ekf_batch(EkfBatchOptions::from_env());
     if (!b)
     {
         return fail(CSLAM_ERR_ALLOC, "ekf_batch_create: out of host memory");
