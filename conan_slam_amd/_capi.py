@@ -79,6 +79,19 @@ _PROTOTYPES.update({
 SCORE_SYMBOLS = tuple(k for k in _PROTOTYPES if "_score" in k)
 
 
+# The particle filter's data association (EKF.cpp:131-144, 235-326 on every particle's own state) and the consumers of
+# its per-particle table.
+_PROTOTYPES.update({
+    "cslam_pf_associate": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double],
+    "cslam_pf_get_association": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "cslam_pf_sample_proposal_assoc": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double],
+    "cslam_pf_feature_update_assoc": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "cslam_pf_get_stream": [C.c_void_p, C.POINTER(C.c_void_p)],
+})
+PF_ASSOC_SYMBOLS = tuple(k for k in _PROTOTYPES if k.startswith("cslam_pf_") and "assoc" in k)
+PF_ASSOC_FEAT_CHUNK, PF_ASSOC_OBS_CHUNK = 32, 8  # kPfAssocFeatChunk / kPfAssocObsChunk of csrc/pf_assoc_kernels.hpp
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
     text = open(header_path).read()

@@ -10,6 +10,7 @@
 #include <rccl/rccl.h> // types only: the library itself is bound with dlopen (see Rccl below)
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <mutex>
@@ -18,6 +19,7 @@
 
 #include "cslam_common.hpp"
 #include "device_owners.hpp"
+#include "pf_assoc_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
 
@@ -367,6 +369,12 @@ struct PfBase
     virtual int best_particle(Comm* c, int pick, long long* index, void* w, void* Xv, void* Pv, void* XF, void* PF) = 0;
     virtual int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF)              = 0;
     virtual int get_all_features(void* XF_all)                                                                      = 0;
+    // per-particle data association (pf_assoc_kernels.hpp) and the consumers of its table
+    virtual int associate(const void* Z, int m, const void* R, double gate1, double gate2)                          = 0;
+    virtual int get_association(int* idf, int* kind, double* summary)                                               = 0;
+    virtual int sample_proposal_assoc(const void* Z, int m, const void* R, const void* normals, const int* use,
+                                      double miss_likelihood)                                                       = 0;
+    virtual int feature_update_assoc(const void* Z, int m, const void* R, const int* use)                           = 0;
 };
 
 template <typename T>
@@ -860,6 +868,7 @@ struct Pf : PfBase
         {
             return rc;
         }
+        assoc_moved = true;
         hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx.get(), count,
                            static_cast<const T*>(drec));
         CSLAM_HIP_TRY(hipGetLastError());
@@ -875,6 +884,7 @@ struct Pf : PfBase
         {
             return rc;
         }
+        assoc_moved = true;
         hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx.get(), np, dRec.get());
         CSLAM_HIP_TRY(hipGetLastError());
         std::vector<int> ident((size_t)np);
@@ -1017,6 +1027,7 @@ struct Pf : PfBase
             return fail(CSLAM_ERR_HIP, "pf_resample_sharded: librccl could not be loaded");
         }
         const int world = c->world, rank = c->rank, L = np, N = np * world;
+        assoc_moved = true;
         int rc = use_device();
         if (rc || (rc = ensure_sharded_buffers(world)))
         {
@@ -1188,6 +1199,7 @@ struct Pf : PfBase
     // plan (sums, normalise, Neff, decision, keep[]) -> gather -> copy back + w = 1/N, the last two gated by a device flag
     int launch_resample(const T* d_select, double n_eff, int status)
     {
+        assoc_moved = true; // (whether it resamples is decided on the device)
         hipLaunchKernelGGL(pf_resample_plan_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, d_select, n_eff,
                            status, dCum.get(), dKeep.get(), dInfo.get(), dEnable.get());
         CSLAM_HIP_TRY(hipGetLastError());
@@ -1394,6 +1406,7 @@ struct Pf : PfBase
             return rc;
         }
         const size_t s = sizeof(T), pitch = (size_t)np * s;
+        assoc_moved    = true;
         if (w)
         {
             CSLAM_HIP_TRY(hipMemcpyAsync(dW.get() + i, w, s, hipMemcpyHostToDevice, stream));
@@ -1632,6 +1645,228 @@ struct Pf : PfBase
         std::memcpy(XF_all, hEst.get(), count * sizeof(T));
         return CSLAM_OK;
     }
+
+    // ------------------------------------------------------------------------------------------------
+    // Per-particle gated nearest-neighbour association (EKF.cpp:131-144, 235-326 on each particle's own state) and the
+    // consumers that read its table.  The tables belong to the handle and describe the LAST associate call: its
+    // observations (kept on the host to recognise them again), the particle order and the map size of that moment.
+    // ------------------------------------------------------------------------------------------------
+    DevBuf<T>         dAPartNd, dAPartNis, dARawNd;
+    DevBuf<int>       dAPartJ, dARawIdf, dARawKind, dAIdf, dAKind;
+    DevBuf<double>    dASummary;
+    size_t            assoc_part_cap = 0; // entries of the three partial tables
+    int               assoc_mcap     = 0; // observations the (m x np) tables and the summary hold
+    int               assoc_m        = -1; // -1: associate has not been called
+    int               assoc_nf       = 0;
+    bool              assoc_moved    = false; // particles changed slots (resample, unpack, set_particle) since associate
+    std::vector<char> assoc_Z;            // the 2 * assoc_m observation scalars of the last associate
+
+    // all-or-nothing growth (device_owners.hpp): new buffers into locals first, members replaced only when all exist
+    int ensure_assoc(int m, int nchunks)
+    {
+        const size_t need_part = (size_t)std::max(nchunks, 1) * m * np;
+        if (need_part > assoc_part_cap)
+        {
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still reads the old partials
+            DevBuf<T>   nd, nis;
+            DevBuf<int> pj;
+            int         rc = nd.alloc(need_part);
+            if (rc || (rc = nis.alloc(need_part)) || (rc = pj.alloc(need_part)))
+            {
+                return rc;
+            }
+            dAPartNd       = std::move(nd);
+            dAPartNis      = std::move(nis);
+            dAPartJ        = std::move(pj);
+            assoc_part_cap = need_part;
+        }
+        if (m > assoc_mcap)
+        {
+            const int    newm = std::max(m, std::max(64, 2 * assoc_mcap));
+            const size_t cnt  = (size_t)newm * np;
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+            DevBuf<T>      rnd;
+            DevBuf<int>    ridf, rkind, idf, kind;
+            DevBuf<double> sum;
+            int            rc = rnd.alloc(cnt);
+            if (rc || (rc = ridf.alloc(cnt)) || (rc = rkind.alloc(cnt)) || (rc = idf.alloc(cnt)) ||
+                (rc = kind.alloc(cnt)) || (rc = sum.alloc((size_t)newm * 4)))
+            {
+                return rc;
+            }
+            dARawNd    = std::move(rnd);
+            dARawIdf   = std::move(ridf);
+            dARawKind  = std::move(rkind);
+            dAIdf      = std::move(idf);
+            dAKind     = std::move(kind);
+            dASummary  = std::move(sum);
+            assoc_mcap = newm;
+            assoc_m    = -1; // the old tables are gone
+        }
+        return CSLAM_OK;
+    }
+
+    int associate(const void* Z, int m, const void* Rv, double gate1, double gate2) override
+    {
+        if (m < 0 || m > 65535 || !Rv || (m > 0 && !Z)) // (one grid row per observation)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_associate: bad arguments (m=%d)", m);
+        }
+        if (!std::isfinite(gate1) || !std::isfinite(gate2))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_associate: gates must be finite (gate1=%g, gate2=%g)", gate1, gate2);
+        }
+        int rc = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        const int nchunks = (nf + kPfAssocFeatChunk - 1) / kPfAssocFeatChunk;
+        if (m > 0)
+        {
+            if ((rc = ensure_assoc(m, nchunks)) || (rc = stage(Z, m, nullptr)))
+            {
+                return rc;
+            }
+            const T*   R = static_cast<const T*>(Rv);
+            const int  pb = (np + 63) / 64;
+            if (nchunks > 0)
+            {
+                hipLaunchKernelGGL(pf_assoc_scan_kernel<T>, dim3(pb, nchunks, (m + kPfAssocObsChunk - 1) / kPfAssocObsChunk),
+                                   dim3(64), 0, stream, store(), dObs.get(), m, R[0], R[1], R[2], R[3], (T)gate1,
+                                   dAPartNd.get(), dAPartJ.get(), dAPartNis.get());
+                CSLAM_HIP_TRY(hipGetLastError());
+            }
+            hipLaunchKernelGGL(pf_assoc_merge_kernel<T>, dim3(pb, m), dim3(64), 0, stream, np, m, nchunks, dAPartNd.get(),
+                               dAPartJ.get(), dAPartNis.get(), (T)gate2, dARawIdf.get(), dARawKind.get(), dARawNd.get());
+            CSLAM_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(pf_assoc_resolve_kernel<T>, dim3(pb, m), dim3(64), 0, stream, np, m, dARawIdf.get(),
+                               dARawKind.get(), dARawNd.get(), dAIdf.get(), dAKind.get());
+            CSLAM_HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(pf_assoc_summary_kernel<T>, dim3(m), dim3(256), 0, stream, dW.get(), np, dAKind.get(),
+                               dASummary.get());
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        assoc_m     = m;
+        assoc_nf    = nf;
+        assoc_moved = false;
+        assoc_Z.clear();
+        if (m > 0)
+        {
+            assoc_Z.assign(static_cast<const char*>(Z), static_cast<const char*>(Z) + (size_t)2 * m * sizeof(T));
+        }
+        return CSLAM_OK;
+    }
+
+    int get_association(int* idf, int* kind, double* summary) override
+    {
+        if (assoc_m < 0)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_get_association: cslam_pf_associate has not been called");
+        }
+        int rc = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        const size_t cnt = (size_t)assoc_m * np;
+        if (idf && cnt)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(idf, dAIdf.get(), cnt * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (kind && cnt)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(kind, dAKind.get(), cnt * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (summary && assoc_m)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(summary, dASummary.get(), (size_t)assoc_m * 4 * sizeof(double),
+                                         hipMemcpyDeviceToHost, stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+
+    // the consumers take the observations of the last associate: anything else would pair a table with the wrong scan
+    int check_assoc_inputs(const void* Z, int m, const int* use, const char* who)
+    {
+        if (assoc_m < 0)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: cslam_pf_associate has not been called", who);
+        }
+        if (assoc_moved)
+        {
+            return fail(CSLAM_ERR_BAD_ARG,
+                        "%s: particles were resampled, unpacked or set since cslam_pf_associate (its table is per slot)", who);
+        }
+        if (m != assoc_m || (m > 0 && std::memcmp(assoc_Z.data(), Z, (size_t)2 * m * sizeof(T)) != 0))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: Z / m (%d) are not those of the last cslam_pf_associate (m=%d)", who, m,
+                        assoc_m);
+        }
+        if (nf < assoc_nf)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: the map shrank (%d features) since cslam_pf_associate (%d)", who, nf,
+                        assoc_nf);
+        }
+        for (int i = 0; i < m; i++)
+        {
+            if (use[i] != 0 && use[i] != 1)
+            {
+                return fail(CSLAM_ERR_BAD_ARG, "%s: use[%d]=%d is neither 0 nor 1", who, i, use[i]);
+            }
+        }
+        return CSLAM_OK;
+    }
+
+    int sample_proposal_assoc(const void* Z, int m, const void* Rv, const void* normals, const int* use,
+                              double miss_likelihood) override
+    {
+        if (m < 0 || !Rv || !normals || (m > 0 && (!Z || !use)) || !std::isfinite(miss_likelihood))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_assoc: bad arguments");
+        }
+        int rc = use_device();
+        // (the mask travels in the staging area's idf slot)
+        if (rc || (rc = check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc")) ||
+            (rc = stage(Z, m, use, normals, (size_t)3 * np * sizeof(T))))
+        {
+            return rc;
+        }
+        const T* R = static_cast<const T*>(Rv);
+        hipLaunchKernelGGL(pf_sample_proposal_assoc_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
+                           store(), dObs.get(), dAIdf.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(),
+                           (T)miss_likelihood, (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 1 : 2);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+
+    int feature_update_assoc(const void* Z, int m, const void* Rv, const int* use) override
+    {
+        if (m < 0 || !Rv || (m > 0 && (!Z || !use)))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_feature_update_assoc: bad arguments");
+        }
+        int rc = use_device();
+        if (rc || (rc = check_assoc_inputs(Z, m, use, "pf_feature_update_assoc")))
+        {
+            return rc;
+        }
+        if (m == 0)
+        {
+            return CSLAM_OK;
+        }
+        if ((rc = stage(Z, m, use)))
+        {
+            return rc;
+        }
+        const T* R = static_cast<const T*>(Rv);
+        hipLaunchKernelGGL(pf_feature_update_assoc_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(),
+                           dObs.get(), dAIdf.get(), dIdf(), m, R[0], R[1], R[2], R[3],
+                           (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
 };
 
 inline PfBase* B(cslam_pf_t h)
@@ -1707,6 +1942,17 @@ int cslam_pf_synchronize(cslam_pf_t h)
     CSLAM_NEED(h);
     CSLAM_HIP_TRY(hipSetDevice(B(h)->device));
     CSLAM_HIP_TRY(hipStreamSynchronize(B(h)->stream));
+    return CSLAM_OK;
+}
+
+int cslam_pf_get_stream(cslam_pf_t h, void** stream)
+{
+    CSLAM_NEED(h);
+    if (!stream)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pf_get_stream: null");
+    }
+    *stream = reinterpret_cast<void*>(B(h)->stream);
     return CSLAM_OK;
 }
 
@@ -2032,6 +2278,35 @@ int cslam_pf_get_all_features(cslam_pf_t h, void* XF_all)
 {
     CSLAM_NEED(h);
     return B(h)->get_all_features(XF_all);
+}
+
+/* EKF.cpp:131-144, 235-326 on every particle's own state */
+int cslam_pf_associate(cslam_pf_t h, const void* Z, int m, const void* R, double gate1, double gate2)
+{
+    CSLAM_NEED(h);
+    return B(h)->associate(Z, m, R, gate1, gate2);
+}
+
+/* the tables of the last associate (EKF.cpp:131-144, 235-326 per particle) */
+int cslam_pf_get_association(cslam_pf_t h, int* idf_host, int* kind_host, double* summary_host)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_association(idf_host, kind_host, summary_host);
+}
+
+/* PF.cpp:502-544 + 222-277 with every particle's own correspondences (EKF.cpp:131-144, 235-326) */
+int cslam_pf_sample_proposal_assoc(cslam_pf_t h, const void* Z, int m, const void* R, const void* normals, const int* use,
+                                   double miss_likelihood)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_proposal_assoc(Z, m, R, normals, use, miss_likelihood);
+}
+
+/* PF.cpp:222-277 alone with every particle's own correspondences (EKF.cpp:131-144, 235-326) */
+int cslam_pf_feature_update_assoc(cslam_pf_t h, const void* Z, int m, const void* R, const int* use)
+{
+    CSLAM_NEED(h);
+    return B(h)->feature_update_assoc(Z, m, R, use);
 }
 
 int cslam_pf_best_particle_sharded(cslam_pf_t h, cslam_comm_t comm, int pick, long long* global_index, void* w, void* Xv,

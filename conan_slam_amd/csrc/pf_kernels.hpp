@@ -691,6 +691,10 @@ __device__ inline void pf_feature_kf(const T* xf, const T* pf, const T* HF, cons
 
 constexpr int kPfSubLanes = 8; // lanes per particle in pf_sample_proposal_kernel (= its observation chunk)
 
+// (pf_assoc_kernels.hpp holds siblings of the next two kernels that read a per-particle correspondence table,
+// pf_sample_proposal_assoc_kernel and pf_feature_update_assoc_kernel: a change to the arithmetic or its order here must
+// be mirrored there -- tests/test_pf_assoc_gpu.py holds the two bit for bit on uniform tables)
+
 template <typename T>
 __global__ void __launch_bounds__(64) pf_sample_proposal_kernel(PfStore<T> s, const T* __restrict__ Z,
                                                                  const int* __restrict__ idf, int m, T r00, T r10, T r01,

@@ -235,6 +235,12 @@ class ParticleShard:
     def synchronize(self):
         check(self._L.cslam_pf_synchronize(self._h))
 
+    def stream_ptr(self) -> int:
+        """The hipStream_t every call of this shard is ordered on (e.g. for torch.cuda.ExternalStream and timing events)."""
+        p = C.c_void_p(None)
+        check(self._L.cslam_pf_get_stream(self._h, C.byref(p)))
+        return p.value
+
     # ---- the per-particle path (every owned particle)
     def predict(self, v, swa, Q, wb, dt):
         """PF::predict -- PF.cpp:419-471."""
@@ -265,6 +271,49 @@ class ParticleShard:
         """PF::addOneNewFeature -- PF.cpp:9-60."""
         Zc, q = self._z(Z)
         check(self._L.cslam_pf_add_features(self._h, _vp(Zc), C.c_int(q), _vp(self._m22(R))))
+
+    # ---- unknown correspondences: every particle carries its own association (EKF.cpp:131-144, 235-326 per particle)
+    def associate(self, Z, R, gate1, gate2):
+        """Gated nearest-neighbour association of the observations Z (2 x m) against every particle's own map
+        (cslam_pf_associate).  Fills the shard's device tables; asynchronous.  See association()."""
+        Zc, m = self._z(Z)
+        self._assoc_m = None  # (a refused call leaves nothing this wrapper can size its buffers from)
+        check(self._L.cslam_pf_associate(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)), C.c_double(float(gate1)),
+                                         C.c_double(float(gate2))))
+        self._assoc_m = m
+
+    def association(self):
+        """-> (idf, kind, summary) of the last associate(): idf and kind are m x n_local int32 (idf 1-based, 0 = none;
+        kind 1 matched, 2 new, 0 ambiguous), summary is m x 4 float64 = (sum w matched, sum w new, sum w ambiguous,
+        number of particles matched) over THIS shard's particles."""
+        m = getattr(self, "_assoc_m", None)
+        if m is None:
+            check(self._L.cslam_pf_get_association(self._h, None, None, None))  # raises if associate was never called
+            raise _capi.CslamError(_capi.ERR_BAD_ARG, "association(): the last associate() on this shard was refused")
+        idf = np.zeros((m, self.n_local), np.int32)
+        kind = np.zeros((m, self.n_local), np.int32)
+        summary = np.zeros((m, 4), np.float64)
+        check(self._L.cslam_pf_get_association(self._h, _vp(idf), _vp(kind), _vp(summary)))
+        return idf, kind, summary
+
+    def sample_proposal_assoc(self, Z, R, normals, use=None, miss_likelihood=1.0):
+        """PF::sampleProposal + PF::featureUpdate where every particle takes its correspondences from the table of the
+        last associate(Z, ...).  use: m flags (default all 1), 0 = nobody sees that observation; a particle without a
+        match for a used observation multiplies its weight by miss_likelihood instead."""
+        Zc, m = self._z(Z)
+        use = np.ones(m, np.int32) if use is None else np.ascontiguousarray(use, dtype=np.int32)
+        assert use.shape[0] == m
+        nrm = np.ascontiguousarray(np.asarray(normals, dtype=self.dtype).reshape(3, self.n_local))
+        check(self._L.cslam_pf_sample_proposal_assoc(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)), _vp(nrm),
+                                                     _vp(use) if m else None, C.c_double(float(miss_likelihood))))
+
+    def feature_update_assoc(self, Z, R, use=None):
+        """PF::featureUpdate alone from the table of the last associate(Z, ...) (the unfused form)."""
+        Zc, m = self._z(Z)
+        use = np.ones(m, np.int32) if use is None else np.ascontiguousarray(use, dtype=np.int32)
+        assert use.shape[0] == m
+        check(self._L.cslam_pf_feature_update_assoc(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)),
+                                                    _vp(use) if m else None))
 
     # ---- pieces of the resample step
     def weight_sums(self) -> Tuple[float, float]:
@@ -511,3 +560,32 @@ def resample_particles(shard, comm, n_effective: int, resample_status: bool, sel
     shard.unpack(recv_dst, recv)
     shard.set_uniform_weight(1.0 / n)                 # PF.cpp:495
     return neff, True
+
+
+# ------------------------------------------------------------------------------------------------
+# what to do with the association: a policy, and it lives on the host
+# ------------------------------------------------------------------------------------------------
+def new_feature_votes(summary: np.ndarray, new_fraction: float = 0.5) -> np.ndarray:
+    """Per observation: does the weight mass of the particles that call it NEW reach new_fraction of the whole?
+    summary: m x 4 as ParticleShard.association() returns it (a sharded caller passes the sum over the shards).
+    An observation nobody calls new, or a set without weight mass, is never new (whatever new_fraction is)."""
+    summary = np.asarray(summary, dtype=np.float64).reshape(-1, 4)
+    total = summary[:, :3].sum(axis=1)
+    return (total > 0) & (summary[:, 1] > 0) & (summary[:, 1] >= new_fraction * total)
+
+
+def data_associate(shard, Z, R, gate1, gate2, new_fraction: float = 0.5):
+    """One policy for a FastSLAM-2 step with unknown correspondences -> (use, ZN).
+
+    The C ABI supplies the mechanism only (cslam_pf_associate and the consumers that read its table); which
+    observations become new features is decided HERE, on the host, because the feature index space is shared by all
+    particles: observation j is declared new, for every particle, when summary[j].new / sum w >= new_fraction.  Then
+    use[j] = 0 (no particle updates from it) and its column goes to ZN for add_features after the resample; every other
+    observation keeps use[j] = 1, and a particle that has no match for it pays miss_likelihood in sample_proposal_assoc."""
+    shard.associate(Z, R, gate1, gate2)
+    _, _, summary = shard.association()
+    Z = np.asarray(Z, dtype=shard.dtype)
+    Z = Z.reshape(2, -1, order="F") if Z.size else np.zeros((2, 0), shard.dtype)
+    new = new_feature_votes(summary, new_fraction) if summary.shape[0] else np.zeros(0, bool)
+    use = np.where(new, 0, 1).astype(np.int32)
+    return use, np.asfortranarray(Z[:, new])

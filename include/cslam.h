@@ -354,6 +354,11 @@ int cslam_pf_create(int n_particles, int max_features, int dtype, int device, in
 int cslam_pf_destroy(cslam_pf_t h);
 int cslam_pf_synchronize(cslam_pf_t h);
 int cslam_pf_get_counts(cslam_pf_t h, int* n_particles, int* n_features);
+/* The stream every call of this handle is ordered on (a hipStream_t).  The handle owns it and destroys it with
+ * cslam_pf_destroy.  A caller MAY record events on it (timing around calls), make other streams wait for such events,
+ * and synchronise it.  A caller MUST NOT enqueue kernels or copies on it that touch the handle's buffers, capture it
+ * into a graph, or destroy it. */
+int cslam_pf_get_stream(cslam_pf_t h, void** stream);
 
 /* set every particle's weight to w0 (PF.cpp:327 uses 1/N of the GLOBAL particle count) */
 int cslam_pf_set_uniform_weight(cslam_pf_t h, double w0);
@@ -381,6 +386,36 @@ int cslam_pf_feature_update(cslam_pf_t h, const void* Z, int m, const int* idf, 
 
 /* Replaces PF::addOneNewFeature(particle, Z, R) for every owned particle -- slam.h:134, PF.cpp:9-60. */
 int cslam_pf_add_features(cslam_pf_t h, const void* Z, int q, const void* R);
+
+/* ---- observations whose correspondence is unknown: every particle carries its own association hypothesis ----
+ * Gated nearest-neighbour association of m observations against the map of EVERY owned particle: the measure of
+ * EKF::computeAssociation and the rule of dataAssociate (EKF.cpp:131-144, 235-326) on the particle's own state, whose
+ * covariance is blockdiag(Pv, PF_f): S = HV Pv HV^T + HF PF_f HF^T + R (all four entries of R are read),
+ * nis = v^T S^-1 v, nd = nis + log det S.  For particle p and observation j: kind 1 and idf = the lowest-index feature
+ * with the smallest nd among those with nis < gate1; else idf 0 and kind 2 when the smallest nis exceeds gate2 (a new
+ * feature), kind 0 otherwise (ambiguous).  Comparisons are strict; a NaN takes part in none; an empty map gives kind 2.
+ * Afterwards no two observations of one particle hold the same feature: the smallest nd keeps it (the lower observation
+ * index on equal nd), the others become idf 0 / kind 0.  Fills the handle's device tables idf[m][np], kind[m][np]
+ * (particle index fastest) and summary[m][4] = (sum of w over the particles of kind 1, of kind 2, of kind 0, number of
+ * particles of kind 1), sums in double over THIS handle's particles (a sharded caller adds the shards' summaries).
+ * Asynchronous like the other per-particle calls; returns nothing to the host. */
+int cslam_pf_associate(cslam_pf_t h, const void* Z, int m, const void* R, double gate1, double gate2);
+/* The tables of the last cslam_pf_associate (EKF.cpp:131-144, 235-326): idf_host and kind_host m * n_particles ints,
+ * summary_host m * 4 doubles; any of the three may be NULL.  Synchronises. */
+int cslam_pf_get_association(cslam_pf_t h, int* idf_host, int* kind_host, double* summary_host);
+/* PF::sampleProposal with PF::featureUpdate at the sampled pose (PF.cpp:502-544, 222-277) where particle p takes the
+ * correspondence of observation j from the table of the last cslam_pf_associate (EKF.cpp:131-144, 235-326).  Z and m
+ * must be those of that call, and the particles must not have changed slots in between (resample, gather, unpack,
+ * set_particle, observation_step): the table is indexed by particle slot.  Either violation is CSLAM_ERR_BAD_ARG.
+ * use: m ints (host), 0 or 1.  use[j] = 0: no particle sees observation j (the caller adds it as a new feature).
+ * use[j] = 1 and idf != 0: the arithmetic of cslam_pf_sample_proposal + cslam_pf_feature_update in their order.
+ * use[j] = 1 and idf == 0: no pose or feature update; the particle's likelihood product takes the factor
+ * miss_likelihood (FastSLAM's new-feature likelihood) at observation j's place. */
+int cslam_pf_sample_proposal_assoc(cslam_pf_t h, const void* Z, int m, const void* R, const void* normals, const int* use,
+                                   double miss_likelihood);
+/* PF::featureUpdate alone (PF.cpp:222-277) from the table of the last cslam_pf_associate (EKF.cpp:131-144, 235-326) and
+ * the same mask: the unfused form, for a caller that has moved the poses with cslam_pf_sample_proposal itself. */
+int cslam_pf_feature_update_assoc(cslam_pf_t h, const void* Z, int m, const void* R, const int* use);
 
 /* ---- the resample step (PF.cpp:473-500, 546-577), split so that a multi-GPU driver can put its
  *      collectives between the pieces; see INTEGRATION.md ---- */
