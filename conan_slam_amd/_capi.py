@@ -92,6 +92,28 @@ PF_ASSOC_SYMBOLS = tuple(k for k in _PROTOTYPES if k.startswith("cslam_pf_") and
 PF_ASSOC_FEAT_CHUNK, PF_ASSOC_OBS_CHUNK = 32, 8  # kPfAssocFeatChunk / kPfAssocObsChunk of csrc/pf_assoc_kernels.hpp
 
 
+# The particle filter's random inputs drawn on the device (slam.h:753-764, PF.cpp:557, 579-596) and the calls that consume
+# them; cslam_pf_stage_copies counts the staged host-to-device copies of a handle.
+_PROTOTYPES.update({
+    "cslam_pf_seed_draws": [C.c_void_p, C.c_longlong, C.c_longlong, C.c_longlong],
+    "cslam_pf_get_draws": [C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p],
+    "cslam_pf_sample_proposal_drawn": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong],
+    "cslam_pf_sample_proposal_assoc_drawn": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
+                                             C.c_longlong],
+    "cslam_pf_resample_local_drawn": [C.c_void_p, C.c_longlong, C.c_double, C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_int)],
+    "cslam_pf_resample_sharded_drawn": [C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_int, C.POINTER(C.c_double),
+                                        C.POINTER(C.c_int)],
+    "cslam_pf_observation_step_drawn": [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_double, C.c_int],
+    "cslam_pf_stage_copies": [C.c_void_p, C.POINTER(C.c_longlong)],
+})
+PF_DRAW_SYMBOLS = ("cslam_pf_seed_draws", "cslam_pf_get_draws", "cslam_pf_sample_proposal_drawn",
+                   "cslam_pf_sample_proposal_assoc_drawn", "cslam_pf_resample_local_drawn",
+                   "cslam_pf_resample_sharded_drawn", "cslam_pf_observation_step_drawn", "cslam_pf_stage_copies")
+PF_DRAW_OBS_MAX = 32  # kPfDrawObsMax of csrc/pf_draw_kernels.hpp: observations that travel as kernel arguments
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
     text = open(header_path).read()

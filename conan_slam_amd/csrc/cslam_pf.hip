@@ -20,6 +20,7 @@
 #include "cslam_common.hpp"
 #include "device_owners.hpp"
 #include "pf_assoc_kernels.hpp"
+#include "pf_draw_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
 
@@ -375,6 +376,17 @@ struct PfBase
     virtual int sample_proposal_assoc(const void* Z, int m, const void* R, const void* normals, const int* use,
                                       double miss_likelihood)                                                       = 0;
     virtual int feature_update_assoc(const void* Z, int m, const void* R, const int* use)                           = 0;
+    // the random inputs drawn on the device (pf_draw_kernels.hpp) and the calls that consume them
+    virtual int seed_draws(long long seed, long long first_global, long long n_global)                              = 0;
+    virtual int get_draws(long long step, void* normals, void* select)                                              = 0;
+    virtual int sample_proposal_drawn(const void* Z, int m, const int* idf, const void* R, long long step)          = 0;
+    virtual int sample_proposal_assoc_drawn(const void* Z, int m, const void* R, const int* use, double miss_likelihood,
+                                            long long step)                                                         = 0;
+    virtual int resample_local_drawn(long long step, double n_eff, int status, double* neff, int* did)              = 0;
+    virtual int resample_sharded_drawn(Comm* c, long long step, double n_eff, int status, double* neff, int* did)   = 0;
+    virtual int observation_step_drawn(double v, double swa, const void* Q, double wb, double dt, const void* Z, int m,
+                                       const int* idf, const void* R, long long step, double n_eff, int status)     = 0;
+    virtual int get_stage_copies(long long* copies)                                                                 = 0;
 };
 
 template <typename T>
@@ -399,6 +411,7 @@ struct Pf : PfBase
     int               stage_inflight = 0;
     Event             stage_ev[kStageSlots]; // created (and recorded) by the first copy out of the slot
     int               stage_last = 0; // slot handed out by the last stage_slot_for()
+    long long         stage_copies = 0; // host-to-device copy commands enqueued for per-step inputs (stage_commit)
     std::vector<char> staged; // Z || idf bytes currently in dObs (empty = unknown)
     PinnedBuf<double> hInfo;
 
@@ -462,6 +475,7 @@ struct Pf : PfBase
             CSLAM_TRY(stage_ev[stage_last].create(hipEventDisableTiming));
         }
         CSLAM_HIP_TRY(hipEventRecord(stage_ev[stage_last].get(), stream));
+        stage_copies++;
         return CSLAM_OK;
     }
 
@@ -937,6 +951,12 @@ struct Pf : PfBase
         {
             return rc;
         }
+        return resample_result(neff, did);
+    }
+
+    // {Neff, resampled} of the resample just launched, when the caller asks for either
+    int resample_result(double* neff, int* did)
+    {
         if (neff || did)
         {
             CSLAM_HIP_TRY(hipMemcpyAsync(hInfo.get(), dInfo.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
@@ -1022,6 +1042,32 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_resample_sharded: null communicator or select");
         }
+        return resample_sharded_from(c, select, 0, n_eff, status, neff, did);
+    }
+
+    int resample_sharded_drawn(Comm* c, long long step, double n_eff, int status, double* neff, int* did) override
+    {
+        if (!c)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_resample_sharded_drawn: null communicator");
+        }
+        int rc = need_draws("pf_resample_sharded_drawn");
+        if (rc)
+        {
+            return rc;
+        }
+        if (draw_nglobal != (long long)c->world * np || draw_first != (long long)c->rank * np)
+        {
+            return fail(CSLAM_ERR_BAD_ARG,
+                        "pf_resample_sharded_drawn: the draws were seeded for slots %lld.. of %lld, rank %d of %d holds %lld.. of %lld",
+                        draw_first, draw_nglobal, c->rank, c->world, (long long)c->rank * np, (long long)c->world * np);
+        }
+        return resample_sharded_from(c, nullptr, step, n_eff, status, neff, did);
+    }
+
+    // select != nullptr: the caller's strata positions (one staged copy); nullptr: those of `step`, drawn into dSelG
+    int resample_sharded_from(Comm* c, const void* select, long long step, double n_eff, int status, double* neff, int* did)
+    {
         if (!c->loop && !rccl())
         {
             return fail(CSLAM_ERR_HIP, "pf_resample_sharded: librccl could not be loaded");
@@ -1035,14 +1081,21 @@ struct Pf : PfBase
         }
         const ncclDataType_t dt = (sizeof(T) == 4) ? ncclFloat : ncclDouble;
         // the strata positions go to the device up front as well (staging can fail; the copy is cheap when unused)
-        char* slot = nullptr;
-        if ((rc = stage_slot_for((size_t)N * sizeof(T), &slot)))
+        if (select)
         {
-            return rc;
+            char* slot = nullptr;
+            if ((rc = stage_slot_for((size_t)N * sizeof(T), &slot)))
+            {
+                return rc;
+            }
+            std::memcpy(slot, select, (size_t)N * sizeof(T));
+            CSLAM_HIP_TRY(hipMemcpyAsync(dSelG.get(), slot, (size_t)N * sizeof(T), hipMemcpyHostToDevice, stream));
+            if ((rc = stage_commit()))
+            {
+                return rc;
+            }
         }
-        std::memcpy(slot, select, (size_t)N * sizeof(T));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dSelG.get(), slot, (size_t)N * sizeof(T), hipMemcpyHostToDevice, stream));
-        if ((rc = stage_commit()))
+        else if ((rc = launch_draw(step, nullptr, dSelG.get(), N, 0, nullptr, nullptr)))
         {
             return rc;
         }
@@ -1287,6 +1340,14 @@ struct Pf : PfBase
         {
             return rc;
         }
+        return launch_observation_step(v, swa, Qv, wb, dt, m, idf, Rv, n_eff, status);
+    }
+
+    // the launches of one observation step behind its inputs in dObs (Z | idf | normals | select); idf: the host copy
+    int launch_observation_step(double v, double swa, const void* Qv, double wb, double dt, int m, const int* idf,
+                                const void* Rv, double n_eff, int status)
+    {
+        const size_t off_sel = off_normals() + (size_t)3 * np * sizeof(T);
         char*      base = reinterpret_cast<char*>(dObs.get());
         const T*   sZ   = reinterpret_cast<const T*>(base);
         const int* sIdf = reinterpret_cast<const int*>(base + off_idf());
@@ -1867,6 +1928,266 @@ struct Pf : PfBase
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
+
+    // ------------------------------------------------------------------------------------------------
+    // The random inputs drawn on the device (pf_draw_kernels.hpp).  A _drawn call is its host-array twin with ONE
+    // producer launch in place of the caller's normals / select: pf_stage_draw_kernel fills the staging area in the
+    // layout the consumers read, and these are launched behind it with the arguments they always get.  Up to
+    // kPfDrawObsMax observations Z / idf ride along as kernel arguments (no copy command at all); more take the staged copy.
+    // ------------------------------------------------------------------------------------------------
+    bool               draw_seeded  = false;
+    unsigned long long draw_seed    = 0;
+    long long          draw_first   = 0; // global slot of this handle's particle 0
+    long long          draw_nglobal = 0; // particles of the whole set = strata of the resample
+    T                  draw_k       = (T)0; // 1 / n_global in T (stratified_random's k)
+    DevBuf<T>          dDrawDi;  // [n_global, none beyond 2^31 - 1] k/2, +k, +k, ...: the running sum of stratified_random, in T and in index order
+    DevBuf<T>          dDrawOut; // [3 np + n_global] what cslam_pf_get_draws brings back (never the staging area)
+
+    int seed_draws(long long seed, long long first_global, long long n_global) override
+    {
+        if (first_global < 0 || n_global >= (1LL << 32) || first_global > n_global - np)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_seed_draws: need 0 <= first_global, first_global + %d <= n_global < 2^32 (got %lld, %lld)",
+                        np, first_global, n_global);
+        }
+        int rc = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        // One launch draws at most 2^31 - 1 strata (and every resample form counts its particles in an int): a larger
+        // set gets its normals -- the keys reach slot 2^32 - 1 -- and no strata table.
+        const long long n_strata = (n_global <= 0x7fffffffLL) ? n_global : 0;
+        // all-or-nothing (device_owners.hpp): new buffers into locals first, members replaced only when all exist
+        DevBuf<T>      di, out;
+        std::vector<T> h;
+        try
+        {
+            h.resize((size_t)n_strata);
+        }
+        catch (const std::bad_alloc&)
+        {
+            return fail(CSLAM_ERR_ALLOC, "pf_seed_draws: out of host memory for %lld strata", n_global);
+        }
+        if ((rc = di.alloc((size_t)std::max(n_strata, 1LL))) || (rc = out.alloc((size_t)3 * np + (size_t)n_strata)))
+        {
+            return rc;
+        }
+        const T k = (T)1 / (T)n_global; // PF.cpp:579-596, as pf.py's stratified_random rounds it
+        T       acc = k / (T)2;
+        for (long long i = 0; i < n_strata; i++)
+        {
+            h[(size_t)i] = acc;
+            acc          = acc + k;
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still reads the old table
+        if (n_strata > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(di.get(), h.data(), (size_t)n_strata * sizeof(T), hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        }
+        dDrawDi      = std::move(di);
+        dDrawOut     = std::move(out);
+        draw_seed    = (unsigned long long)seed;
+        draw_first   = first_global;
+        draw_nglobal = n_global;
+        draw_k       = k;
+        draw_seeded  = true;
+        return CSLAM_OK;
+    }
+
+    int need_draws(const char* who)
+    {
+        if (!draw_seeded)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: cslam_pf_seed_draws has not been called", who);
+        }
+        return CSLAM_OK;
+    }
+    int need_whole_set(const char* who)
+    {
+        int rc = need_draws(who);
+        if (rc == CSLAM_OK && (draw_first != 0 || draw_nglobal != np))
+        {
+            rc = fail(CSLAM_ERR_BAD_ARG, "%s: the draws were seeded for slots %lld.. of %lld, this handle resamples its own %d",
+                      who, draw_first, draw_nglobal, np);
+        }
+        return rc;
+    }
+
+    // normals (3 np, or nullptr), select (n_sel strata, or nullptr with n_sel = 0) of `step`, and -- m > 0 -- Z | idf into
+    // the staging area from the kernel's own arguments
+    int launch_draw(long long step, T* normals, T* select, int n_sel, int m, const void* Z, const int* idf)
+    {
+        PfDrawObs<T> obs;
+        std::memset(&obs, 0, sizeof(obs));
+        if (m > 0)
+        {
+            std::memcpy(obs.z, Z, (size_t)2 * m * sizeof(T));
+            std::memcpy(obs.idf, idf, (size_t)m * sizeof(int));
+        }
+        const int nn = normals ? np : 0;
+        const int lanes = std::max(std::max(nn, n_sel), std::max(2 * m, 1));
+        hipLaunchKernelGGL(pf_stage_draw_kernel<T>, dim3((lanes + 255) / 256), dim3(256), 0, stream, draw_seed,
+                           (unsigned long long)step, (unsigned long long)draw_first, normals, nn, select, dDrawDi.get(),
+                           n_sel, draw_k, dObs.get(), dIdf(), m, obs);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+
+    // Z | idf (or the use[] mask) of a proposal call and the normals of `step` into the staging area
+    int stage_drawn(const void* Z, int m, const int* idf, long long step)
+    {
+        int rc = ensure_m(m);
+        if (rc)
+        {
+            return rc;
+        }
+        if (m > kPfDrawObsMax)
+        {
+            if ((rc = stage(Z, m, idf)))
+            {
+                return rc;
+            }
+            return launch_draw(step, dNormals(), nullptr, 0, 0, nullptr, nullptr);
+        }
+        staged.clear();
+        if ((rc = launch_draw(step, dNormals(), nullptr, 0, m, Z, idf)))
+        {
+            return rc;
+        }
+        if (m > 0) // (what stage() remembers: a feature update right behind sends nothing)
+        {
+            const size_t zb = (size_t)2 * m * sizeof(T), ib = (size_t)m * sizeof(int);
+            staged.resize(zb + ib);
+            std::memcpy(staged.data(), Z, zb);
+            std::memcpy(staged.data() + zb, idf, ib);
+        }
+        return CSLAM_OK;
+    }
+
+    int get_draws(long long step, void* normals, void* select) override
+    {
+        int rc = need_draws("pf_get_draws");
+        if (rc || (rc = use_device()))
+        {
+            return rc;
+        }
+        if (select && draw_nglobal > 0x7fffffffLL)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_get_draws: a set of %lld has no strata (at most 2^31 - 1), only normals", draw_nglobal);
+        }
+        T* dn = dDrawOut.get();
+        T* ds = dn + (size_t)3 * np;
+        if ((rc = launch_draw(step, normals ? dn : nullptr, select ? ds : nullptr, select ? (int)draw_nglobal : 0, 0, nullptr,
+                              nullptr)))
+        {
+            return rc;
+        }
+        if (normals)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(normals, dn, (size_t)3 * np * sizeof(T), hipMemcpyDeviceToHost, stream));
+        }
+        if (select)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(select, ds, (size_t)draw_nglobal * sizeof(T), hipMemcpyDeviceToHost, stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+
+    int sample_proposal_drawn(const void* Z, int m, const int* idf, const void* Rv, long long step) override
+    {
+        if (m < 0 || !Rv || (m > 0 && (!Z || !idf)))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_drawn: bad arguments");
+        }
+        int rc = need_draws("pf_sample_proposal_drawn");
+        if (rc || (rc = use_device()) || (rc = check_idf(idf, m, "pf_sample_proposal_drawn")) ||
+            (rc = stage_drawn(Z, m, idf, step)))
+        {
+            return rc;
+        }
+        const T* R = static_cast<const T*>(Rv);
+        hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
+                           store(), dObs.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(), PfPredict<T>{0, (T)0,
+                           (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0}, 0);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+
+    int sample_proposal_assoc_drawn(const void* Z, int m, const void* Rv, const int* use, double miss_likelihood,
+                                    long long step) override
+    {
+        if (m < 0 || !Rv || (m > 0 && (!Z || !use)) || !std::isfinite(miss_likelihood))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_assoc_drawn: bad arguments");
+        }
+        int rc = need_draws("pf_sample_proposal_assoc_drawn");
+        // (the mask travels in the staging area's idf slot)
+        if (rc || (rc = use_device()) || (rc = check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc_drawn")) ||
+            (rc = stage_drawn(Z, m, use, step)))
+        {
+            return rc;
+        }
+        const T* R = static_cast<const T*>(Rv);
+        hipLaunchKernelGGL(pf_sample_proposal_assoc_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
+                           store(), dObs.get(), dAIdf.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(),
+                           (T)miss_likelihood, (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 1 : 2);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+
+    int resample_local_drawn(long long step, double n_eff, int status, double* neff, int* did) override
+    {
+        int rc = need_whole_set("pf_resample_local_drawn");
+        if (rc || (rc = use_device()) || (rc = ensure_resample_buffers()) ||
+            (rc = launch_draw(step, nullptr, dSel.get(), np, 0, nullptr, nullptr)) ||
+            (rc = launch_resample(dSel.get(), n_eff, status)))
+        {
+            return rc;
+        }
+        return resample_result(neff, did);
+    }
+
+    // cslam_pf_observation_step with launches only: the producer writes normals | select (and Z | idf up to
+    // kPfDrawObsMax observations) where the staged copy of the host-array form puts them
+    int observation_step_drawn(double v, double swa, const void* Qv, double wb, double dt, const void* Z, int m,
+                               const int* idf, const void* Rv, long long step, double n_eff, int status) override
+    {
+        if (!Qv || !Rv || m < 0 || (m > 0 && (!Z || !idf)))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_observation_step_drawn: bad arguments");
+        }
+        int rc = need_whole_set("pf_observation_step_drawn");
+        if (rc || (rc = use_device()) || (rc = check_idf(idf, m, "pf_observation_step_drawn")) ||
+            (rc = ensure_m(std::max(m, 1))) || (rc = ensure_resample_buffers()))
+        {
+            return rc;
+        }
+        staged.clear();
+        const bool by_copy = m > kPfDrawObsMax;
+        if (by_copy && (rc = stage(Z, m, idf)))
+        {
+            return rc;
+        }
+        T* nrm = dNormals();
+        if ((rc = launch_draw(step, m > 0 ? nrm : nullptr, nrm + (size_t)3 * np, np, by_copy ? 0 : m, Z, idf)))
+        {
+            return rc;
+        }
+        return launch_observation_step(v, swa, Qv, wb, dt, m, idf, Rv, n_eff, status);
+    }
+
+    int get_stage_copies(long long* copies) override
+    {
+        if (!copies)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_stage_copies: null");
+        }
+        *copies = stage_copies;
+        return CSLAM_OK;
+    }
 };
 
 inline PfBase* B(cslam_pf_t h)
@@ -2307,6 +2628,63 @@ int cslam_pf_feature_update_assoc(cslam_pf_t h, const void* Z, int m, const void
 {
     CSLAM_NEED(h);
     return B(h)->feature_update_assoc(Z, m, R, use);
+}
+
+/* slam.h:587-594: the seed of every draw the _drawn calls make */
+int cslam_pf_seed_draws(cslam_pf_t h, long long seed, long long first_global, long long n_global)
+{
+    CSLAM_NEED(h);
+    return B(h)->seed_draws(seed, first_global, n_global);
+}
+
+/* slam.h:753-764 and PF.cpp:557, 579-596 of one step, read back */
+int cslam_pf_get_draws(cslam_pf_t h, long long step, void* normals, void* select)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_draws(step, normals, select);
+}
+
+/* PF.cpp:502-544 with the normals of slam.h:753-764 drawn on the device */
+int cslam_pf_sample_proposal_drawn(cslam_pf_t h, const void* Z, int m, const int* idf, const void* R, long long step)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_proposal_drawn(Z, m, idf, R, step);
+}
+
+int cslam_pf_sample_proposal_assoc_drawn(cslam_pf_t h, const void* Z, int m, const void* R, const int* use,
+                                         double miss_likelihood, long long step)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_proposal_assoc_drawn(Z, m, R, use, miss_likelihood, step);
+}
+
+/* PF.cpp:473-500 with the strata of PF.cpp:557, 579-596 drawn on the device */
+int cslam_pf_resample_local_drawn(cslam_pf_t h, long long step, double n_effective, int resample_status, double* neff,
+                                  int* resampled)
+{
+    CSLAM_NEED(h);
+    return B(h)->resample_local_drawn(step, n_effective, resample_status, neff, resampled);
+}
+
+int cslam_pf_resample_sharded_drawn(cslam_pf_t h, cslam_comm_t comm, long long step, double n_effective,
+                                    int resample_status, double* neff, int* resampled)
+{
+    CSLAM_NEED(h);
+    return B(h)->resample_sharded_drawn(reinterpret_cast<Comm*>(comm), step, n_effective, resample_status, neff, resampled);
+}
+
+int cslam_pf_observation_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt,
+                                    const void* Z, int m, const int* idf, const void* R, long long step,
+                                    double n_effective, int resample_status)
+{
+    CSLAM_NEED(h);
+    return B(h)->observation_step_drawn(v, swa, Q, wb, dt, Z, m, idf, R, step, n_effective, resample_status);
+}
+
+int cslam_pf_stage_copies(cslam_pf_t h, long long* copies)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_stage_copies(copies);
 }
 
 int cslam_pf_best_particle_sharded(cslam_pf_t h, cslam_comm_t comm, int pick, long long* global_index, void* w, void* Xv,

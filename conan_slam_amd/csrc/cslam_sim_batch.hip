@@ -20,6 +20,7 @@
 #include <new>
 #include <vector>
 
+#include "counter_rng.hpp"
 #include "cslam_common.hpp"
 #include "device_owners.hpp"
 #include "device_math.hpp"
@@ -65,23 +66,7 @@ __global__ void __launch_bounds__(kSimThreads) sim_batch_scan_kernel(const float
     }
 }
 
-// the counter-based standard normal of synth.py: splitmix64(seed, idx) -> 53-bit uniforms -> Box-Muller, in f64
-__device__ inline unsigned long long splitmix64(unsigned long long seed, unsigned long long idx)
-{
-    unsigned long long z = seed * 0x9E3779B97F4A7C15ull + idx + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ inline double uniform01(unsigned long long seed, unsigned long long idx)
-{
-    return (double)(splitmix64(seed, idx) >> 11) * (1.0 / 9007199254740992.0);
-}
-__device__ inline double counter_normal(unsigned long long seed, unsigned long long idx)
-{
-    const double u1 = uniform01(seed, 2ull * idx), u2 = uniform01(seed, 2ull * idx + 1ull);
-    return sqrt(-2.0 * log(1.0 - u1)) * cos((2.0 * kPi) * u2);
-}
+// (the counter-based standard normal of synth.py the noise is drawn from: counter_rng.hpp)
 
 // slam.h:168-178: z0 + g * s with the product and the sum rounded separately, as the reference's f32 code rounds them
 // (the compiler's default contraction would fuse them into one multiply-add with a single rounding)

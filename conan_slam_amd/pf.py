@@ -402,6 +402,74 @@ class ParticleShard:
                                                 _vp(idf) if m else None, _vp(self._m22(R)), _vp(nrm), _vp(sel),
                                                 C.c_double(float(n_effective)), C.c_int(1 if resample_status else 0)))
 
+    # ---- the random inputs drawn on the device (synth.pf_draw_normals / pf_draw_select restate them)
+    def seed_draws(self, seed: int, first_global: int = 0, n_global: int | None = None):
+        """Seed the draws of the *_drawn calls (cslam_pf_seed_draws).  first_global: the global slot of this shard's
+        particle 0; n_global: the size of the whole set (default: the shard's own n_global)."""
+        n_global = self.n_global if n_global is None else int(n_global)
+        check(self._L.cslam_pf_seed_draws(self._h, C.c_longlong(int(seed)), C.c_longlong(int(first_global)),
+                                          C.c_longlong(n_global)))
+        self._draw_n = n_global
+
+    def draws(self, step: int, normals: bool = True, select: bool = True):
+        """-> (normals 3 x n_local, select n_global) that the *_drawn calls of `step` consume (None where not asked)."""
+        n = getattr(self, "_draw_n", None)
+        nrm = np.zeros((3, self.n_local), self.dtype) if normals else None
+        # (unseeded, or a set beyond 2^31 - 1 that has no strata: the call refuses before it writes)
+        sel = np.zeros(n if n and n < 2**31 else 1, self.dtype) if select else None
+        check(self._L.cslam_pf_get_draws(self._h, C.c_longlong(int(step)), _vp(nrm) if normals else None,
+                                         _vp(sel) if select else None))
+        return nrm, sel
+
+    def sample_proposal_drawn(self, Z, idf, R, step: int):
+        """sample_proposal with the normals of `step` drawn on the device (streams 0..2)."""
+        Zc, m = self._z(Z)
+        idf = np.ascontiguousarray(idf, dtype=np.int32)
+        check(self._L.cslam_pf_sample_proposal_drawn(self._h, _vp(Zc), C.c_int(m), _vp(idf) if m else None,
+                                                     _vp(self._m22(R)), C.c_longlong(int(step))))
+
+    def sample_proposal_assoc_drawn(self, Z, R, step: int, use=None, miss_likelihood=1.0):
+        """sample_proposal_assoc with the normals of `step` drawn on the device."""
+        Zc, m = self._z(Z)
+        use = np.ones(m, np.int32) if use is None else np.ascontiguousarray(use, dtype=np.int32)
+        assert use.shape[0] == m
+        check(self._L.cslam_pf_sample_proposal_assoc_drawn(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)),
+                                                           _vp(use) if m else None, C.c_double(float(miss_likelihood)),
+                                                           C.c_longlong(int(step))))
+
+    def resample_local_drawn(self, step: int, n_effective: float, resample_status: bool, want_result: bool = True):
+        """resample_local with the strata of `step` drawn on the device (stream 3)."""
+        neff, did = C.c_double(0.0), C.c_int(0)
+        check(self._L.cslam_pf_resample_local_drawn(self._h, C.c_longlong(int(step)), C.c_double(float(n_effective)),
+                                                    C.c_int(1 if resample_status else 0),
+                                                    C.byref(neff) if want_result else None,
+                                                    C.byref(did) if want_result else None))
+        return (float(neff.value), bool(did.value)) if want_result else None
+
+    def resample_sharded_drawn(self, comm, step: int, n_effective: float, resample_status: bool):
+        """resample_sharded with the strata of `step` drawn on every rank's device: nobody distributes select."""
+        neff, did = C.c_double(0.0), C.c_int(0)
+        check(self._L.cslam_pf_resample_sharded_drawn(self._h, comm._h, C.c_longlong(int(step)),
+                                                      C.c_double(float(n_effective)), C.c_int(1 if resample_status else 0),
+                                                      C.byref(neff), C.byref(did)))
+        return float(neff.value), bool(did.value)
+
+    def observation_step_drawn(self, v, swa, Q, wb, dt, Z, idf, R, step: int, n_effective: float, resample_status: bool):
+        """observation_step with every random input of `step` drawn on the device: launches only when m <= 32."""
+        Zc, m = self._z(Z)
+        idf = np.ascontiguousarray(idf, dtype=np.int32)
+        check(self._L.cslam_pf_observation_step_drawn(self._h, C.c_double(float(v)), C.c_double(float(swa)),
+                                                      _vp(self._m22(Q)), C.c_double(float(wb)), C.c_double(float(dt)),
+                                                      _vp(Zc), C.c_int(m), _vp(idf) if m else None, _vp(self._m22(R)),
+                                                      C.c_longlong(int(step)), C.c_double(float(n_effective)),
+                                                      C.c_int(1 if resample_status else 0)))
+
+    def stage_copies(self) -> int:
+        """Host-to-device copy commands this shard has enqueued for per-step inputs (cslam_pf_stage_copies)."""
+        n = C.c_longlong(0)
+        check(self._L.cslam_pf_stage_copies(self._h, C.byref(n)))
+        return n.value
+
     def resample_stats(self):
         """(resample calls, resamples performed, last Neff) from the device-side counters."""
         a, b, c = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
@@ -515,14 +583,22 @@ class ParticleShard:
 # PF::resampleParticles over a sharded particle set
 # ------------------------------------------------------------------------------------------------
 def resample_particles(shard, comm, n_effective: int, resample_status: bool, select: np.ndarray | None = None,
-                       uniforms: np.ndarray | None = None):
+                       uniforms: np.ndarray | None = None, step: int | None = None):
     """PF::resampleParticles(particles, numEffective, resampleStatus) -- PF.cpp:473-500 -- for the particle set
     block-partitioned over comm.world shards.  `shard` is a ParticleShard (or anything with its resample
     surface: weight_sums, scale_weights, weights_tensor, pack, unpack, gather_local, set_uniform_weight,
     n_local, dtype).  `select` are the N strata positions (PF.cpp:557); when None they are built from
-    `uniforms` (N uniform[0,1) draws that every rank must pass identically).  Returns (neff, resampled)."""
+    `uniforms` (N uniform[0,1) draws that every rank must pass identically).  With `step` (and neither of the two) the
+    strata are drawn on the device of a shard seeded with seed_draws: resample_local_drawn for one shard,
+    resample_sharded_drawn over an RcclComm.  Returns (neff, resampled)."""
     n_local = shard.n_local
     n = n_local * comm.world
+    if step is not None:
+        assert select is None and uniforms is None, "step= draws the strata on the device: pass no select / uniforms"
+        if comm.world == 1:
+            return shard.resample_local_drawn(step, n_effective, resample_status)
+        assert isinstance(comm, (RcclComm, LoopbackComm)), "the drawn sharded resample runs behind the C ABI"
+        return shard.resample_sharded_drawn(comm, step, n_effective, resample_status)
     if comm.world == 1 and hasattr(shard, "resample_local") and not getattr(shard, "host_resample", False):
         # one shard holds everything: sums, normalisation, Neff, decision, keep[] and the moves stay on the device
         if select is None:

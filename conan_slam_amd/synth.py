@@ -42,6 +42,35 @@ def normal(seed: int, idx) -> np.ndarray:
     return np.sqrt(-2.0 * np.log(1.0 - u1)) * np.cos(2.0 * np.pi * u2)
 
 
+def pf_draw_key(step, e, g) -> np.ndarray:
+    """Counter of one particle-filter draw: ((step * 4 + e) << 32) | g in uint64 (wrapping).  g: the GLOBAL particle slot
+    (< 2^32); e: the stream -- 0, 1, 2 the three proposal normals, 3 the strata uniform."""
+    with np.errstate(over="ignore"):
+        s = np.asarray(step, dtype=np.uint64) * np.uint64(4) + np.asarray(e, dtype=np.uint64)
+        return (s << np.uint64(32)) | np.asarray(g, dtype=np.uint64)
+
+
+def pf_draw_normals(seed: int, step: int, first: int, count: int, dtype=np.float32) -> np.ndarray:
+    """The [3][count] proposal normals of the global particle slots first .. first + count - 1 at `step` (what
+    cslam_pf_sample_proposal_drawn consumes): normal() in f64, then one rounding to the particle dtype."""
+    g = np.uint64(first) + np.arange(count, dtype=np.uint64)
+    return np.stack([normal(seed, pf_draw_key(step, e, g)) for e in range(3)]).astype(dtype)
+
+
+def pf_draw_uniforms(seed: int, step: int, n: int) -> np.ndarray:
+    """The n strata uniforms of `step` in f64: u[i] = uniform01(seed, 2 * pf_draw_key(step, 3, i))."""
+    with np.errstate(over="ignore"):
+        return uniform01(seed, np.uint64(2) * pf_draw_key(step, 3, np.arange(n, dtype=np.uint64)))
+
+
+def pf_draw_select(seed: int, step: int, n: int, dtype=np.float32) -> np.ndarray:
+    """The n strata positions of `step` (what the _drawn resample calls consume): pf.stratified_random on
+    pf_draw_uniforms.  A pure function of bits -- the device reproduces it bit for bit."""
+    from .pf import stratified_random
+
+    return stratified_random(n, pf_draw_uniforms(seed, step, n), dtype)
+
+
 def noise_matrices(dtype=np.float32):
     """Q, R (slam.h:72-81, test/main.cpp:93-103) and the inflated QE = 2Q, RE = 8R (main.cpp:125-129)."""
     f = np.float32

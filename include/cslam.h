@@ -488,6 +488,51 @@ int cslam_pf_resample_sharded(cslam_pf_t h, cslam_comm_t comm, const void* selec
  * ints -- records sent to each destination rank, then records received from each source rank (all 0 when it did not
  * resample); send_idx: the local source indices in send order (capacity >= *n_send).  Any pointer may be NULL. */
 int cslam_pf_debug_last_exchange(cslam_pf_t h, int* counts, int* send_idx, int capacity, int* n_send);
+
+/* ---- the random inputs drawn on the device.  The reference draws them on the host from generators it seeds from the
+ * clock (slam.h:587-594): the three standard normals per particle of multivariateGauss (slam.h:753-764) that
+ * PF::sampleProposal consumes, and the strata positions of stratifiedRandom (PF.cpp:557, PF.cpp:579-596) that
+ * PF::resampleParticles consumes.  The calls above take them as host arrays (`normals`, `select`); the _drawn calls below
+ * take a step number instead and draw them on the device from the counter-based generator of conan_slam_amd/synth.py:
+ *     key(step, e, g) = ((step * 4 + e) << 32) | g   (uint64, wrapping; g = GLOBAL particle slot, e = stream)
+ *     normals[e][p]   = T(normal(seed, key(step, e, first_global + p)))                e = 0, 1, 2
+ *     select          = stratified_random(n_global, u),  u[i] = uniform01(seed, 2 * key(step, 3, i))
+ * (synth.pf_draw_normals / synth.pf_draw_select; select comes out bit for bit, the normals to the device's log / cos).
+ * A draw depends on (seed, step, global slot) only: ranks that hold 8 x 64 particles and one handle that holds 512 see
+ * the same noise, and nobody distributes select.  One producer kernel writes the draws where the staged copy of the
+ * host-array call would have put them, and the same consumer kernels follow with the same arguments; with m <= 32 the
+ * observations travel as that kernel's arguments and the call enqueues no copy command at all.
+ *
+ * cslam_pf_seed_draws   the seed (slam.h:587-594), the global slot of this handle's particle 0 and the size of the whole
+ *                       set: 0 <= first_global, first_global + n_particles <= n_global < 2^32.  May be called again.
+ *                       The strata (select) exist for n_global <= 2^31 - 1, which is all a resample can hold; a larger
+ *                       set draws normals only, and cslam_pf_get_draws refuses its select.
+ *                       Seeding changes nothing about any call that takes host arrays.
+ * cslam_pf_get_draws    what the _drawn calls of `step` consume: normals 3 * n_particles (component-major, as
+ *                       cslam_pf_sample_proposal takes them; slam.h:753-764) and select n_global (PF.cpp:557); either may
+ *                       be NULL.  Synchronises; touches neither the particles nor the staging area.
+ * Every _drawn call returns CSLAM_ERR_BAD_ARG on an unseeded handle and changes nothing; otherwise it validates and
+ * behaves as its host-array twin (cslam_pf_sample_proposal: PF.cpp:502-544, cslam_pf_sample_proposal_assoc,
+ * cslam_pf_resample_local / _sharded: PF.cpp:473-500, cslam_pf_observation_step).  The proposal uses streams 0..2 of
+ * `step`, the resample stream 3: cslam_pf_sample_proposal_drawn(step) + cslam_pf_feature_update +
+ * cslam_pf_resample_local_drawn(step) behind cslam_pf_predict is cslam_pf_observation_step_drawn(step).
+ * cslam_pf_resample_local_drawn and cslam_pf_observation_step_drawn need first_global = 0 and n_global = n_particles;
+ * cslam_pf_resample_sharded_drawn needs n_global = world * n_particles and first_global = rank * n_particles.
+ * cslam_pf_stage_copies  introspection: host-to-device copy commands this handle has enqueued for per-step inputs (the
+ *                       staged copies of Z / idf / normals / select), so that a test can hold "no copy". */
+int cslam_pf_seed_draws(cslam_pf_t h, long long seed, long long first_global, long long n_global);
+int cslam_pf_get_draws(cslam_pf_t h, long long step, void* normals /* 3*np or NULL */, void* select /* n_global or NULL */);
+int cslam_pf_sample_proposal_drawn(cslam_pf_t h, const void* Z, int m, const int* idf, const void* R, long long step);
+int cslam_pf_sample_proposal_assoc_drawn(cslam_pf_t h, const void* Z, int m, const void* R, const int* use,
+                                         double miss_likelihood, long long step);
+int cslam_pf_resample_local_drawn(cslam_pf_t h, long long step, double n_effective, int resample_status, double* neff,
+                                  int* resampled);
+int cslam_pf_resample_sharded_drawn(cslam_pf_t h, cslam_comm_t comm, long long step, double n_effective,
+                                    int resample_status, double* neff, int* resampled);
+int cslam_pf_observation_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z,
+                                    int m, const int* idf, const void* R, long long step, double n_effective,
+                                    int resample_status);
+int cslam_pf_stage_copies(cslam_pf_t h, long long* copies);
 /* download one particle (host buffers; any may be NULL): w (1), Xv (3), Pv (9), XF (2*nf), PF (4*nf) */
 int cslam_pf_get_particle(cslam_pf_t h, int index, void* w, void* Xv, void* Pv, void* XF, void* PF);
 /* upload one particle with nf features (nf must equal the current feature count, or set it when the

@@ -289,6 +289,12 @@ class HipPF : public PF
         report(cslam_pf_sample_proposal(h_, Z.data(), static_cast<int>(Z.cols()), idf.data(), R.data(), nrm.data()),
                "HipPF::sampleProposal"); // PF.cpp:502-544
     }
+    /// the same with the normals of slam.h:753-764 drawn on the device for the step set with setStep(): needs seedDraws()
+    void sampleProposalAll(const Eigen::MatrixXf& Z, const Eigen::VectorXi& idf, const Eigen::MatrixXf& R)
+    {
+        report(cslam_pf_sample_proposal_drawn(h_, Z.data(), static_cast<int>(Z.cols()), idf.data(), R.data(), step_),
+               "HipPF::sampleProposal"); // PF.cpp:502-544
+    }
     void featureUpdateAll(const Eigen::MatrixXf& Z, const Eigen::VectorXi& idf, const Eigen::MatrixXf& R)
     {
         report(cslam_pf_feature_update(h_, Z.data(), static_cast<int>(Z.cols()), idf.data(), R.data()),
@@ -305,6 +311,17 @@ class HipPF : public PF
     /// The reference draws fresh strata on every call (stratifiedRandom, PF.cpp:557): so must the caller -- the strata
     /// are consumed by the next resampleParticles and have to be set again before the one after.
     void setStrata(const Eigen::VectorXf& select) { select_ = select; }
+    /// Draw the normals of sampleProposalAll(Z, idf, R) and the strata of resampleParticles on the device instead, from
+    /// this seed (the reference's generators are seeded from the clock, slam.h:587-594): a draw depends on (seed, step,
+    /// particle slot of the WHOLE set) only, so with a communicator every rank passes the same seed and nothing else.
+    void seedDraws(long long seed)
+    {
+        seed_   = seed;
+        seeded_ = true;
+        applySeed();
+    }
+    /// the step whose draws the next sampleProposalAll(Z, idf, R) and resampleParticles consume (the caller counts)
+    void setStep(long long step) { step_ = step; }
     /// shard the particle set over ranks: resampleParticles then runs the three collectives of SURVEY 8e over RCCL
     void setCommunicator(cslam_comm_t comm)
     {
@@ -314,6 +331,15 @@ class HipPF : public PF
         {
             int rank = 0;
             report(cslam_comm_info(comm, &rank, &world_), "HipPF::setCommunicator");
+            rank_ = rank;
+        }
+        else
+        {
+            rank_ = 0;
+        }
+        if (seeded_)
+        {
+            applySeed(); // (the draws are keyed by the slot in the whole set)
         }
     }
 
@@ -323,6 +349,23 @@ class HipPF : public PF
     {
         double neff      = 0.0;
         int    resampled = 0;
+        if (seeded_ && select_.rows() == 0) // no strata set: those of step_, drawn on the device (PF.cpp:557)
+        {
+            if (comm_ != nullptr)
+            {
+                report(cslam_pf_resample_sharded_drawn(h_, comm_, step_, numEffective, resampleStatus ? 1 : 0, &neff,
+                                                       &resampled),
+                       "HipPF::resampleParticles");
+            }
+            else
+            {
+                report(cslam_pf_resample_local_drawn(h_, step_, numEffective, resampleStatus ? 1 : 0, &neff, &resampled),
+                       "HipPF::resampleParticles");
+            }
+            lastNeff_      = static_cast<float>(neff);
+            lastResampled_ = resampled != 0;
+            return;
+        }
         // the engine reads numParticles x ranks strata positions from this pointer: refuse anything else, as loudly as
         // the reference's catch blocks do (PF.cpp:215-218), instead of reading past the caller's vector
         if (select_.rows() != static_cast<long>(np_) * world_)
@@ -394,7 +437,11 @@ class HipPF : public PF
     cslam_pf_t      h_    = nullptr;
     cslam_comm_t    comm_ = nullptr;
     int             world_ = 1;
+    int             rank_  = 0;
     int             np_   = 0;
+    long long       seed_   = 0;
+    long long       step_   = 0;
+    bool            seeded_ = false;
     Eigen::VectorXf select_;
     float           lastNeff_      = 0.f;
     bool            lastResampled_ = false;
@@ -405,6 +452,11 @@ class HipPF : public PF
         {
             std::cout << cslam_last_error() << "\t" << who << std::endl; // cf. PF.cpp:215-218
         }
+    }
+    void applySeed()
+    {
+        report(cslam_pf_seed_draws(h_, seed_, static_cast<long long>(rank_) * np_, static_cast<long long>(world_) * np_),
+               "HipPF::seedDraws");
     }
 };
 

@@ -2,7 +2,9 @@
 """Timeline of a rocprofv3 --kernel-trace CSV: for a window of dispatches in the steady state, each kernel's start and
 end relative to the first one, its stream/queue, and how much of it overlapped the covariance downdate (P-GEMM); then, over everything after the skipped part, the duration
 statistics per kernel and the P-GEMM's start-to-start period.
-Usage: python tools/trace_timeline.py <kernel_trace.csv> [skip_fraction=0.5] [count=40]"""
+A trace without a P-GEMM (the particle filter's) names the kernel its window starts at and whose start-to-start period is
+the step: e.g. `pf_resample_plan` -- the copy command of a step shows as its blit kernel, or as the gap it leaves.
+Usage: python tools/trace_timeline.py <kernel_trace.csv> [skip_fraction=0.5] [count=40] [anchor=downdate]"""
 import csv
 import sys
 
@@ -19,10 +21,11 @@ def main():
     rows = list(csv.DictReader(open(sys.argv[1])))
     skip = float(sys.argv[2]) if len(sys.argv) > 2 else 0.5
     count = int(sys.argv[3]) if len(sys.argv) > 3 else 40
+    anchor = sys.argv[4] if len(sys.argv) > 4 else "downdate"
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     i0 = int(len(rows) * skip)
-    # start the window at a P-GEMM
-    while i0 < len(rows) and "downdate" not in rows[i0]["Kernel_Name"]:
+    # start the window at a P-GEMM (or at the named kernel)
+    while i0 < len(rows) and anchor not in rows[i0]["Kernel_Name"]:
         i0 += 1
     win = rows[i0:i0 + count]
     if not win:
@@ -46,6 +49,12 @@ def main():
         busy = sum(b - a for a, b in dd[:-1]) / (len(dd) - 1) / 1e3
         print(f"P-GEMM period {per:.1f} us, P-GEMM busy {busy:.1f} us per period ({100 * busy / per:.0f} %)")
     stats(rows, int(len(rows) * skip), skip)
+    if anchor != "downdate":
+        st = [int(r["Start_Timestamp"]) for r in rows[int(len(rows) * skip):] if anchor in r["Kernel_Name"]]
+        per = [(b - a) / 1e3 for a, b in zip(st, st[1:])]
+        if per:
+            print(f"  {anchor} start to start: n={len(per)} median {quantile(per, 0.5):.1f} us, quartiles "
+                  f"[{quantile(per, 0.25):.1f}, {quantile(per, 0.5):.1f}, {quantile(per, 0.75):.1f}]")
 
 
 def quantile(v, q):
