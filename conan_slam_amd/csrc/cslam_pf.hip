@@ -6,327 +6,27 @@
 // pack / unpack of particle records, local gather) so that a multi-GPU driver can put its collectives
 // between them (conan_slam_amd/pf.py does that with torch.distributed over RCCL).
 #include <hip/hip_runtime.h>
-#include <dlfcn.h>
-#include <rccl/rccl.h> // types only: the library itself is bound with dlopen (see Rccl below)
 
-#include <chrono>
+#include <algorithm>
 #include <cmath>
-#include <condition_variable>
 #include <cstring>
-#include <mutex>
 #include <new>
 #include <vector>
 
 #include "cslam_common.hpp"
 #include "device_owners.hpp"
 #include "pf_assoc_kernels.hpp"
+#include "pf_buffers.hpp"
+#include "pf_comm.hpp"
 #include "pf_draw_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
+#include "pf_staging.hpp"
 
 using namespace cslam;
 
 namespace
 {
-
-// ------------------------------------------------------------------------------------------------
-// RCCL, bound at run time.  One process must hold ONE copy of librccl (PyTorch wheels bundle their own, as they do
-// libamdhip64): dlopen by SONAME returns the copy the process already has, else the system one.
-// ------------------------------------------------------------------------------------------------
-struct Rccl
-{
-    void* lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*)                                                            = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int)                                     = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t)                                                               = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllGather)(const void*, void*, size_t, ncclDataType_t, ncclComm_t, hipStream_t)        = nullptr;
-    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)               = nullptr;
-    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t)                     = nullptr;
-    ncclResult_t (*GroupStart)()                                                                          = nullptr;
-    ncclResult_t (*GroupEnd)()                                                                            = nullptr;
-    const char* (*GetErrorString)(ncclResult_t)                                                           = nullptr;
-};
-
-inline Rccl* rccl()
-{
-    static Rccl r;
-    static bool tried = false;
-    if (!tried)
-    {
-        tried = true;
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-        {
-            r.lib = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (r.lib)
-            {
-                break;
-            }
-        }
-        if (r.lib)
-        {
-#define CSLAM_RCCL_SYM(field, sym) r.field = reinterpret_cast<decltype(r.field)>(dlsym(r.lib, sym))
-            CSLAM_RCCL_SYM(GetUniqueId, "ncclGetUniqueId");
-            CSLAM_RCCL_SYM(CommInitRank, "ncclCommInitRank");
-            CSLAM_RCCL_SYM(CommDestroy, "ncclCommDestroy");
-            CSLAM_RCCL_SYM(AllReduce, "ncclAllReduce");
-            CSLAM_RCCL_SYM(AllGather, "ncclAllGather");
-            CSLAM_RCCL_SYM(Send, "ncclSend");
-            CSLAM_RCCL_SYM(Recv, "ncclRecv");
-            CSLAM_RCCL_SYM(GroupStart, "ncclGroupStart");
-            CSLAM_RCCL_SYM(GroupEnd, "ncclGroupEnd");
-            CSLAM_RCCL_SYM(GetErrorString, "ncclGetErrorString");
-#undef CSLAM_RCCL_SYM
-            if (!r.GetUniqueId || !r.CommInitRank || !r.CommDestroy || !r.AllReduce || !r.AllGather || !r.Send || !r.Recv ||
-                !r.GroupStart || !r.GroupEnd)
-            {
-                r.lib = nullptr;
-            }
-        }
-    }
-    return r.lib ? &r : nullptr;
-}
-
-#define CSLAM_RCCL_TRY(expr)                                                                                         \
-    do                                                                                                               \
-    {                                                                                                                \
-        ncclResult_t r__ = (expr);                                                                                   \
-        if (r__ != ncclSuccess)                                                                                      \
-        {                                                                                                            \
-            return ::cslam::fail(CSLAM_ERR_HIP, "%s failed: %s (%s:%d)", #expr,                                      \
-                                 rccl()->GetErrorString ? rccl()->GetErrorString(r__) : "rccl error", __FILE__, __LINE__); \
-        }                                                                                                            \
-    } while (0)
-
-// ------------------------------------------------------------------------------------------------
-// The communicator of the sharded resample.  Two back-ends behind one interface:
-//   RCCL      one process (rank) per GPU, collectives over xGMI -- production;
-//   loopback  `world` ranks that live in ONE process on ONE device, one host thread per rank (RCCL refuses the same device
-//             twice in a communicator, SURVEY 7 "hard parts"): all-reduce / all-gather / send-recv are device-to-device
-//             copies ordered by a host barrier.  It exists so that the multi-rank code paths of
-//             cslam_pf_resample_sharded (ranks > 0, the exchange plan, the receive ordering) can run under test on a
-//             one-GPU box; it is slow on purpose (every collective synchronises the calling rank's stream twice).
-// ------------------------------------------------------------------------------------------------
-constexpr int kLoopMaxWorld = 16;
-
-struct LoopPtrs
-{
-    const double* p[kLoopMaxWorld];
-};
-
-__global__ void comm_loop_sum_kernel(LoopPtrs ptrs, int world, double* __restrict__ out, int count)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count)
-    {
-        double s = 0.0;
-        for (int r = 0; r < world; r++) // rank order: the same sum on every rank
-        {
-            s += ptrs.p[r][i];
-        }
-        out[i] = s;
-    }
-}
-
-struct LoopShared
-{
-    int                     world = 1;
-    int                     refs  = 0;
-    std::mutex              mu;
-    std::condition_variable cv;
-    int                     arrived = 0;
-    unsigned                gen     = 0;
-    bool                    broken  = false; // a rank gave up (error / timeout): every later barrier fails at once
-    std::vector<const void*> src;            // [rank] buffer registered for the collective in flight
-    struct P2P
-    {
-        const void* ptr   = nullptr;
-        size_t      bytes = 0;
-    };
-    std::vector<P2P> sends; // [from * world + to] of the group in flight
-
-    // all `world` ranks arrive, or false after `seconds` (a peer failed and never came)
-    bool barrier(double seconds = 60.0)
-    {
-        std::unique_lock<std::mutex> lk(mu);
-        if (broken)
-        {
-            return false;
-        }
-        const unsigned g = gen;
-        if (++arrived == world)
-        {
-            arrived = 0;
-            gen++;
-            cv.notify_all();
-            return true;
-        }
-        const bool ok = cv.wait_for(lk, std::chrono::duration<double>(seconds), [&] { return gen != g || broken; });
-        if (!ok || broken)
-        {
-            broken = true;
-            cv.notify_all();
-            return false;
-        }
-        return true;
-    }
-    void poison()
-    {
-        std::lock_guard<std::mutex> lk(mu);
-        broken = true;
-        cv.notify_all();
-    }
-};
-
-struct Comm
-{
-    ncclComm_t  comm   = nullptr; // RCCL back-end
-    LoopShared* loop   = nullptr; // loopback back-end
-    int         rank   = 0;
-    int         world  = 1;
-    int         device = 0;
-    bool        in_group = false;
-    struct Rv
-    {
-        void*  ptr;
-        size_t bytes;
-        int    peer;
-    };
-    std::vector<Rv> recvs; // loopback: receives of the open group
-
-    int loop_fail(const char* what)
-    {
-        loop->poison();
-        return ::cslam::fail(CSLAM_ERR_HIP, "loopback communicator: %s (rank %d of %d)", what, rank, world);
-    }
-
-    // recv[i] = sum over ranks of send[i], i < count doubles; identical on every rank
-    int all_reduce_sum_f64(const double* send, double* recv, int count, hipStream_t st)
-    {
-        if (!loop)
-        {
-            CSLAM_RCCL_TRY(rccl()->AllReduce(send, recv, (size_t)count, ncclDouble, ncclSum, comm, st));
-            return CSLAM_OK;
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(st)); // `send` is complete
-        loop->src[(size_t)rank] = send;
-        if (!loop->barrier())
-        {
-            return loop_fail("all-reduce: a peer never arrived");
-        }
-        LoopPtrs ptrs{};
-        for (int r = 0; r < world; r++)
-        {
-            ptrs.p[r] = static_cast<const double*>(loop->src[(size_t)r]);
-        }
-        hipLaunchKernelGGL(comm_loop_sum_kernel, dim3((count + 63) / 64), dim3(64), 0, st, ptrs, world, recv, count);
-        CSLAM_HIP_TRY(hipGetLastError());
-        CSLAM_HIP_TRY(hipStreamSynchronize(st)); // every peer's `send` has been read before anybody moves on
-        if (!loop->barrier())
-        {
-            return loop_fail("all-reduce: a peer never finished");
-        }
-        return CSLAM_OK;
-    }
-
-    // recv[r * bytes .. (r+1) * bytes) = rank r's send
-    int all_gather(const void* send, void* recv, size_t count, ncclDataType_t dt, size_t elt, hipStream_t st)
-    {
-        if (!loop)
-        {
-            CSLAM_RCCL_TRY(rccl()->AllGather(send, recv, count, dt, comm, st));
-            return CSLAM_OK;
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(st));
-        loop->src[(size_t)rank] = send;
-        if (!loop->barrier())
-        {
-            return loop_fail("all-gather: a peer never arrived");
-        }
-        const size_t bytes = count * elt;
-        for (int r = 0; r < world; r++)
-        {
-            CSLAM_HIP_TRY(hipMemcpyAsync(static_cast<char*>(recv) + (size_t)r * bytes, loop->src[(size_t)r], bytes,
-                                         hipMemcpyDeviceToDevice, st));
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(st));
-        if (!loop->barrier())
-        {
-            return loop_fail("all-gather: a peer never finished");
-        }
-        return CSLAM_OK;
-    }
-
-    int group_start()
-    {
-        in_group = true;
-        if (!loop)
-        {
-            CSLAM_RCCL_TRY(rccl()->GroupStart());
-            return CSLAM_OK;
-        }
-        recvs.clear();
-        for (int r = 0; r < world; r++)
-        {
-            loop->sends[(size_t)rank * world + r] = LoopShared::P2P{};
-        }
-        return CSLAM_OK;
-    }
-    int send(const void* buf, size_t count, ncclDataType_t dt, size_t elt, int peer, hipStream_t st)
-    {
-        if (!loop)
-        {
-            CSLAM_RCCL_TRY(rccl()->Send(buf, count, dt, peer, comm, st));
-            return CSLAM_OK;
-        }
-        loop->sends[(size_t)rank * world + peer] = LoopShared::P2P{buf, count * elt};
-        return CSLAM_OK;
-    }
-    int recv(void* buf, size_t count, ncclDataType_t dt, size_t elt, int peer, hipStream_t st)
-    {
-        if (!loop)
-        {
-            CSLAM_RCCL_TRY(rccl()->Recv(buf, count, dt, peer, comm, st));
-            return CSLAM_OK;
-        }
-        recvs.push_back(Rv{buf, count * elt, peer});
-        return CSLAM_OK;
-    }
-    // closes the group on every path (a group left open would swallow the next collective)
-    int group_end(hipStream_t st)
-    {
-        if (!in_group)
-        {
-            return CSLAM_OK;
-        }
-        in_group = false;
-        if (!loop)
-        {
-            CSLAM_RCCL_TRY(rccl()->GroupEnd());
-            return CSLAM_OK;
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(st)); // the send buffers are packed
-        if (!loop->barrier())
-        {
-            return loop_fail("send/recv: a peer never arrived");
-        }
-        for (const Rv& rv : recvs)
-        {
-            const LoopShared::P2P& sp = loop->sends[(size_t)rv.peer * world + rank];
-            if (sp.ptr == nullptr || sp.bytes != rv.bytes)
-            {
-                return loop_fail("send/recv: a receive has no matching send of the same size");
-            }
-            CSLAM_HIP_TRY(hipMemcpyAsync(rv.ptr, sp.ptr, rv.bytes, hipMemcpyDeviceToDevice, st));
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(st));
-        if (!loop->barrier()) // nobody reuses a send buffer before its receiver has copied it
-        {
-            return loop_fail("send/recv: a peer never finished");
-        }
-        return CSLAM_OK;
-    }
-};
 
 struct PfBase
 {
@@ -389,31 +89,22 @@ struct PfBase
     virtual int get_stage_copies(long long* copies)                                                                 = 0;
 };
 
+// Pf<T> sequences the runtime calls of every entry point; what it sequences them over lives in parts with one job each
+// (pf_staging.hpp, pf_buffers.hpp, pf_host_parts.hpp).  The parts are members, so they die before PfBase's stream.
 template <typename T>
 struct Pf : PfBase
 {
-    DevBuf<T>      dW, dXv, dPv, dXF, dPF;
-    // the twin set the single-pass resample gathers into; the two sets are swapped after every resample call
-    DevBuf<T>      dXv2, dPv2, dXF2, dPF2;
-    DevBuf<T>      dObs; // staging: Z (2*mcap T) | idf (mcap int) | normals (3*np T), filled by one copy per call
-    DevBuf<int>    dIdx; // index lists of pack/unpack (max(mcap, np))
-    DevBuf<double> dSums;
-    DevBuf<T>      dRec; // scratch for gather_local
-    int            mcap = 0;
-
-    // Pinned staging ring.  The small host inputs of a call (Z, idf, normals, select) are copied into the next slot and
-    // sent with ONE asynchronous copy, so the call returns without waiting for the stream (the caller's arrays are
-    // consumed before return all the same).  The stream is drained once per lap of the ring, never per call.
-    static constexpr int kStageSlots = 16;
-    PinnedBuf<char>   hStage;
-    size_t            stage_slot     = 0;
-    int               stage_pos      = 0;
-    int               stage_inflight = 0;
-    Event             stage_ev[kStageSlots]; // created (and recorded) by the first copy out of the slot
-    int               stage_last = 0; // slot handed out by the last stage_slot_for()
-    long long         stage_copies = 0; // host-to-device copy commands enqueued for per-step inputs (stage_commit)
-    std::vector<char> staged; // Z || idf bytes currently in dObs (empty = unknown)
-    PinnedBuf<double> hInfo;
+    DevBuf<T>          dW;
+    PfArrays<T>        cur, twin; // the store, and the set the single-pass resample gathers into; swapped by every resample
+    PfObsArea<T>       obs;
+    DevBuf<double>     dSums;
+    DevBuf<T>          dRec; // scratch for gather_local
+    PfStageRing        ring;
+    PfResampleBufs<T>  rs;
+    PfShardedBufs<T>   sh;
+    PfEstimateBufs<T>  est;
+    PfAssocTables<T>   assoc;
+    PfDraws<T>         draws;
 
     ~Pf() override
     {
@@ -424,149 +115,118 @@ struct Pf : PfBase
         }
     }
 
-    size_t off_idf() const
-    {
-        return (size_t)2 * mcap * sizeof(T);
-    }
-    size_t off_normals() const
-    {
-        return off_idf() + (size_t)mcap * sizeof(int);
-    }
-    int* dIdf() const
-    {
-        return reinterpret_cast<int*>(reinterpret_cast<char*>(dObs.get()) + off_idf());
-    }
-    T* dNormals() const
-    {
-        return reinterpret_cast<T*>(reinterpret_cast<char*>(dObs.get()) + off_normals());
-    }
-
-    int stage_slot_for(size_t bytes, char** out)
-    {
-        if (bytes > stage_slot)
-        {
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            size_t          newsz = std::max((bytes + 4095) / 4096 * 4096, 2 * stage_slot);
-            PinnedBuf<char> ring;
-            CSLAM_TRY(ring.alloc(newsz * kStageSlots));
-            hStage         = std::move(ring);
-            stage_slot     = newsz;
-            stage_pos      = 0;
-            stage_inflight = 0; // (the slots' events are all complete after the synchronisation above)
-        }
-        // a slot is reused one lap later: wait for the copy that read it last (long done in the steady state) instead of
-        // draining the stream once per lap (which cost a ~60 us bubble every 16 calls)
-        if (stage_ev[stage_pos])
-        {
-            CSLAM_HIP_TRY(hipEventSynchronize(stage_ev[stage_pos].get()));
-        }
-        stage_last = stage_pos;
-        *out      = hStage.get() + (size_t)stage_pos * stage_slot;
-        stage_pos = (stage_pos + 1) % kStageSlots;
-        stage_inflight++;
-        return CSLAM_OK;
-    }
-
-    // the copy out of the slot handed out last has been enqueued: mark it
-    int stage_commit()
-    {
-        if (!stage_ev[stage_last])
-        {
-            CSLAM_TRY(stage_ev[stage_last].create(hipEventDisableTiming));
-        }
-        CSLAM_HIP_TRY(hipEventRecord(stage_ev[stage_last].get(), stream));
-        stage_copies++;
-        return CSLAM_OK;
-    }
-
-
     int use_device()
     {
         CSLAM_HIP_TRY(hipSetDevice(device));
         return CSLAM_OK;
     }
 
-    PfStore<T> store() const
+    PfStore<T> store_of(const PfArrays<T>& a) const
     {
-        PfStore<T> s;
-        s.w  = dW.get();
-        s.xv = dXv.get();
-        s.pv = dPv.get();
-        s.xf = dXF.get();
-        s.pf = dPF.get();
-        s.np = np;
-        s.nf = nf;
-        return s;
+        return PfStore<T>{dW.get(), a.xv.get(), a.pv.get(), a.xf.get(), a.pf.get(), np, nf};
     }
+    PfStore<T> store() const { return store_of(cur); }
 
-    int ensure_m(int m)
-    {
-        if (m <= mcap)
-        {
-            return CSLAM_OK;
-        }
-        int newm = (std::max(m, std::max(64, 2 * mcap)) + 3) / 4 * 4; // keeps the normals 16-byte aligned
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        DevBuf<T>   obs;
-        DevBuf<int> idx;
-        // (newm is a multiple of 4: its ints are a whole number of T)
-        int rc = obs.alloc((size_t)2 * newm + (size_t)4 * np + (size_t)newm * sizeof(int) / sizeof(T));
-        if (rc || (rc = idx.alloc((size_t)std::max(newm, np))))
-        {
-            return rc;
-        }
-        staged.clear();
-        dObs = std::move(obs);
-        dIdx = std::move(idx);
-        mcap = newm;
-        return CSLAM_OK;
-    }
+    int ensure_m(int m) { return obs.ensure(m, stream); }
 
     int init() override
     {
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
         CSLAM_TRY(stream_own.create(hipStreamNonBlocking));
         stream    = stream_own.get();
         size_t n1 = (size_t)np;
         size_t cf = (size_t)std::max(nfcap, 1);
-        // PF.cpp:319-341: X = 0, P = 0, empty map; w = 1/np until the driver sets the global value
-        if ((rc = dW.alloc(n1)) || (rc = dXv.alloc_zeroed(3 * n1, stream)) || (rc = dPv.alloc_zeroed(9 * n1, stream)) ||
-            (rc = dXF.alloc_zeroed(2 * cf * n1, stream)) || (rc = dPF.alloc_zeroed(4 * cf * n1, stream)) ||
-            (rc = dSums.alloc(2)) || (rc = dRec.alloc(n1 * (13 + 6 * cf))) || (rc = dXv2.alloc_zeroed(3 * n1,
-            stream)) || (rc = dPv2.alloc_zeroed(9 * n1, stream)) || (rc = dXF2.alloc_zeroed(2 * cf * n1, stream)) ||
-            (rc = dPF2.alloc_zeroed(4 * cf * n1, stream)))
-        {
-            return rc;
-        }
-        rc = ensure_m(64);
-        if (rc)
-        {
-            return rc;
-        }
-        rc = set_uniform_weight(1.0 / (double)np);
-        if (rc)
-        {
-            return rc;
-        }
+        obs.set_particles(np);
+        // w = 1/np until the driver sets the global value
+        CSLAM_TRY(dW.alloc(n1));
+        CSLAM_TRY(cur.alloc_zeroed(n1, cf, stream));
+        CSLAM_TRY(dSums.alloc(2));
+        CSLAM_TRY(dRec.alloc(n1 * (13 + 6 * cf)));
+        CSLAM_TRY(twin.alloc_zeroed(n1, cf, stream));
+        CSLAM_TRY(ensure_m(64));
+        CSLAM_TRY(set_uniform_weight(1.0 / (double)np));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // One launch helper per kernel that more than one entry point launches.  Z | idf | normals are those of the staging
+    // area.  The quirk decides the gain of the feature update: a flag of the update kernels, another of the fused forms.
+    // ------------------------------------------------------------------------------------------------
+    int update_gain() const { return (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1; }
+    int fused_update_gain() const { return (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 1 : 2; }
+    static PfPredict<T> no_predict() { return PfPredict<T>{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0}; }
+
+    int launch_predict(double v, double swa, const T* Q, double wb, double dt)
+    {
+        hipLaunchKernelGGL(pf_predict_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), (T)v, (T)swa, Q[0],
+                           Q[1], Q[2], Q[3], (T)wb, (T)dt);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    // fu: 0 = proposal alone, else fused_update_gain()
+    int launch_proposal(int m, const T* R, const PfPredict<T>& pr, int fu)
+    {
+        hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
+                           store(), obs.z(), obs.dIdf(), m, R[0], R[1], R[2], R[3], obs.dNormals(), pr, fu);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    // (the use[] mask travels in the staging area's idf slot)
+    int launch_proposal_assoc(int m, const T* R, double miss_likelihood)
+    {
+        hipLaunchKernelGGL(pf_sample_proposal_assoc_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
+                           store(), obs.z(), assoc.tab.idf.get(), obs.dIdf(), m, R[0], R[1], R[2], R[3], obs.dNormals(),
+                           (T)miss_likelihood, fused_update_gain());
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    int launch_feature_update(int m, const T* R)
+    {
+        hipLaunchKernelGGL(pf_feature_update_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(), obs.z(),
+                           obs.dIdf(), m, R[0], R[1], R[2], R[3], update_gain());
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    int launch_feature_update_assoc(int m, const T* R)
+    {
+        hipLaunchKernelGGL(pf_feature_update_assoc_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(),
+                           obs.z(), assoc.tab.idf.get(), obs.dIdf(), m, R[0], R[1], R[2], R[3], update_gain());
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    int launch_weight_sums()
+    {
+        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, dSums.get());
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    // w = value (set) or w *= value
+    int launch_scale_weights(double value, int set)
+    {
+        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
+                           (T)value, set);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    int launch_pack(const int* d_idx, int count, T* d_rec)
+    {
+        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), d_idx, count, d_rec);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    // d_idx == nullptr: record i into slot i
+    int launch_unpack(const int* d_idx, int count, const T* d_rec)
+    {
+        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), d_idx, count, d_rec);
+        CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
 
     int set_uniform_weight(double w0) override
     {
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
-                           (T)w0, 1);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        return launch_scale_weights(w0, 1);
     }
 
     int predict(double v, double swa, const void* Qv, double wb, double dt) override
@@ -575,16 +235,8 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_predict: Q is null");
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        const T* Q = static_cast<const T*>(Qv);
-        hipLaunchKernelGGL(pf_predict_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), (T)v, (T)swa, Q[0],
-                           Q[1], Q[2], Q[3], (T)wb, (T)dt);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        return launch_predict(v, swa, static_cast<const T*>(Qv), wb, dt);
     }
 
     int observe_heading(double phi, int use) override
@@ -593,11 +245,7 @@ struct Pf : PfBase
         {
             return CSLAM_OK;
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
         T sigma = (T)(((double)0.01f * kPi) / 180.0); // PF.cpp:391
         hipLaunchKernelGGL(pf_heading_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), (T)phi,
                            sigma * sigma);
@@ -617,56 +265,33 @@ struct Pf : PfBase
         return CSLAM_OK;
     }
 
-    // stage Z (2*m) and idf (m) of one call, plus `extra` (the normals) when given; inputs are consumed before return.
-    // A call whose Z/idf are byte-identical to what dObs already holds (featureUpdate right after sampleProposal,
-    // PF.cpp:150-156) sends nothing.
-    int stage(const void* Z, int m, const int* idf, const void* extra = nullptr, size_t extra_bytes = 0)
+    // stage Z (2*m) and idf (m, or the use[] mask, or nullptr) of one call, plus the 3*np normals when given; inputs are
+    // consumed before return.  Without normals, a call whose Z / idf the staging area already holds sends nothing.
+    int stage(const void* Z, int m, const int* idf, const void* normals = nullptr)
     {
-        int rc = ensure_m(m);
-        if (rc)
-        {
-            return rc;
-        }
-        const size_t zb = (size_t)2 * m * sizeof(T), ib = idf ? (size_t)m * sizeof(int) : 0;
-        const bool   same = !extra && !staged.empty() && staged.size() == zb + ib && std::memcmp(staged.data(), Z, zb) == 0 &&
-                          (ib == 0 || std::memcmp(staged.data() + zb, idf, ib) == 0);
-        if (same)
+        CSLAM_TRY(ensure_m(m));
+        if (!normals && obs.holds(Z, m, idf))
         {
             return CSLAM_OK;
         }
-        const size_t bytes = extra ? off_normals() + extra_bytes : (idf ? off_idf() + ib : zb);
-        char*        slot  = nullptr;
-        if ((rc = stage_slot_for(bytes, &slot)))
-        {
-            return rc;
-        }
-        if (zb)
-        {
-            std::memcpy(slot, Z, zb);
-        }
-        if (ib)
-        {
-            std::memcpy(slot + off_idf(), idf, ib);
-        }
-        if (extra)
-        {
-            std::memcpy(slot + off_normals(), extra, extra_bytes);
-        }
-        staged.clear();
-        CSLAM_HIP_TRY(hipMemcpyAsync(dObs.get(), slot, bytes, hipMemcpyHostToDevice, stream));
-        if ((rc = stage_commit()))
-        {
-            return rc;
-        }
-        staged.resize(zb + ib);
-        if (zb)
-        {
-            std::memcpy(staged.data(), Z, zb);
-        }
-        if (ib)
-        {
-            std::memcpy(staged.data() + zb, idf, ib);
-        }
+        const PfObsLayout<T>& lay = obs.layout();
+        const size_t zb = lay.bytes_z(m), ib = idf ? (size_t)m * sizeof(int) : 0, nb = (size_t)3 * np * sizeof(T);
+        const size_t bytes = normals ? lay.bytes_z_idf_normals() : (idf ? lay.bytes_z_idf(m) : zb);
+        CSLAM_TRY(obs.receive(ring, bytes, stream, [&](char* slot) {
+            if (zb)
+            {
+                std::memcpy(slot, Z, zb);
+            }
+            if (ib)
+            {
+                std::memcpy(slot + lay.off_idf(), idf, ib);
+            }
+            if (normals)
+            {
+                std::memcpy(slot + lay.off_normals(), normals, nb);
+            }
+        }));
+        obs.remember(Z, m, idf);
         return CSLAM_OK;
     }
 
@@ -676,18 +301,10 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal: bad arguments");
         }
-        int rc = use_device();
-        if (rc || (rc = check_idf(idf, m, "pf_sample_proposal")) ||
-            (rc = stage(Z, m, idf, normals, (size_t)3 * np * sizeof(T))))
-        {
-            return rc;
-        }
-        const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
-                           store(), dObs.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(), PfPredict<T>{0, (T)0,
-                           (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0}, 0);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_idf(idf, m, "pf_sample_proposal"));
+        CSLAM_TRY(stage(Z, m, idf, normals));
+        return launch_proposal(m, static_cast<const T*>(Rv), no_predict(), 0);
     }
 
     int feature_update(const void* Z, int m, const int* idf, const void* Rv) override
@@ -700,16 +317,10 @@ struct Pf : PfBase
         {
             return CSLAM_OK;
         }
-        int rc = use_device();
-        if (rc || (rc = check_idf(idf, m, "pf_feature_update")) || (rc = stage(Z, m, idf)))
-        {
-            return rc;
-        }
-        const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_feature_update_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(),
-                           dObs.get(), dIdf(), m, R[0], R[1], R[2], R[3], (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_idf(idf, m, "pf_feature_update"));
+        CSLAM_TRY(stage(Z, m, idf));
+        return launch_feature_update(m, static_cast<const T*>(Rv));
     }
 
     int add_features(const void* Z, int q, const void* Rv) override
@@ -726,14 +337,11 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_CAPACITY, "pf_add_features: %d features would exceed max_features=%d", nf + q, nfcap);
         }
-        int rc = use_device();
-        if (rc || (rc = stage(Z, q, nullptr)))
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage(Z, q, nullptr));
         const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, q), dim3(64), 0, stream, store(), dObs.get(),
-                           q, R[0], R[1], R[2], R[3]);
+        hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, q), dim3(64), 0, stream, store(), obs.z(), q,
+                           R[0], R[1], R[2], R[3]);
         CSLAM_HIP_TRY(hipGetLastError());
         nf += q;
         return CSLAM_OK;
@@ -745,13 +353,8 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_weight_sums: null");
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, dSums.get());
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(launch_weight_sums());
         CSLAM_HIP_TRY(hipMemcpyAsync(sums, dSums.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -759,15 +362,8 @@ struct Pf : PfBase
 
     int scale_weights(double scale) override
     {
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
-                           (T)scale, 0);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        return launch_scale_weights(scale, 0);
     }
 
     int weights_ptr(void** p) override
@@ -787,11 +383,7 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_get_weights: null");
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
         CSLAM_HIP_TRY(hipMemcpyAsync(w, dW.get(), (size_t)np * sizeof(T), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -803,11 +395,7 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_set_weights: null");
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
         CSLAM_HIP_TRY(hipMemcpyAsync(dW.get(), w, (size_t)np * sizeof(T), hipMemcpyHostToDevice, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -836,12 +424,8 @@ struct Pf : PfBase
                 return fail(CSLAM_ERR_BAD_ARG, "%s: index %d outside 0..%d", who, idx[i], np - 1);
             }
         }
-        int rc = ensure_m(count);
-        if (rc)
-        {
-            return rc;
-        }
-        CSLAM_HIP_TRY(hipMemcpyAsync(dIdx.get(), idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, stream));
+        CSLAM_TRY(ensure_m(count));
+        CSLAM_HIP_TRY(hipMemcpyAsync(obs.dIdx(), idx, (size_t)count * sizeof(int), hipMemcpyHostToDevice, stream));
         return CSLAM_OK;
     }
 
@@ -855,14 +439,9 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_pack: null buffer");
         }
-        int rc = use_device();
-        if (rc || (rc = stage_idx(idx, count, "pf_pack")))
-        {
-            return rc;
-        }
-        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx.get(), count,
-                           static_cast<T*>(drec));
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage_idx(idx, count, "pf_pack"));
+        CSLAM_TRY(launch_pack(obs.dIdx(), count, static_cast<T*>(drec)));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // the buffer is handed to a collective on another stream
         return CSLAM_OK;
     }
@@ -877,15 +456,10 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_unpack: null buffer");
         }
-        int rc = use_device();
-        if (rc || (rc = stage_idx(idx, count, "pf_unpack")))
-        {
-            return rc;
-        }
-        assoc_moved = true;
-        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), dIdx.get(), count,
-                           static_cast<const T*>(drec));
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage_idx(idx, count, "pf_unpack"));
+        assoc.memo.moved();
+        CSLAM_TRY(launch_unpack(obs.dIdx(), count, static_cast<const T*>(drec)));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
@@ -893,64 +467,36 @@ struct Pf : PfBase
     // PF.cpp:490-499 for a single shard: slot i <- particle keep[i], weights = w_new
     int gather_local(const int* keep, double w_new) override
     {
-        int rc = use_device();
-        if (rc || (rc = stage_idx(keep, np, "pf_gather_local")))
-        {
-            return rc;
-        }
-        assoc_moved = true;
-        hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx.get(), np, dRec.get());
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage_idx(keep, np, "pf_gather_local"));
+        assoc.memo.moved();
+        CSLAM_TRY(launch_pack(obs.dIdx(), np, dRec.get()));
         std::vector<int> ident((size_t)np);
         for (int i = 0; i < np; i++)
         {
             ident[i] = i;
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dIdx.get(), ident.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice,
-                                     stream));
-        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(np), dim3(256), 0, stream, store(), dIdx.get(), np, dRec.get());
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_HIP_TRY(hipMemcpyAsync(obs.dIdx(), ident.data(), (size_t)np * sizeof(int), hipMemcpyHostToDevice, stream));
+        CSLAM_TRY(launch_unpack(obs.dIdx(), np, dRec.get()));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return set_uniform_weight(w_new);
     }
 
     // PF.cpp:473-500 for a single shard that holds the whole particle set, without leaving the device: plan
-    // (sums, normalise, Neff, decision, keep[]) -> pack(keep) -> unpack(identity) -> w = 1/N, the last three gated by a
-    // device flag.  One D2H of {Neff, flag} at the end, and only if the caller asks for them.
-    DevBuf<T>      dSel, dCum;
-    DevBuf<int>    dKeep, dEnable;
-    DevBuf<double> dInfo;
+    // (sums, normalise, Neff, decision, keep[]) -> gather into the twin set -> w = 1/N, the last two gated by a device
+    // flag.  One D2H of {Neff, flag} at the end, and only if the caller asks for them.
     int resample_local(const void* select, double n_eff, int status, double* neff, int* did) override
     {
         if (!select)
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_resample_local: null select");
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        if ((rc = ensure_resample_buffers()))
-        {
-            return rc;
-        }
-        char* slot = nullptr;
-        if ((rc = stage_slot_for((size_t)np * sizeof(T), &slot)))
-        {
-            return rc;
-        }
-        std::memcpy(slot, select, (size_t)np * sizeof(T));
-        CSLAM_HIP_TRY(hipMemcpyAsync(dSel.get(), slot, (size_t)np * sizeof(T), hipMemcpyHostToDevice, stream));
-        if ((rc = stage_commit()))
-        {
-            return rc;
-        }
-        if ((rc = launch_resample(dSel.get(), n_eff, status)))
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(rs.ensure(np, stream));
+        const size_t bytes = (size_t)np * sizeof(T);
+        CSLAM_TRY(ring.send(rs.sel.get(), bytes, stream, [&](char* slot) { std::memcpy(slot, select, bytes); }));
+        CSLAM_TRY(launch_resample(rs.sel.get(), n_eff, status));
         return resample_result(neff, did);
     }
 
@@ -959,79 +505,16 @@ struct Pf : PfBase
     {
         if (neff || did)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(hInfo.get(), dInfo.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(rs.hInfo.get(), rs.info.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            stage_inflight = 0;
             if (neff)
             {
-                *neff = hInfo[0];
+                *neff = rs.hInfo[0];
             }
             if (did)
             {
-                *did = hInfo[1] != 0.0 ? 1 : 0;
+                *did = rs.hInfo[1] != 0.0 ? 1 : 0;
             }
-        }
-        return CSLAM_OK;
-    }
-
-    // PF.cpp:473-500 over a particle set sharded across ranks (one rank per GPU): see cslam_pf_resample_sharded in
-    // include/cslam.h.  Everything is ordered on the handle's stream; the host reads back the two global sums (the
-    // decision must be the same on every rank and drives which collectives run) and, when it resamples, the
-    // 2 x world record counts of the exchange.
-    DevBuf<double>    dSumsG;
-    DevBuf<T>         dWall, dSelG;
-    DevBuf<T>         dCumG; // running sum of the gathered weights (pf_keep_kernel)
-    DevBuf<int>       dKeepG, dSendIdx, dCounts;
-    PinnedBuf<double> hCounts; // the two global sums first, later the record counts (ints from double 4 on)
-    DevBuf<T>         dSendBuf, dRecvBuf;
-    int     sh_world = 0;
-    int     sh_nf    = -1;
-    std::vector<int> last_counts; // 2 * world record counts of the last exchange (send per destination, receive per source)
-    int              last_n_send = 0;
-
-    // buffers of the sharded resample: everything that can fail is allocated BEFORE the first collective, so that a rank
-    // never leaves its peers waiting inside one because a local allocation failed
-    int ensure_sharded_buffers(int world)
-    {
-        const int N = np * world;
-        if (sh_world != world)
-        {
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            DevBuf<double>    sums;
-            DevBuf<T>         wall, sel, cum;
-            DevBuf<int>       keep, send_idx, counts;
-            PinnedBuf<double> hcounts;
-            int               rc = sums.alloc(2);
-            if (rc || (rc = wall.alloc((size_t)N)) || (rc = sel.alloc((size_t)N)) || (rc = cum.alloc((size_t)N)) ||
-                (rc = keep.alloc((size_t)N)) || (rc = send_idx.alloc((size_t)N)) ||
-                (rc = counts.alloc((size_t)2 * world)) || (rc = hcounts.alloc((size_t)2 * world + 4)))
-            {
-                return rc;
-            }
-            dSumsG   = std::move(sums);
-            dWall    = std::move(wall);
-            dSelG    = std::move(sel);
-            dCumG    = std::move(cum);
-            dKeepG   = std::move(keep);
-            dSendIdx = std::move(send_idx);
-            dCounts  = std::move(counts);
-            hCounts  = std::move(hcounts);
-            sh_world = world;
-            sh_nf    = -1; // (the record buffers below are sized by N as well)
-        }
-        if (sh_nf != nf)
-        {
-            const size_t rec = (size_t)(13 + 6 * nf);
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            DevBuf<T> send, recv;
-            int       rc = send.alloc((size_t)N * rec); // worst case: every slot keeps a particle of this rank
-            if (rc || (rc = recv.alloc((size_t)np * rec)))
-            {
-                return rc;
-            }
-            dSendBuf = std::move(send);
-            dRecvBuf = std::move(recv);
-            sh_nf    = nf;
         }
         return CSLAM_OK;
     }
@@ -1051,21 +534,21 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_resample_sharded_drawn: null communicator");
         }
-        int rc = need_draws("pf_resample_sharded_drawn");
-        if (rc)
-        {
-            return rc;
-        }
-        if (draw_nglobal != (long long)c->world * np || draw_first != (long long)c->rank * np)
+        CSLAM_TRY(need_draws("pf_resample_sharded_drawn"));
+        if (draws.nglobal != (long long)c->world * np || draws.first != (long long)c->rank * np)
         {
             return fail(CSLAM_ERR_BAD_ARG,
                         "pf_resample_sharded_drawn: the draws were seeded for slots %lld.. of %lld, rank %d of %d holds %lld.. of %lld",
-                        draw_first, draw_nglobal, c->rank, c->world, (long long)c->rank * np, (long long)c->world * np);
+                        draws.first, draws.nglobal, c->rank, c->world, (long long)c->rank * np, (long long)c->world * np);
         }
         return resample_sharded_from(c, nullptr, step, n_eff, status, neff, did);
     }
 
-    // select != nullptr: the caller's strata positions (one staged copy); nullptr: those of `step`, drawn into dSelG
+    // PF.cpp:473-500 over a particle set sharded across ranks (one rank per GPU): see cslam_pf_resample_sharded in
+    // include/cslam.h.  Everything is ordered on the handle's stream; the host reads back the two global sums (the
+    // decision must be the same on every rank and drives which collectives run) and, when it resamples, the
+    // 2 x world record counts of the exchange.
+    // select != nullptr: the caller's strata positions (one staged copy); nullptr: those of `step`, drawn on the device
     int resample_sharded_from(Comm* c, const void* select, long long step, double n_eff, int status, double* neff, int* did)
     {
         if (!c->loop && !rccl())
@@ -1073,48 +556,29 @@ struct Pf : PfBase
             return fail(CSLAM_ERR_HIP, "pf_resample_sharded: librccl could not be loaded");
         }
         const int world = c->world, rank = c->rank, L = np, N = np * world;
-        assoc_moved = true;
-        int rc = use_device();
-        if (rc || (rc = ensure_sharded_buffers(world)))
-        {
-            return rc;
-        }
+        assoc.memo.moved();
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(sh.ensure(world, nf, np, stream));
         const ncclDataType_t dt = (sizeof(T) == 4) ? ncclFloat : ncclDouble;
         // the strata positions go to the device up front as well (staging can fail; the copy is cheap when unused)
         if (select)
         {
-            char* slot = nullptr;
-            if ((rc = stage_slot_for((size_t)N * sizeof(T), &slot)))
-            {
-                return rc;
-            }
-            std::memcpy(slot, select, (size_t)N * sizeof(T));
-            CSLAM_HIP_TRY(hipMemcpyAsync(dSelG.get(), slot, (size_t)N * sizeof(T), hipMemcpyHostToDevice, stream));
-            if ((rc = stage_commit()))
-            {
-                return rc;
-            }
+            const size_t bytes = (size_t)N * sizeof(T);
+            CSLAM_TRY(ring.send(sh.plan.selG.get(), bytes, stream, [&](char* slot) { std::memcpy(slot, select, bytes); }));
         }
-        else if ((rc = launch_draw(step, nullptr, dSelG.get(), N, 0, nullptr, nullptr)))
+        else
         {
-            return rc;
+            CSLAM_TRY(launch_draw(step, nullptr, sh.plan.selG.get(), N, 0, nullptr, nullptr));
         }
         // 1. global weight sums
-        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, dSums.get());
-        CSLAM_HIP_TRY(hipGetLastError());
-        if ((rc = c->all_reduce_sum_f64(dSums.get(), dSumsG.get(), 2, stream)))
-        {
-            return rc;
-        }
-        double* hs = reinterpret_cast<double*>(hCounts.get()); // (pinned; the counts use it later)
-        CSLAM_HIP_TRY(hipMemcpyAsync(hs, dSumsG.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        CSLAM_TRY(launch_weight_sums());
+        CSLAM_TRY(c->all_reduce_sum_f64(dSums.get(), sh.plan.sumsG.get(), 2, stream));
+        double* hs = sh.h_sums(); // (pinned; the counts use it later)
+        CSLAM_HIP_TRY(hipMemcpyAsync(hs, sh.plan.sumsG.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        stage_inflight = 0;
         const double ws = hs[0], ws2 = hs[1];
         // 2. w /= ws (PF.cpp:482-487), Neff = 1 / sum (w/ws)^2 (PF.cpp:549-554), the decision (PF.cpp:490)
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream, dW.get(), np,
-                           (T)(1.0 / ws), 0);
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_TRY(launch_scale_weights(1.0 / ws, 0));
         const double ne = (ws2 > 0.0) ? (ws * ws) / ws2 : 0.0;
         const bool   go = (ne < n_eff) && status;
         if (neff)
@@ -1125,94 +589,73 @@ struct Pf : PfBase
         {
             *did = go ? 1 : 0;
         }
-        last_counts.assign((size_t)2 * world, 0);
-        last_n_send = 0;
+        sh.last_counts.assign((size_t)2 * world, 0);
+        sh.last_n_send = 0;
         if (!go)
         {
             return CSLAM_OK;
         }
         // 3. every rank plans the same keep[] from the gathered weights and the shared strata
-        if ((rc = c->all_gather(dW.get(), dWall.get(), (size_t)L, dt, sizeof(T), stream)))
-        {
-            return rc;
-        }
-        hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, dWall.get(), N, dSelG.get(), dKeepG.get(),
-                           dCumG.get());
+        CSLAM_TRY(c->all_gather(dW.get(), sh.plan.wall.get(), (size_t)L, dt, sizeof(T), stream));
+        hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, sh.plan.wall.get(), N, sh.plan.selG.get(),
+                           sh.plan.keepG.get(), sh.plan.cumG.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pf_exchange_plan_kernel<0>, dim3(1), dim3(256), 0, stream, dKeepG.get(), N, L, rank, world,
-                           dSendIdx.get(), dCounts.get());
+        hipLaunchKernelGGL(pf_exchange_plan_kernel<0>, dim3(1), dim3(256), 0, stream, sh.plan.keepG.get(), N, L, rank, world,
+                           sh.plan.sendIdx.get(), sh.plan.counts.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        int* hc = reinterpret_cast<int*>(hCounts.get()) + 8;
-        CSLAM_HIP_TRY(hipMemcpyAsync(hc, dCounts.get(), (size_t)2 * world * sizeof(int), hipMemcpyDeviceToHost,
+        int* hc = sh.h_counts();
+        CSLAM_HIP_TRY(hipMemcpyAsync(hc, sh.plan.counts.get(), (size_t)2 * world * sizeof(int), hipMemcpyDeviceToHost,
                                      stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        stage_inflight = 0;
-        int n_send = 0, n_recv = 0;
-        for (int r = 0; r < world; r++)
-        {
-            n_send += hc[r];
-            n_recv += hc[world + r];
-        }
-        last_counts.assign(hc, hc + 2 * world);
-        last_n_send = n_send;
+        int        n_send = 0, n_recv = 0;
+        const bool plan_ok = pf_exchange_plan_ok(hc, world, rank, L, &n_send, &n_recv);
+        sh.last_counts.assign(hc, hc + 2 * world);
+        sh.last_n_send = n_send;
         // (every rank derives the plan from the same gathered weights, so these checks fail on all ranks or on none)
-        if (n_recv != L || hc[rank] != hc[world + rank])
+        if (!plan_ok)
         {
             return fail(CSLAM_ERR_HIP, "pf_resample_sharded: inconsistent exchange plan (%d of %d slots filled, self %d / %d)",
                         n_recv, L, hc[rank], hc[world + rank]);
         }
         const size_t rec = (size_t)(13 + 6 * nf);
+        T *          sbuf = sh.rec.send.get(), *rbuf = sh.rec.recv.get();
         // 4. records out of the store (before any slot is overwritten), exchange, records into the slots in order
         if (n_send > 0)
         {
-            hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(n_send), dim3(256), 0, stream, store(), dSendIdx.get(), n_send,
-                               dSendBuf.get());
-            CSLAM_HIP_TRY(hipGetLastError());
+            CSLAM_TRY(launch_pack(sh.plan.sendIdx.get(), n_send, sbuf));
         }
+        size_t soff = 0, roff = 0;
         // the records that stay on this rank: a device copy, outside the group
+        pf_exchange_offsets(hc, world, rank, &soff, &roff);
+        if (hc[rank] > 0)
         {
-            size_t soff = 0, roff = 0;
-            for (int r = 0; r < rank; r++)
-            {
-                soff += (size_t)hc[r];
-                roff += (size_t)hc[world + r];
-            }
-            if (hc[rank] > 0)
-            {
-                CSLAM_HIP_TRY(hipMemcpyAsync(dRecvBuf.get() + roff * rec, dSendBuf.get() + soff * rec,
-                                             (size_t)hc[rank] * rec * sizeof(T), hipMemcpyDeviceToDevice, stream));
-            }
+            CSLAM_HIP_TRY(hipMemcpyAsync(rbuf + roff * rec, sbuf + soff * rec, (size_t)hc[rank] * rec * sizeof(T),
+                                         hipMemcpyDeviceToDevice, stream));
         }
-        if ((rc = c->group_start()))
+        int rc = c->group_start();
+        if (rc)
         {
             return rc;
         }
-        size_t soff = 0, roff = 0;
         for (int r = 0; r < world && rc == CSLAM_OK; r++)
         {
             const size_t sc = (size_t)hc[r], rcv = (size_t)hc[world + r];
-            if (r != rank)
+            pf_exchange_offsets(hc, world, r, &soff, &roff);
+            if (r != rank && sc > 0)
             {
-                if (sc > 0)
-                {
-                    rc = c->send(dSendBuf.get() + soff * rec, sc * rec, dt, sizeof(T), r, stream);
-                }
-                if (rcv > 0 && rc == CSLAM_OK)
-                {
-                    rc = c->recv(dRecvBuf.get() + roff * rec, rcv * rec, dt, sizeof(T), r, stream);
-                }
+                rc = c->send(sbuf + soff * rec, sc * rec, dt, sizeof(T), r, stream);
             }
-            soff += sc;
-            roff += rcv;
+            if (r != rank && rcv > 0 && rc == CSLAM_OK)
+            {
+                rc = c->recv(rbuf + roff * rec, rcv * rec, dt, sizeof(T), r, stream);
+            }
         }
         const int rc_end = c->group_end(stream); // (closed on the failure path too)
         if (rc || rc_end)
         {
             return rc ? rc : rc_end;
         }
-        hipLaunchKernelGGL(pf_unpack_kernel<T>, dim3(L), dim3(256), 0, stream, store(), (const int*)nullptr, L,
-                           dRecvBuf.get());
-        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_TRY(launch_unpack(nullptr, L, rbuf));
         return set_uniform_weight(1.0 / (double)N); // PF.cpp:495-499
     }
 
@@ -1221,30 +664,22 @@ struct Pf : PfBase
     {
         if (n_send)
         {
-            *n_send = last_n_send;
+            *n_send = sh.last_n_send;
         }
         if (counts)
         {
-            for (size_t i = 0; i < last_counts.size(); i++)
-            {
-                counts[i] = last_counts[i];
-            }
+            std::copy(sh.last_counts.begin(), sh.last_counts.end(), counts);
         }
-        if (send_idx && last_n_send > 0)
+        if (send_idx && sh.last_n_send > 0)
         {
-            if (cap < last_n_send)
+            if (cap < sh.last_n_send)
             {
-                return fail(CSLAM_ERR_BAD_ARG, "debug_last_exchange: capacity %d < %d", cap, last_n_send);
+                return fail(CSLAM_ERR_BAD_ARG, "debug_last_exchange: capacity %d < %d", cap, sh.last_n_send);
             }
-            int rc = use_device();
-            if (rc)
-            {
-                return rc;
-            }
-            CSLAM_HIP_TRY(hipMemcpyAsync(send_idx, dSendIdx.get(), (size_t)last_n_send * sizeof(int),
+            CSLAM_TRY(use_device());
+            CSLAM_HIP_TRY(hipMemcpyAsync(send_idx, sh.plan.sendIdx.get(), (size_t)sh.last_n_send * sizeof(int),
                                          hipMemcpyDeviceToHost, stream));
             CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            stage_inflight = 0;
         }
         return CSLAM_OK;
     }
@@ -1252,49 +687,16 @@ struct Pf : PfBase
     // plan (sums, normalise, Neff, decision, keep[]) -> gather -> copy back + w = 1/N, the last two gated by a device flag
     int launch_resample(const T* d_select, double n_eff, int status)
     {
-        assoc_moved = true; // (whether it resamples is decided on the device)
+        assoc.memo.moved(); // (whether it resamples is decided on the device)
         hipLaunchKernelGGL(pf_resample_plan_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, d_select, n_eff,
-                           status, dCum.get(), dKeep.get(), dInfo.get(), dEnable.get());
+                           status, rs.cum.get(), rs.keep.get(), rs.info.get(), rs.enable.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        const dim3 ggrid(13 + 6 * store().nf, (np + 255) / 256);
+        const dim3 ggrid(13 + 6 * nf, (np + 255) / 256);
         const T    w_new = (T)(1.0 / (double)np);
-        PfStore<T> twin  = store();
-        twin.xv          = dXv2.get();
-        twin.pv          = dPv2.get();
-        twin.xf          = dXF2.get();
-        twin.pf          = dPF2.get();
-        hipLaunchKernelGGL(pf_gather_move_kernel<T>, ggrid, dim3(256), 0, stream, store(), twin, dKeep.get(),
-                           dEnable.get(), w_new);
+        hipLaunchKernelGGL(pf_gather_move_kernel<T>, ggrid, dim3(256), 0, stream, store(), store_of(twin), rs.keep.get(),
+                           rs.enable.get(), w_new);
         CSLAM_HIP_TRY(hipGetLastError());
-        std::swap(dXv, dXv2); // the twin set is the store now (whether particles moved or were copied in place)
-        std::swap(dPv, dPv2);
-        std::swap(dXF, dXF2);
-        std::swap(dPF, dPF2);
-        return CSLAM_OK;
-    }
-
-    int ensure_resample_buffers()
-    {
-        if (dSel.get())
-        {
-            return CSLAM_OK;
-        }
-        DevBuf<T>         sel, cum;
-        DevBuf<int>       keep, enable;
-        DevBuf<double>    info;
-        PinnedBuf<double> hinfo;
-        int               rc = sel.alloc((size_t)np);
-        if (rc || (rc = cum.alloc((size_t)np)) || (rc = keep.alloc((size_t)np)) || (rc = enable.alloc(1)) ||
-            (rc = info.alloc_zeroed(4, stream)) || (rc = hinfo.alloc(4)))
-        {
-            return rc;
-        }
-        dSel    = std::move(sel);
-        dCum    = std::move(cum);
-        dKeep   = std::move(keep);
-        dEnable = std::move(enable);
-        dInfo   = std::move(info);
-        hInfo   = std::move(hinfo);
+        std::swap(cur, twin); // the twin set is the store now (whether particles moved or were copied in place)
         return CSLAM_OK;
     }
 
@@ -1308,50 +710,34 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_observation_step: bad arguments");
         }
-        int rc = use_device();
-        if (rc || (rc = check_idf(idf, m, "pf_observation_step")) || (rc = ensure_m(std::max(m, 1))) ||
-            (rc = ensure_resample_buffers()))
-        {
-            return rc;
-        }
-        const size_t zb = (size_t)2 * m * sizeof(T), ib = (size_t)m * sizeof(int), nb = (size_t)3 * np * sizeof(T);
-        const size_t off_sel = off_normals() + nb, bytes = off_sel + (size_t)np * sizeof(T);
-        char*        slot    = nullptr;
-        if ((rc = stage_slot_for(bytes, &slot)))
-        {
-            return rc;
-        }
-        if (m > 0)
-        {
-            std::memcpy(slot, Z, zb);
-            std::memcpy(slot + off_idf(), idf, ib);
-            std::memcpy(slot + off_normals(), normals, nb);
-        }
-        std::memcpy(slot + off_sel, select, (size_t)np * sizeof(T));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_idf(idf, m, "pf_observation_step"));
+        CSLAM_TRY(ensure_m(std::max(m, 1)));
+        CSLAM_TRY(rs.ensure(np, stream));
+        const PfObsLayout<T>& lay = obs.layout();
         // (zero-copy -- the kernels reading the pinned slot over the host link -- was tried instead of this staged copy:
         // 13.7 k instead of 15.0 k steps/s)
-        staged.clear();
         // (a small kernel reading the pinned slot in place of this copy command: 19.6 k instead of 19.9 k steps/s)
         // (a second stream for this copy, double-buffered inputs and event hand-overs so that it runs under the previous
         // step's kernels was tried: 14.8 k instead of 16.7 k steps/s -- four more runtime calls per step cost more host
         // time than the 10 us of stream time they free)
-        CSLAM_HIP_TRY(hipMemcpyAsync(dObs.get(), slot, bytes, hipMemcpyHostToDevice, stream));
-        if ((rc = stage_commit()))
-        {
-            return rc;
-        }
+        CSLAM_TRY(obs.receive(ring, lay.bytes_step(), stream, [&](char* slot) {
+            if (m > 0)
+            {
+                std::memcpy(slot, Z, lay.bytes_z(m));
+                std::memcpy(slot + lay.off_idf(), idf, (size_t)m * sizeof(int));
+                std::memcpy(slot + lay.off_normals(), normals, (size_t)3 * np * sizeof(T));
+            }
+            std::memcpy(slot + lay.off_select(), select, (size_t)np * sizeof(T));
+        }));
         return launch_observation_step(v, swa, Qv, wb, dt, m, idf, Rv, n_eff, status);
     }
 
-    // the launches of one observation step behind its inputs in dObs (Z | idf | normals | select); idf: the host copy
+    // the launches of one observation step behind its inputs in the staging area (Z | idf | normals | select); idf: the
+    // host copy
     int launch_observation_step(double v, double swa, const void* Qv, double wb, double dt, int m, const int* idf,
                                 const void* Rv, double n_eff, int status)
     {
-        const size_t off_sel = off_normals() + (size_t)3 * np * sizeof(T);
-        char*      base = reinterpret_cast<char*>(dObs.get());
-        const T*   sZ   = reinterpret_cast<const T*>(base);
-        const int* sIdf = reinterpret_cast<const int*>(base + off_idf());
-        const T*   sNrm = reinterpret_cast<const T*>(base + off_normals());
         const T* Q = static_cast<const T*>(Qv);
         const T* R = static_cast<const T*>(Rv);
         if (m > 0) // predict rides inside the proposal kernel (which overwrites xv / Pv anyway)
@@ -1359,60 +745,62 @@ struct Pf : PfBase
             const PfPredict<T> pr{1, (T)v, (T)swa, Q[0], Q[1], Q[2], Q[3], (T)wb, (T)dt};
             // ... and so does the feature update, unless an observation list names a feature twice (the separate kernel
             // then updates it twice from the same old value, last writer wins: kept as it was)
-            bool dup = false;
-            for (int a = 0; a < m && !dup; a++)
-            {
-                for (int c = a + 1; c < m; c++)
-                {
-                    if (idf[a] == idf[c])
-                    {
-                        dup = true;
-                        break;
-                    }
-                }
-            }
-            const int fu = dup ? 0 : ((quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 1 : 2);
-            hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream, store(), sZ, sIdf,
-                               m, R[0], R[1], R[2], R[3], sNrm, pr, fu);
-            CSLAM_HIP_TRY(hipGetLastError());
+            const int fu = pf_has_duplicate(idf, m) ? 0 : fused_update_gain();
+            CSLAM_TRY(launch_proposal(m, R, pr, fu));
             if (fu == 0)
             {
-                hipLaunchKernelGGL(pf_feature_update_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(), sZ,
-                                   sIdf, m, R[0], R[1], R[2], R[3], (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1);
-                CSLAM_HIP_TRY(hipGetLastError());
+                CSLAM_TRY(launch_feature_update(m, R));
             }
         }
         else
         {
-            hipLaunchKernelGGL(pf_predict_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), (T)v, (T)swa, Q[0],
-                               Q[1], Q[2], Q[3], (T)wb, (T)dt);
-            CSLAM_HIP_TRY(hipGetLastError());
+            CSLAM_TRY(launch_predict(v, swa, Q, wb, dt));
         }
-        return launch_resample(reinterpret_cast<const T*>(base + off_sel), n_eff, status);
+        return launch_resample(obs.dSelect(), n_eff, status);
     }
 
     int resample_stats(double* calls, double* resamples, double* last_neff) override
     {
-        int rc = use_device();
-        if (rc || (rc = ensure_resample_buffers()))
-        {
-            return rc;
-        }
-        CSLAM_HIP_TRY(hipMemcpyAsync(hInfo.get(), dInfo.get(), 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(rs.ensure(np, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(rs.hInfo.get(), rs.info.get(), 4 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        stage_inflight = 0;
         if (last_neff)
         {
-            *last_neff = hInfo[0];
+            *last_neff = rs.hInfo[0];
         }
         if (calls)
         {
-            *calls = hInfo[2];
+            *calls = rs.hInfo[2];
         }
         if (resamples)
         {
-            *resamples = hInfo[3];
+            *resamples = rs.hInfo[3];
         }
+        return CSLAM_OK;
+    }
+
+    // column i of an np-column array <-> a contiguous host vector of `rows` scalars (nothing for a null vector or no rows)
+    int copy_column(void* host, T* dev, int i, size_t rows, bool to_device)
+    {
+        const size_t s = sizeof(T), pitch = (size_t)np * s;
+        if (host && rows > 0 && to_device)
+        {
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(dev + i, pitch, host, s, s, rows, hipMemcpyHostToDevice, stream));
+        }
+        else if (host && rows > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpy2DAsync(host, s, dev + i, pitch, s, rows, hipMemcpyDeviceToHost, stream));
+        }
+        return CSLAM_OK;
+    }
+    int copy_particle(int i, void* Xv, void* Pv, void* XF, void* PF, int nfeat, bool to_device)
+    {
+        CSLAM_TRY(copy_column(Xv, cur.xv.get(), i, 3, to_device));
+        CSLAM_TRY(copy_column(Pv, cur.pv.get(), i, 9, to_device));
+        CSLAM_TRY(copy_column(XF, cur.xf.get(), i, (size_t)2 * nfeat, to_device));
+        CSLAM_TRY(copy_column(PF, cur.pf.get(), i, (size_t)4 * nfeat, to_device));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
 
@@ -1422,36 +810,12 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_get_particle: index %d", i);
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        const size_t s = sizeof(T), pitch = (size_t)np * s;
+        CSLAM_TRY(use_device());
         if (w)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(w, dW.get() + i, s, hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(w, dW.get() + i, sizeof(T), hipMemcpyDeviceToHost, stream));
         }
-        if (Xv)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(Xv, s, dXv.get() + i, pitch, s, 3, hipMemcpyDeviceToHost, stream));
-        }
-        if (Pv)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(Pv, s, dPv.get() + i, pitch, s, 9, hipMemcpyDeviceToHost, stream));
-        }
-        if (XF && nf > 0)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(XF, s, dXF.get() + i, pitch, s, (size_t)2 * nf, hipMemcpyDeviceToHost,
-                                           stream));
-        }
-        if (PF && nf > 0)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(PF, s, dPF.get() + i, pitch, s, (size_t)4 * nf, hipMemcpyDeviceToHost,
-                                           stream));
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        return CSLAM_OK;
+        return copy_particle(i, Xv, Pv, XF, PF, nf, false);
     }
 
     int set_particle(int i, const void* w, const void* Xv, const void* Pv, const void* XF, const void* PF,
@@ -1461,108 +825,30 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_set_particle: index %d / nf %d", i, nfeat);
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        const size_t s = sizeof(T), pitch = (size_t)np * s;
-        assoc_moved    = true;
+        CSLAM_TRY(use_device());
+        assoc.memo.moved();
         if (w)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(dW.get() + i, w, s, hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(dW.get() + i, w, sizeof(T), hipMemcpyHostToDevice, stream));
         }
-        if (Xv)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dXv.get() + i, pitch, Xv, s, s, 3, hipMemcpyHostToDevice, stream));
-        }
-        if (Pv)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dPv.get() + i, pitch, Pv, s, s, 9, hipMemcpyHostToDevice, stream));
-        }
-        if (XF && nfeat > 0)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dXF.get() + i, pitch, XF, s, s, (size_t)2 * nfeat, hipMemcpyHostToDevice,
-                                           stream));
-        }
-        if (PF && nfeat > 0)
-        {
-            CSLAM_HIP_TRY(hipMemcpy2DAsync(dPF.get() + i, pitch, PF, s, s, (size_t)4 * nfeat, hipMemcpyHostToDevice,
-                                           stream));
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        CSLAM_TRY(copy_particle(i, const_cast<void*>(Xv), const_cast<void*>(Pv), const_cast<void*>(XF),
+                                const_cast<void*>(PF), nfeat, true)); // (read only in this direction)
         nf = nfeat; // every particle of the store carries the same number of features
         return CSLAM_OK;
     }
 
     // ------------------------------------------------------------------------------------------------
     // The read path: best particle, mixture moments, all features.  Every call queues its launches behind whatever is
-    // on the stream, brings ONE block back through hEst (pinned) and synchronises; the store is only read.
+    // on the stream, brings ONE block back through est.hEst (pinned) and synchronises; the store is only read.
     // ------------------------------------------------------------------------------------------------
-    DevBuf<double>  dEstPart;               // per-chunk partials of passes 1 and 2
-    DevBuf<double>  dEstOut, dEstLocal;     // output block: kEstOutHdr doubles, then the T record [w, Xv, Pv, XF, PF]
-    DevBuf<double>  dEstSum, dEstSumAll;    // this rank's summary / every rank's (sharded estimate)
-    DevBuf<double>  dBestHdrAll;            // every rank's pick (sharded best particle)
-    DevBuf<T>       dBestRecAll, dEstFeat;  // every rank's picked record; the transposed features
-    PinnedBuf<char> hEst;
-
-    template <typename B>
-    int est_grow(B& buf, size_t count)
+    int est_grow_common(size_t part_count, size_t od)
     {
-        if (buf.count() >= count)
-        {
-            return CSLAM_OK;
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still uses the old buffer
-        B nb;
-        CSLAM_TRY(nb.alloc(count));
-        buf = std::move(nb);
-        return CSLAM_OK;
+        CSLAM_TRY(est.grow(est.part, part_count, stream));
+        CSLAM_TRY(est.grow(est.out, od, stream));
+        return est.grow(est.hEst, od * sizeof(double), stream);
     }
-    int est_chunks() const
-    {
-        return (np + kEstChunk - 1) / kEstChunk;
-    }
-    size_t est_out_doubles() const
-    {
-        return (size_t)kEstOutHdr + ((size_t)(13 + 6 * nf) * sizeof(T) + 7) / 8;
-    }
-    static T* est_rec(double* block)
-    {
-        return reinterpret_cast<T*>(block + kEstOutHdr);
-    }
-    // header + the first rec_len scalars of the record of `block` -> hEst, one copy, synchronised
-    int est_fetch(const double* block, size_t rec_len)
-    {
-        const size_t bytes = (size_t)kEstOutHdr * sizeof(double) + rec_len * sizeof(T);
-        CSLAM_HIP_TRY(hipMemcpyAsync(hEst.get(), block, bytes, hipMemcpyDeviceToHost, stream));
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        return CSLAM_OK;
-    }
-    void est_scatter(bool map, void* w, void* Xv, void* Pv, void* XF, void* PF) const
-    {
-        const T* rec = reinterpret_cast<const T*>(hEst.get() + (size_t)kEstOutHdr * sizeof(double));
-        if (w)
-        {
-            std::memcpy(w, rec, sizeof(T));
-        }
-        if (Xv)
-        {
-            std::memcpy(Xv, rec + 1, 3 * sizeof(T));
-        }
-        if (Pv)
-        {
-            std::memcpy(Pv, rec + 4, 9 * sizeof(T));
-        }
-        if (map && XF)
-        {
-            std::memcpy(XF, rec + 13, (size_t)2 * nf * sizeof(T));
-        }
-        if (map && PF)
-        {
-            std::memcpy(PF, rec + 13 + 2 * nf, (size_t)4 * nf * sizeof(T));
-        }
-    }
+    int    est_chunks() const { return (np + kEstChunk - 1) / kEstChunk; }
+    size_t est_out_doubles() const { return (size_t)kEstOutHdr + ((size_t)(13 + 6 * nf) * sizeof(T) + 7) / 8; }
     int est_comm_ok(Comm* c, const char* who)
     {
         if (c && !c->loop && !rccl())
@@ -1578,78 +864,61 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_best_particle: pick %d is neither CSLAM_PF_PICK_MAX nor _MIN", pick);
         }
-        int rc = use_device();
-        if (rc || (rc = est_comm_ok(c, "pf_best_particle_sharded")))
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(est_comm_ok(c, "pf_best_particle_sharded"));
         const int    nch = est_chunks(), len = 13 + 6 * nf, world = c ? c->world : 1;
         const size_t od  = est_out_doubles();
         // (everything that can fail is allocated before the first collective)
-        if ((rc = est_grow(dEstPart, (size_t)nch * kEstP1)) || (rc = est_grow(dEstOut, od)) ||
-            (rc = est_grow(hEst, od * sizeof(double))))
+        CSLAM_TRY(est_grow_common((size_t)nch * kEstP1, od));
+        if (c)
         {
-            return rc;
+            CSLAM_TRY(est.grow(est.local, od, stream));
+            CSLAM_TRY(est.grow(est.bestHdrAll, (size_t)world * kEstOutHdr, stream));
+            CSLAM_TRY(est.grow(est.bestRecAll, (size_t)world * len, stream));
         }
-        if (c && ((rc = est_grow(dEstLocal, od)) || (rc = est_grow(dBestHdrAll, (size_t)world * kEstOutHdr)) ||
-                  (rc = est_grow(dBestRecAll, (size_t)world * len))))
-        {
-            return rc;
-        }
-        double* local = c ? dEstLocal.get() : dEstOut.get();
-        hipLaunchKernelGGL(pf_est_pass1_kernel<T>, dim3(nch), dim3(256), 0, stream, store(), dEstPart.get());
+        double* local = c ? est.local.get() : est.out.get();
+        hipLaunchKernelGGL(pf_est_pass1_kernel<T>, dim3(nch), dim3(256), 0, stream, store(), est.part.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(pf_best_finish_kernel<T>, dim3(1), dim3(256), 0, stream, store(), dEstPart.get(), nch, pick,
-                           c ? (long long)c->rank * np : 0LL, local, est_rec(local));
+        hipLaunchKernelGGL(pf_best_finish_kernel<T>, dim3(1), dim3(256), 0, stream, store(), est.part.get(), nch, pick,
+                           c ? (long long)c->rank * np : 0LL, local, est.rec(local));
         CSLAM_HIP_TRY(hipGetLastError());
         if (c)
         {
             const ncclDataType_t dt = (sizeof(T) == 4) ? ncclFloat : ncclDouble;
-            if ((rc = c->all_gather(local, dBestHdrAll.get(), (size_t)kEstOutHdr, ncclDouble, sizeof(double), stream)) ||
-                (rc = c->all_gather(est_rec(local), dBestRecAll.get(), (size_t)len, dt, sizeof(T), stream)))
-            {
-                return rc;
-            }
-            hipLaunchKernelGGL(pf_best_combine_kernel<T>, dim3(1), dim3(256), 0, stream, dBestHdrAll.get(),
-                               dBestRecAll.get(), world, len, pick, dEstOut.get(), est_rec(dEstOut.get()));
+            CSLAM_TRY(c->all_gather(local, est.bestHdrAll.get(), (size_t)kEstOutHdr, ncclDouble, sizeof(double), stream));
+            CSLAM_TRY(c->all_gather(est.rec(local), est.bestRecAll.get(), (size_t)len, dt, sizeof(T), stream));
+            hipLaunchKernelGGL(pf_best_combine_kernel<T>, dim3(1), dim3(256), 0, stream, est.bestHdrAll.get(),
+                               est.bestRecAll.get(), world, len, pick, est.out.get(), est.rec(est.out.get()));
             CSLAM_HIP_TRY(hipGetLastError());
         }
         const bool map = nf > 0 && (XF || PF);
-        if ((rc = est_fetch(dEstOut.get(), map ? (size_t)len : 13)))
-        {
-            return rc;
-        }
+        CSLAM_TRY(est.fetch(est.out.get(), map ? (size_t)len : 13, stream));
         if (index)
         {
-            *index = (long long)reinterpret_cast<const double*>(hEst.get())[2];
+            *index = (long long)est.h_hdr()[2];
         }
-        est_scatter(map, w, Xv, Pv, XF, PF);
+        est.scatter(map, nf, w, Xv, Pv, XF, PF);
         return CSLAM_OK;
     }
 
     int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF) override
     {
-        int rc = use_device();
-        if (rc || (rc = est_comm_ok(c, "pf_estimate_sharded")))
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(est_comm_ok(c, "pf_estimate_sharded"));
         const bool   map = nf > 0 && (XF || PF);
         const int    nch = est_chunks(), world = c ? c->world : 1;
         const int    stride = kEstSumHdr + (map ? kEstSumFeat * nf : 0);
-        const size_t od     = est_out_doubles();
-        if ((rc = est_grow(dEstPart, (size_t)nch * (kEstP1 + kEstP2Pose + (map ? (size_t)kEstP2Feat * nf : 0)))) ||
-            (rc = est_grow(dEstOut, od)) || (rc = est_grow(hEst, od * sizeof(double))))
+        CSLAM_TRY(est_grow_common((size_t)nch * (kEstP1 + kEstP2Pose + (map ? (size_t)kEstP2Feat * nf : 0)),
+                                  est_out_doubles()));
+        if (c)
         {
-            return rc;
+            CSLAM_TRY(est.grow(est.sum, (size_t)stride, stream));
+            CSLAM_TRY(est.grow(est.sumAll, (size_t)world * stride, stream));
         }
-        if (c && ((rc = est_grow(dEstSum, (size_t)stride)) || (rc = est_grow(dEstSumAll, (size_t)world * stride))))
-        {
-            return rc;
-        }
-        double* p1 = dEstPart.get();
+        double* p1 = est.part.get();
         double* p2 = p1 + (size_t)nch * kEstP1;
         double* pm = map ? p2 + (size_t)nch * kEstP2Pose : nullptr;
+        double* out = est.out.get();
         const int fgroups = map ? (nf + kEstFeatPerWg - 1) / kEstFeatPerWg : 0;
         const int fblocks = map ? (nf + 255) / 256 : 0;
         hipLaunchKernelGGL(pf_est_pass1_kernel<T>, dim3(nch), dim3(256), 0, stream, store(), p1);
@@ -1657,32 +926,25 @@ struct Pf : PfBase
         hipLaunchKernelGGL(pf_est_pass2_kernel<T>, dim3(nch, 1 + fgroups), dim3(256), 0, stream, store(), p1, nch, p2, pm);
         CSLAM_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(pf_est_finish_kernel<T>, dim3(1 + fblocks), dim3(256), 0, stream, store(), p1, p2, pm, nch,
-                           c ? dEstSum.get() : nullptr, dEstOut.get(), est_rec(dEstOut.get()));
+                           c ? est.sum.get() : nullptr, out, est.rec(out));
         CSLAM_HIP_TRY(hipGetLastError());
         if (c)
         {
-            if ((rc = c->all_gather(dEstSum.get(), dEstSumAll.get(), (size_t)stride, ncclDouble, sizeof(double), stream)))
-            {
-                return rc;
-            }
-            hipLaunchKernelGGL(pf_est_combine_kernel<T>, dim3(1 + fblocks), dim3(256), 0, stream, dEstSumAll.get(), world,
-                               stride, nf, map ? 1 : 0, dEstOut.get(), est_rec(dEstOut.get()));
+            CSLAM_TRY(c->all_gather(est.sum.get(), est.sumAll.get(), (size_t)stride, ncclDouble, sizeof(double), stream));
+            hipLaunchKernelGGL(pf_est_combine_kernel<T>, dim3(1 + fblocks), dim3(256), 0, stream, est.sumAll.get(), world,
+                               stride, nf, map ? 1 : 0, out, est.rec(out));
             CSLAM_HIP_TRY(hipGetLastError());
         }
-        if ((rc = est_fetch(dEstOut.get(), map ? (size_t)(13 + 6 * nf) : 13)))
-        {
-            return rc;
-        }
-        const double* hdr = reinterpret_cast<const double*>(hEst.get());
+        CSLAM_TRY(est.fetch(out, map ? (size_t)(13 + 6 * nf) : 13, stream));
         if (w_sum)
         {
-            *w_sum = hdr[0];
+            *w_sum = est.h_hdr()[0];
         }
         if (neff)
         {
-            *neff = hdr[1];
+            *neff = est.h_hdr()[1];
         }
-        est_scatter(map, nullptr, Xv, Pv, XF, PF);
+        est.scatter(map, nf, nullptr, Xv, Pv, XF, PF);
         return CSLAM_OK;
     }
 
@@ -1694,79 +956,22 @@ struct Pf : PfBase
             return rc;
         }
         const size_t count = (size_t)2 * nf * np;
-        if ((rc = est_grow(dEstFeat, count)) || (rc = est_grow(hEst, count * sizeof(T))))
-        {
-            return rc;
-        }
+        CSLAM_TRY(est.grow(est.feat, count, stream));
+        CSLAM_TRY(est.grow(est.hEst, count * sizeof(T), stream));
         hipLaunchKernelGGL(pf_all_features_kernel<T>, dim3((np + 63) / 64, (2 * nf + 63) / 64), dim3(256), 0, stream,
-                           store(), dEstFeat.get());
+                           store(), est.feat.get());
         CSLAM_HIP_TRY(hipGetLastError());
-        CSLAM_HIP_TRY(hipMemcpyAsync(hEst.get(), dEstFeat.get(), count * sizeof(T), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpyAsync(est.hEst.get(), est.feat.get(), count * sizeof(T), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        std::memcpy(XF_all, hEst.get(), count * sizeof(T));
+        std::memcpy(XF_all, est.hEst.get(), count * sizeof(T));
         return CSLAM_OK;
     }
 
     // ------------------------------------------------------------------------------------------------
     // Per-particle gated nearest-neighbour association (EKF.cpp:131-144, 235-326 on each particle's own state) and the
-    // consumers that read its table.  The tables belong to the handle and describe the LAST associate call: its
-    // observations (kept on the host to recognise them again), the particle order and the map size of that moment.
+    // consumers that read its table.  The tables belong to the handle and describe the LAST associate call
+    // (assoc.memo): its observations, the particle order and the map size of that moment.
     // ------------------------------------------------------------------------------------------------
-    DevBuf<T>         dAPartNd, dAPartNis, dARawNd;
-    DevBuf<int>       dAPartJ, dARawIdf, dARawKind, dAIdf, dAKind;
-    DevBuf<double>    dASummary;
-    size_t            assoc_part_cap = 0; // entries of the three partial tables
-    int               assoc_mcap     = 0; // observations the (m x np) tables and the summary hold
-    int               assoc_m        = -1; // -1: associate has not been called
-    int               assoc_nf       = 0;
-    bool              assoc_moved    = false; // particles changed slots (resample, unpack, set_particle) since associate
-    std::vector<char> assoc_Z;            // the 2 * assoc_m observation scalars of the last associate
-
-    // all-or-nothing growth (device_owners.hpp): new buffers into locals first, members replaced only when all exist
-    int ensure_assoc(int m, int nchunks)
-    {
-        const size_t need_part = (size_t)std::max(nchunks, 1) * m * np;
-        if (need_part > assoc_part_cap)
-        {
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still reads the old partials
-            DevBuf<T>   nd, nis;
-            DevBuf<int> pj;
-            int         rc = nd.alloc(need_part);
-            if (rc || (rc = nis.alloc(need_part)) || (rc = pj.alloc(need_part)))
-            {
-                return rc;
-            }
-            dAPartNd       = std::move(nd);
-            dAPartNis      = std::move(nis);
-            dAPartJ        = std::move(pj);
-            assoc_part_cap = need_part;
-        }
-        if (m > assoc_mcap)
-        {
-            const int    newm = std::max(m, std::max(64, 2 * assoc_mcap));
-            const size_t cnt  = (size_t)newm * np;
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-            DevBuf<T>      rnd;
-            DevBuf<int>    ridf, rkind, idf, kind;
-            DevBuf<double> sum;
-            int            rc = rnd.alloc(cnt);
-            if (rc || (rc = ridf.alloc(cnt)) || (rc = rkind.alloc(cnt)) || (rc = idf.alloc(cnt)) ||
-                (rc = kind.alloc(cnt)) || (rc = sum.alloc((size_t)newm * 4)))
-            {
-                return rc;
-            }
-            dARawNd    = std::move(rnd);
-            dARawIdf   = std::move(ridf);
-            dARawKind  = std::move(rkind);
-            dAIdf      = std::move(idf);
-            dAKind     = std::move(kind);
-            dASummary  = std::move(sum);
-            assoc_mcap = newm;
-            assoc_m    = -1; // the old tables are gone
-        }
-        return CSLAM_OK;
-    }
-
     int associate(const void* Z, int m, const void* Rv, double gate1, double gate2) override
     {
         if (m < 0 || m > 65535 || !Rv || (m > 0 && !Z)) // (one grid row per observation)
@@ -1777,107 +982,86 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_associate: gates must be finite (gate1=%g, gate2=%g)", gate1, gate2);
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
         const int nchunks = (nf + kPfAssocFeatChunk - 1) / kPfAssocFeatChunk;
         if (m > 0)
         {
-            if ((rc = ensure_assoc(m, nchunks)) || (rc = stage(Z, m, nullptr)))
-            {
-                return rc;
-            }
-            const T*   R = static_cast<const T*>(Rv);
+            CSLAM_TRY(assoc.ensure(m, nchunks, np, stream));
+            CSLAM_TRY(stage(Z, m, nullptr));
+            const T*   R  = static_cast<const T*>(Rv);
             const int  pb = (np + 63) / 64;
+            const auto& p = assoc.part;
+            const auto& t = assoc.tab;
             if (nchunks > 0)
             {
                 hipLaunchKernelGGL(pf_assoc_scan_kernel<T>, dim3(pb, nchunks, (m + kPfAssocObsChunk - 1) / kPfAssocObsChunk),
-                                   dim3(64), 0, stream, store(), dObs.get(), m, R[0], R[1], R[2], R[3], (T)gate1,
-                                   dAPartNd.get(), dAPartJ.get(), dAPartNis.get());
+                                   dim3(64), 0, stream, store(), obs.z(), m, R[0], R[1], R[2], R[3], (T)gate1,
+                                   p.nd.get(), p.j.get(), p.nis.get());
                 CSLAM_HIP_TRY(hipGetLastError());
             }
-            hipLaunchKernelGGL(pf_assoc_merge_kernel<T>, dim3(pb, m), dim3(64), 0, stream, np, m, nchunks, dAPartNd.get(),
-                               dAPartJ.get(), dAPartNis.get(), (T)gate2, dARawIdf.get(), dARawKind.get(), dARawNd.get());
+            hipLaunchKernelGGL(pf_assoc_merge_kernel<T>, dim3(pb, m), dim3(64), 0, stream, np, m, nchunks, p.nd.get(),
+                               p.j.get(), p.nis.get(), (T)gate2, t.rawIdf.get(), t.rawKind.get(), t.rawNd.get());
             CSLAM_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pf_assoc_resolve_kernel<T>, dim3(pb, m), dim3(64), 0, stream, np, m, dARawIdf.get(),
-                               dARawKind.get(), dARawNd.get(), dAIdf.get(), dAKind.get());
+            hipLaunchKernelGGL(pf_assoc_resolve_kernel<T>, dim3(pb, m), dim3(64), 0, stream, np, m, t.rawIdf.get(),
+                               t.rawKind.get(), t.rawNd.get(), t.idf.get(), t.kind.get());
             CSLAM_HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pf_assoc_summary_kernel<T>, dim3(m), dim3(256), 0, stream, dW.get(), np, dAKind.get(),
-                               dASummary.get());
+            hipLaunchKernelGGL(pf_assoc_summary_kernel<T>, dim3(m), dim3(256), 0, stream, dW.get(), np, t.kind.get(),
+                               t.summary.get());
             CSLAM_HIP_TRY(hipGetLastError());
         }
-        assoc_m     = m;
-        assoc_nf    = nf;
-        assoc_moved = false;
-        assoc_Z.clear();
-        if (m > 0)
-        {
-            assoc_Z.assign(static_cast<const char*>(Z), static_cast<const char*>(Z) + (size_t)2 * m * sizeof(T));
-        }
+        assoc.memo.associated(Z, m, nf);
         return CSLAM_OK;
     }
 
     int get_association(int* idf, int* kind, double* summary) override
     {
-        if (assoc_m < 0)
+        const int am = assoc.memo.m();
+        if (am < 0)
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_get_association: cslam_pf_associate has not been called");
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        const size_t cnt = (size_t)assoc_m * np;
+        CSLAM_TRY(use_device());
+        const size_t cnt = (size_t)am * np;
         if (idf && cnt)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(idf, dAIdf.get(), cnt * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(idf, assoc.tab.idf.get(), cnt * sizeof(int), hipMemcpyDeviceToHost, stream));
         }
         if (kind && cnt)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(kind, dAKind.get(), cnt * sizeof(int), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(kind, assoc.tab.kind.get(), cnt * sizeof(int), hipMemcpyDeviceToHost, stream));
         }
-        if (summary && assoc_m)
+        if (summary && am)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(summary, dASummary.get(), (size_t)assoc_m * 4 * sizeof(double),
+            CSLAM_HIP_TRY(hipMemcpyAsync(summary, assoc.tab.summary.get(), (size_t)am * 4 * sizeof(double),
                                          hipMemcpyDeviceToHost, stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
     }
 
-    // the consumers take the observations of the last associate: anything else would pair a table with the wrong scan
+    // the texts of PfAssocMemo's refusals
     int check_assoc_inputs(const void* Z, int m, const int* use, const char* who)
     {
-        if (assoc_m < 0)
+        int i = 0;
+        switch (assoc.memo.check(Z, m, nf, use, &i))
         {
+        case PfAssocRefusal::none:
+            return CSLAM_OK;
+        case PfAssocRefusal::never_associated:
             return fail(CSLAM_ERR_BAD_ARG, "%s: cslam_pf_associate has not been called", who);
-        }
-        if (assoc_moved)
-        {
+        case PfAssocRefusal::moved:
             return fail(CSLAM_ERR_BAD_ARG,
                         "%s: particles were resampled, unpacked or set since cslam_pf_associate (its table is per slot)", who);
-        }
-        if (m != assoc_m || (m > 0 && std::memcmp(assoc_Z.data(), Z, (size_t)2 * m * sizeof(T)) != 0))
-        {
+        case PfAssocRefusal::other_scan:
             return fail(CSLAM_ERR_BAD_ARG, "%s: Z / m (%d) are not those of the last cslam_pf_associate (m=%d)", who, m,
-                        assoc_m);
-        }
-        if (nf < assoc_nf)
-        {
+                        assoc.memo.m());
+        case PfAssocRefusal::map_shrank:
             return fail(CSLAM_ERR_BAD_ARG, "%s: the map shrank (%d features) since cslam_pf_associate (%d)", who, nf,
-                        assoc_nf);
+                        assoc.memo.nf());
+        case PfAssocRefusal::bad_use:
+            break;
         }
-        for (int i = 0; i < m; i++)
-        {
-            if (use[i] != 0 && use[i] != 1)
-            {
-                return fail(CSLAM_ERR_BAD_ARG, "%s: use[%d]=%d is neither 0 nor 1", who, i, use[i]);
-            }
-        }
-        return CSLAM_OK;
+        return fail(CSLAM_ERR_BAD_ARG, "%s: use[%d]=%d is neither 0 nor 1", who, i, use[i]);
     }
 
     int sample_proposal_assoc(const void* Z, int m, const void* Rv, const void* normals, const int* use,
@@ -1887,19 +1071,10 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_assoc: bad arguments");
         }
-        int rc = use_device();
-        // (the mask travels in the staging area's idf slot)
-        if (rc || (rc = check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc")) ||
-            (rc = stage(Z, m, use, normals, (size_t)3 * np * sizeof(T))))
-        {
-            return rc;
-        }
-        const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_sample_proposal_assoc_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
-                           store(), dObs.get(), dAIdf.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(),
-                           (T)miss_likelihood, (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 1 : 2);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc"));
+        CSLAM_TRY(stage(Z, m, use, normals));
+        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood);
     }
 
     int feature_update_assoc(const void* Z, int m, const void* Rv, const int* use) override
@@ -1908,25 +1083,14 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_feature_update_assoc: bad arguments");
         }
-        int rc = use_device();
-        if (rc || (rc = check_assoc_inputs(Z, m, use, "pf_feature_update_assoc")))
-        {
-            return rc;
-        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_assoc_inputs(Z, m, use, "pf_feature_update_assoc"));
         if (m == 0)
         {
             return CSLAM_OK;
         }
-        if ((rc = stage(Z, m, use)))
-        {
-            return rc;
-        }
-        const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_feature_update_assoc_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(),
-                           dObs.get(), dAIdf.get(), dIdf(), m, R[0], R[1], R[2], R[3],
-                           (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(stage(Z, m, use));
+        return launch_feature_update_assoc(m, static_cast<const T*>(Rv));
     }
 
     // ------------------------------------------------------------------------------------------------
@@ -1935,70 +1099,21 @@ struct Pf : PfBase
     // layout the consumers read, and these are launched behind it with the arguments they always get.  Up to
     // kPfDrawObsMax observations Z / idf ride along as kernel arguments (no copy command at all); more take the staged copy.
     // ------------------------------------------------------------------------------------------------
-    bool               draw_seeded  = false;
-    unsigned long long draw_seed    = 0;
-    long long          draw_first   = 0; // global slot of this handle's particle 0
-    long long          draw_nglobal = 0; // particles of the whole set = strata of the resample
-    T                  draw_k       = (T)0; // 1 / n_global in T (stratified_random's k)
-    DevBuf<T>          dDrawDi;  // [n_global, none beyond 2^31 - 1] k/2, +k, +k, ...: the running sum of stratified_random, in T and in index order
-    DevBuf<T>          dDrawOut; // [3 np + n_global] what cslam_pf_get_draws brings back (never the staging area)
-
     int seed_draws(long long seed, long long first_global, long long n_global) override
     {
-        if (first_global < 0 || n_global >= (1LL << 32) || first_global > n_global - np)
+        long long n_strata = 0;
+        if (!pf_seed_args_ok(first_global, n_global, np, &n_strata))
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_seed_draws: need 0 <= first_global, first_global + %d <= n_global < 2^32 (got %lld, %lld)",
                         np, first_global, n_global);
         }
-        int rc = use_device();
-        if (rc)
-        {
-            return rc;
-        }
-        // One launch draws at most 2^31 - 1 strata (and every resample form counts its particles in an int): a larger
-        // set gets its normals -- the keys reach slot 2^32 - 1 -- and no strata table.
-        const long long n_strata = (n_global <= 0x7fffffffLL) ? n_global : 0;
-        // all-or-nothing (device_owners.hpp): new buffers into locals first, members replaced only when all exist
-        DevBuf<T>      di, out;
-        std::vector<T> h;
-        try
-        {
-            h.resize((size_t)n_strata);
-        }
-        catch (const std::bad_alloc&)
-        {
-            return fail(CSLAM_ERR_ALLOC, "pf_seed_draws: out of host memory for %lld strata", n_global);
-        }
-        if ((rc = di.alloc((size_t)std::max(n_strata, 1LL))) || (rc = out.alloc((size_t)3 * np + (size_t)n_strata)))
-        {
-            return rc;
-        }
-        const T k = (T)1 / (T)n_global; // PF.cpp:579-596, as pf.py's stratified_random rounds it
-        T       acc = k / (T)2;
-        for (long long i = 0; i < n_strata; i++)
-        {
-            h[(size_t)i] = acc;
-            acc          = acc + k;
-        }
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still reads the old table
-        if (n_strata > 0)
-        {
-            CSLAM_HIP_TRY(hipMemcpyAsync(di.get(), h.data(), (size_t)n_strata * sizeof(T), hipMemcpyHostToDevice, stream));
-            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        }
-        dDrawDi      = std::move(di);
-        dDrawOut     = std::move(out);
-        draw_seed    = (unsigned long long)seed;
-        draw_first   = first_global;
-        draw_nglobal = n_global;
-        draw_k       = k;
-        draw_seeded  = true;
-        return CSLAM_OK;
+        CSLAM_TRY(use_device());
+        return draws.reseed(seed, first_global, n_global, n_strata, np, stream);
     }
 
     int need_draws(const char* who)
     {
-        if (!draw_seeded)
+        if (!draws.seeded)
         {
             return fail(CSLAM_ERR_BAD_ARG, "%s: cslam_pf_seed_draws has not been called", who);
         }
@@ -2007,10 +1122,10 @@ struct Pf : PfBase
     int need_whole_set(const char* who)
     {
         int rc = need_draws(who);
-        if (rc == CSLAM_OK && (draw_first != 0 || draw_nglobal != np))
+        if (rc == CSLAM_OK && (draws.first != 0 || draws.nglobal != np))
         {
             rc = fail(CSLAM_ERR_BAD_ARG, "%s: the draws were seeded for slots %lld.. of %lld, this handle resamples its own %d",
-                      who, draw_first, draw_nglobal, np);
+                      who, draws.first, draws.nglobal, np);
         }
         return rc;
     }
@@ -2019,18 +1134,18 @@ struct Pf : PfBase
     // the staging area from the kernel's own arguments
     int launch_draw(long long step, T* normals, T* select, int n_sel, int m, const void* Z, const int* idf)
     {
-        PfDrawObs<T> obs;
-        std::memset(&obs, 0, sizeof(obs));
+        PfDrawObs<T> o;
+        std::memset(&o, 0, sizeof(o));
         if (m > 0)
         {
-            std::memcpy(obs.z, Z, (size_t)2 * m * sizeof(T));
-            std::memcpy(obs.idf, idf, (size_t)m * sizeof(int));
+            std::memcpy(o.z, Z, (size_t)2 * m * sizeof(T));
+            std::memcpy(o.idf, idf, (size_t)m * sizeof(int));
         }
         const int nn = normals ? np : 0;
         const int lanes = std::max(std::max(nn, n_sel), std::max(2 * m, 1));
-        hipLaunchKernelGGL(pf_stage_draw_kernel<T>, dim3((lanes + 255) / 256), dim3(256), 0, stream, draw_seed,
-                           (unsigned long long)step, (unsigned long long)draw_first, normals, nn, select, dDrawDi.get(),
-                           n_sel, draw_k, dObs.get(), dIdf(), m, obs);
+        hipLaunchKernelGGL(pf_stage_draw_kernel<T>, dim3((lanes + 255) / 256), dim3(256), 0, stream, draws.seed,
+                           (unsigned long long)step, (unsigned long long)draws.first, normals, nn, select, draws.di.get(),
+                           n_sel, draws.k, obs.z(), obs.dIdf(), m, o);
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -2038,59 +1153,40 @@ struct Pf : PfBase
     // Z | idf (or the use[] mask) of a proposal call and the normals of `step` into the staging area
     int stage_drawn(const void* Z, int m, const int* idf, long long step)
     {
-        int rc = ensure_m(m);
-        if (rc)
-        {
-            return rc;
-        }
+        CSLAM_TRY(ensure_m(m));
         if (m > kPfDrawObsMax)
         {
-            if ((rc = stage(Z, m, idf)))
-            {
-                return rc;
-            }
-            return launch_draw(step, dNormals(), nullptr, 0, 0, nullptr, nullptr);
+            CSLAM_TRY(stage(Z, m, idf));
+            return launch_draw(step, obs.dNormals(), nullptr, 0, 0, nullptr, nullptr);
         }
-        staged.clear();
-        if ((rc = launch_draw(step, dNormals(), nullptr, 0, m, Z, idf)))
-        {
-            return rc;
-        }
+        obs.forget();
+        CSLAM_TRY(launch_draw(step, obs.dNormals(), nullptr, 0, m, Z, idf));
         if (m > 0) // (what stage() remembers: a feature update right behind sends nothing)
         {
-            const size_t zb = (size_t)2 * m * sizeof(T), ib = (size_t)m * sizeof(int);
-            staged.resize(zb + ib);
-            std::memcpy(staged.data(), Z, zb);
-            std::memcpy(staged.data() + zb, idf, ib);
+            obs.remember(Z, m, idf);
         }
         return CSLAM_OK;
     }
 
     int get_draws(long long step, void* normals, void* select) override
     {
-        int rc = need_draws("pf_get_draws");
-        if (rc || (rc = use_device()))
+        CSLAM_TRY(need_draws("pf_get_draws"));
+        CSLAM_TRY(use_device());
+        if (select && draws.nglobal > 0x7fffffffLL)
         {
-            return rc;
+            return fail(CSLAM_ERR_BAD_ARG, "pf_get_draws: a set of %lld has no strata (at most 2^31 - 1), only normals", draws.nglobal);
         }
-        if (select && draw_nglobal > 0x7fffffffLL)
-        {
-            return fail(CSLAM_ERR_BAD_ARG, "pf_get_draws: a set of %lld has no strata (at most 2^31 - 1), only normals", draw_nglobal);
-        }
-        T* dn = dDrawOut.get();
+        T* dn = draws.out.get();
         T* ds = dn + (size_t)3 * np;
-        if ((rc = launch_draw(step, normals ? dn : nullptr, select ? ds : nullptr, select ? (int)draw_nglobal : 0, 0, nullptr,
-                              nullptr)))
-        {
-            return rc;
-        }
+        CSLAM_TRY(launch_draw(step, normals ? dn : nullptr, select ? ds : nullptr, select ? (int)draws.nglobal : 0, 0, nullptr,
+                              nullptr));
         if (normals)
         {
             CSLAM_HIP_TRY(hipMemcpyAsync(normals, dn, (size_t)3 * np * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         if (select)
         {
-            CSLAM_HIP_TRY(hipMemcpyAsync(select, ds, (size_t)draw_nglobal * sizeof(T), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipMemcpyAsync(select, ds, (size_t)draws.nglobal * sizeof(T), hipMemcpyDeviceToHost, stream));
         }
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         return CSLAM_OK;
@@ -2102,18 +1198,11 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_drawn: bad arguments");
         }
-        int rc = need_draws("pf_sample_proposal_drawn");
-        if (rc || (rc = use_device()) || (rc = check_idf(idf, m, "pf_sample_proposal_drawn")) ||
-            (rc = stage_drawn(Z, m, idf, step)))
-        {
-            return rc;
-        }
-        const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_sample_proposal_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
-                           store(), dObs.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(), PfPredict<T>{0, (T)0,
-                           (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0}, 0);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(need_draws("pf_sample_proposal_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_idf(idf, m, "pf_sample_proposal_drawn"));
+        CSLAM_TRY(stage_drawn(Z, m, idf, step));
+        return launch_proposal(m, static_cast<const T*>(Rv), no_predict(), 0);
     }
 
     int sample_proposal_assoc_drawn(const void* Z, int m, const void* Rv, const int* use, double miss_likelihood,
@@ -2123,30 +1212,20 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_assoc_drawn: bad arguments");
         }
-        int rc = need_draws("pf_sample_proposal_assoc_drawn");
-        // (the mask travels in the staging area's idf slot)
-        if (rc || (rc = use_device()) || (rc = check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc_drawn")) ||
-            (rc = stage_drawn(Z, m, use, step)))
-        {
-            return rc;
-        }
-        const T* R = static_cast<const T*>(Rv);
-        hipLaunchKernelGGL(pf_sample_proposal_assoc_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
-                           store(), dObs.get(), dAIdf.get(), dIdf(), m, R[0], R[1], R[2], R[3], dNormals(),
-                           (T)miss_likelihood, (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 1 : 2);
-        CSLAM_HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        CSLAM_TRY(need_draws("pf_sample_proposal_assoc_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc_drawn"));
+        CSLAM_TRY(stage_drawn(Z, m, use, step));
+        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood);
     }
 
     int resample_local_drawn(long long step, double n_eff, int status, double* neff, int* did) override
     {
-        int rc = need_whole_set("pf_resample_local_drawn");
-        if (rc || (rc = use_device()) || (rc = ensure_resample_buffers()) ||
-            (rc = launch_draw(step, nullptr, dSel.get(), np, 0, nullptr, nullptr)) ||
-            (rc = launch_resample(dSel.get(), n_eff, status)))
-        {
-            return rc;
-        }
+        CSLAM_TRY(need_whole_set("pf_resample_local_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(rs.ensure(np, stream));
+        CSLAM_TRY(launch_draw(step, nullptr, rs.sel.get(), np, 0, nullptr, nullptr));
+        CSLAM_TRY(launch_resample(rs.sel.get(), n_eff, status));
         return resample_result(neff, did);
     }
 
@@ -2159,23 +1238,18 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_observation_step_drawn: bad arguments");
         }
-        int rc = need_whole_set("pf_observation_step_drawn");
-        if (rc || (rc = use_device()) || (rc = check_idf(idf, m, "pf_observation_step_drawn")) ||
-            (rc = ensure_m(std::max(m, 1))) || (rc = ensure_resample_buffers()))
-        {
-            return rc;
-        }
-        staged.clear();
+        CSLAM_TRY(need_whole_set("pf_observation_step_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_idf(idf, m, "pf_observation_step_drawn"));
+        CSLAM_TRY(ensure_m(std::max(m, 1)));
+        CSLAM_TRY(rs.ensure(np, stream));
+        obs.forget();
         const bool by_copy = m > kPfDrawObsMax;
-        if (by_copy && (rc = stage(Z, m, idf)))
+        if (by_copy)
         {
-            return rc;
+            CSLAM_TRY(stage(Z, m, idf));
         }
-        T* nrm = dNormals();
-        if ((rc = launch_draw(step, m > 0 ? nrm : nullptr, nrm + (size_t)3 * np, np, by_copy ? 0 : m, Z, idf)))
-        {
-            return rc;
-        }
+        CSLAM_TRY(launch_draw(step, m > 0 ? obs.dNormals() : nullptr, obs.dSelect(), np, by_copy ? 0 : m, Z, idf));
         return launch_observation_step(v, swa, Qv, wb, dt, m, idf, Rv, n_eff, status);
     }
 
@@ -2185,7 +1259,7 @@ struct Pf : PfBase
         {
             return fail(CSLAM_ERR_BAD_ARG, "pf_stage_copies: null");
         }
-        *copies = stage_copies;
+        *copies = ring.copies();
         return CSLAM_OK;
     }
 };

@@ -1,0 +1,199 @@
+// pf_host_parts.hpp -- the arithmetic and bookkeeping of the particle handle that needs no GPU: the layout of the device
+// staging area, the memo of what it holds, the validity of the association tables, and the small host loops of the
+// fused step, the sharded exchange and the strata table.  No HIP include: tests/host/pf_host_parts_check.cpp builds it
+// with plain g++ (and under the address and undefined-behaviour sanitizers).
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+namespace cslam
+{
+
+// The device staging area of one handle: Z (2*mcap T) | idf (mcap int) | normals (3*np T) | select (np T).
+template <typename T>
+struct PfObsLayout
+{
+    int mcap = 0; // observations the area has room for
+    int np   = 0;
+
+    size_t off_idf() const { return (size_t)2 * mcap * sizeof(T); }
+    size_t off_normals() const { return off_idf() + (size_t)mcap * sizeof(int); }
+    size_t off_select() const { return off_normals() + (size_t)3 * np * sizeof(T); }
+
+    // capacity after growing to m observations: a multiple of 4 keeps the normals 16-byte aligned
+    static int grown(int m, int mcap) { return (std::max(m, std::max(64, 2 * mcap)) + 3) / 4 * 4; }
+    // elements of T behind the area (newm is a multiple of 4: its ints are a whole number of T)
+    static size_t alloc_count(int newm, int np) { return (size_t)2 * newm + (size_t)4 * np + (size_t)newm * sizeof(int) / sizeof(T); }
+
+    // bytes of the one copy that brings ...
+    size_t bytes_z(int m) const { return (size_t)2 * m * sizeof(T); }                  // Z
+    size_t bytes_z_idf(int m) const { return off_idf() + (size_t)m * sizeof(int); }    // Z | idf
+    size_t bytes_z_idf_normals() const { return off_select(); }                        // Z | idf | normals
+    size_t bytes_step() const { return off_select() + (size_t)np * sizeof(T); }        // Z | idf | normals | select
+};
+
+// Which Z || idf bytes the staging area holds (nothing remembered = unknown).  A call whose Z / idf are byte-identical
+// to them (featureUpdate right after sampleProposal, PF.cpp:150-156) sends nothing.
+class PfStagedMemo
+{
+  public:
+    void clear() { bytes_.clear(); }
+    void remember(const void* Z, size_t zb, const int* idf, size_t ib)
+    {
+        bytes_.resize(zb + ib);
+        if (zb)
+        {
+            std::memcpy(bytes_.data(), Z, zb);
+        }
+        if (ib)
+        {
+            std::memcpy(bytes_.data() + zb, idf, ib);
+        }
+    }
+    bool holds(const void* Z, size_t zb, const int* idf, size_t ib) const
+    {
+        return !bytes_.empty() && bytes_.size() == zb + ib && std::memcmp(bytes_.data(), Z, zb) == 0 &&
+               (ib == 0 || std::memcmp(bytes_.data() + zb, idf, ib) == 0);
+    }
+
+  private:
+    std::vector<char> bytes_;
+};
+
+// why a consumer of the association tables may not read them now
+enum class PfAssocRefusal
+{
+    none,
+    never_associated,
+    moved,      // particles changed slots since (the table is per slot)
+    other_scan, // Z / m are not those of the last associate
+    map_shrank,
+    bad_use // use[*index] is neither 0 nor 1
+};
+
+// What the association tables describe: the observations of the LAST associate call (kept to recognise them again), the
+// map size of that moment, and whether the particles still sit in the slots they had then.
+template <typename T>
+class PfAssocMemo
+{
+  public:
+    int m() const { return assoc_m; }   // -1: associate has not been called (or its tables are gone)
+    int nf() const { return assoc_nf; }
+    void forget() { assoc_m = -1; }
+    void moved() { assoc_moved = true; } // resample, unpack, set_particle
+    void associated(const void* Z, int m, int nf)
+    {
+        assoc_m     = m;
+        assoc_nf    = nf;
+        assoc_moved = false;
+        assoc_Z.clear();
+        if (m > 0)
+        {
+            assoc_Z.assign(static_cast<const char*>(Z), static_cast<const char*>(Z) + (size_t)2 * m * sizeof(T));
+        }
+    }
+    // the consumers take the observations of the last associate: anything else would pair a table with the wrong scan
+    PfAssocRefusal check(const void* Z, int m, int nf, const int* use, int* index) const
+    {
+        if (assoc_m < 0)
+        {
+            return PfAssocRefusal::never_associated;
+        }
+        if (assoc_moved)
+        {
+            return PfAssocRefusal::moved;
+        }
+        if (m != assoc_m || (m > 0 && std::memcmp(assoc_Z.data(), Z, (size_t)2 * m * sizeof(T)) != 0))
+        {
+            return PfAssocRefusal::other_scan;
+        }
+        if (nf < assoc_nf)
+        {
+            return PfAssocRefusal::map_shrank;
+        }
+        for (int i = 0; i < m; i++)
+        {
+            if (use[i] != 0 && use[i] != 1)
+            {
+                *index = i;
+                return PfAssocRefusal::bad_use;
+            }
+        }
+        return PfAssocRefusal::none;
+    }
+
+  private:
+    int               assoc_m     = -1;
+    int               assoc_nf    = 0;
+    bool              assoc_moved = false;
+    std::vector<char> assoc_Z; // the 2 * assoc_m observation scalars
+};
+
+// does an observation list name a feature twice?
+inline bool pf_has_duplicate(const int* idf, int m)
+{
+    for (int a = 0; a < m; a++)
+    {
+        for (int c = a + 1; c < m; c++)
+        {
+            if (idf[a] == idf[c])
+            {
+                return true;
+            }
+        }
+    }
+    return false;
+}
+
+// The record counts of a sharded exchange: hc[r] records go to rank r, hc[world + r] come from it; both buffers hold
+// them grouped by rank.  Where the records for / from `rank` start:
+inline void pf_exchange_offsets(const int* hc, int world, int rank, size_t* soff, size_t* roff)
+{
+    *soff = *roff = 0;
+    for (int r = 0; r < rank; r++)
+    {
+        *soff += (size_t)hc[r];
+        *roff += (size_t)hc[world + r];
+    }
+}
+
+// the plan fills the L slots of this rank, and what it sends itself is what it receives from itself
+inline bool pf_exchange_plan_ok(const int* hc, int world, int rank, int L, int* n_send, int* n_recv)
+{
+    *n_send = *n_recv = 0;
+    for (int r = 0; r < world; r++)
+    {
+        *n_send += hc[r];
+        *n_recv += hc[world + r];
+    }
+    return *n_recv == L && hc[rank] == hc[world + rank];
+}
+
+// k/2, +k, +k, ...: the running sum of stratified_random (PF.cpp:579-596, as pf.py rounds it), in T and in index order;
+// returns k = 1 / n_global in T
+template <typename T>
+inline T pf_fill_strata(T* out, long long n_strata, long long n_global)
+{
+    const T k   = (T)1 / (T)n_global;
+    T       acc = k / (T)2;
+    for (long long i = 0; i < n_strata; i++)
+    {
+        out[i] = acc;
+        acc    = acc + k;
+    }
+    return k;
+}
+
+// The arguments of seed_draws: 0 <= first_global, first_global + np <= n_global < 2^32.  One launch draws at most
+// 2^31 - 1 strata (and every resample form counts its particles in an int): a larger set gets its normals -- the keys
+// reach slot 2^32 - 1 -- and no strata table (*n_strata = 0).
+inline bool pf_seed_args_ok(long long first_global, long long n_global, int np, long long* n_strata)
+{
+    *n_strata = (n_global <= 0x7fffffffLL) ? n_global : 0;
+    return !(first_global < 0 || n_global >= (1LL << 32) || first_global > n_global - np);
+}
+
+} // namespace cslam

@@ -532,3 +532,49 @@ def test_records_around_256_scalars_and_a_growing_index_list(gpu_required, nf, d
                 assert _same_bits(np.asarray(x), np.asarray(y)), (count, d)
     a.close()
     b.close()
+
+
+# ------------------------------------------------------------------------------------------------ 8. staging ring
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_staging_ring_round_a_lap_and_grown_inside_one(gpu_required, dtype):
+    """The pinned staging ring of cslam_pf.hip (16 slots of 4096 bytes at first) taken round a lap and reallocated in the
+    middle of one, on two shards A and B from one case (np = 300, nf = 4).  20 feature updates at m = 3 whose Z
+    alternates between two sets, so that every call stages a copy: slots 0..15, then 0..3 again (a slot is reused behind
+    its event, not behind a drained stream).  Then 20 observation steps (host arrays) at m = 3: Z | idf | normals |
+    select of 300 particles is more than 4096 bytes, so the first of them reallocates the ring at position 4 of its second
+    lap, and the rest take the new ring round once more.  A queues everything back to back, B synchronises after every
+    call: every array must agree bit for bit, and each of the 40 calls must have enqueued exactly one copy."""
+    from conan_slam_amd.pf import stratified_random
+
+    npart, nf, m = 300, 4, 3
+    case = proposal_case((m, npart, nf, True), dtype)
+    assert (2 * 64 + 4 * npart) * np.dtype(dtype).itemsize + 64 * 4 > 4096  # the whole step does not fit the first slots
+    shards = [shard_from(case.parts, nf, dtype) for _ in range(2)]
+    rng = np.random.default_rng(310)
+    Zs = [case.Z, tight_obs(case.base, case.idf, dtype, seed=311)]
+    assert not _same_bits(Zs[0], Zs[1])
+    pose, steps = TRUE_POSE, []
+    for t in range(20):
+        pose = advance_pose(pose, *PREDICT)
+        idf = (rng.permutation(nf)[:m] + 1).astype(np.int32)
+        steps.append((tight_obs(case.base, idf, dtype, seed=320 + t, pose=pose), idf,
+                      rng.normal(size=(3, npart)).astype(dtype), stratified_random(npart, rng.uniform(size=npart), dtype)))
+    for sh, sync in zip(shards, (False, True)):
+        copies = sh.stage_copies()
+        for t in range(20):
+            sh.feature_update(Zs[t % 2], case.idf, case.R)
+            if sync:
+                sh.synchronize()
+        assert sh.stage_copies() - copies == 20
+        for Z, idf, nrm, sel in steps:
+            _fused_step(sh, case, Z, idf, nrm, sel, npart + 1)
+            if sync:
+                sh.synchronize()
+        assert sh.stage_copies() - copies == 40
+    a, b = shards
+    calls, resamples, neff = a.resample_stats()
+    assert (calls, resamples) == (20, 20) and np.isfinite(neff)
+    assert np.all(np.isfinite(a.get_weights()))
+    _assert_shards_bit_equal(a, b, "staging ring, back to back against synchronised")
+    a.close()
+    b.close()

@@ -4,7 +4,11 @@ end relative to the first one, its stream/queue, and how much of it overlapped t
 statistics per kernel and the P-GEMM's start-to-start period.
 A trace without a P-GEMM (the particle filter's) names the kernel its window starts at and whose start-to-start period is
 the step: e.g. `pf_resample_plan` -- the copy command of a step shows as its blit kernel, or as the gap it leaves.
-Usage: python tools/trace_timeline.py <kernel_trace.csv> [skip_fraction=0.5] [count=40] [anchor=downdate]"""
+Usage: python tools/trace_timeline.py <kernel_trace.csv> [skip_fraction=0.5] [count=40] [anchor=downdate]
+       python tools/trace_timeline.py <kernel_trace.csv> --sequence
+--sequence prints the whole trace as its launch sequence alone -- kernel name, grid (in threads) and queue (numbered
+by first appearance) in start order, no times -- so that two runs of the same program can be compared line for line
+(profiles/r07_launch_sequence_*.txt, profiles/r10_pf_launch_sequence_*.txt)."""
 import csv
 import sys
 
@@ -17,8 +21,20 @@ def short(name):
     return n[:44]
 
 
+def sequence(rows):
+    rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+    queues = {}
+    print(f"{'kernel':70s} {'grid':>18s} queue")
+    for r in rows:
+        grid = "x".join(r[f"Grid_Size_{a}"] for a in "XYZ")
+        q = queues.setdefault(r.get("Queue_Id", ""), len(queues) + 1)
+        print(f"{r['Kernel_Name'][:70]:70s} {grid:>18s} {q}")
+
+
 def main():
     rows = list(csv.DictReader(open(sys.argv[1])))
+    if "--sequence" in sys.argv[2:]:
+        return sequence(rows)
     skip = float(sys.argv[2]) if len(sys.argv) > 2 else 0.5
     count = int(sys.argv[3]) if len(sys.argv) > 3 else 40
     anchor = sys.argv[4] if len(sys.argv) > 4 else "downdate"
