@@ -39,6 +39,9 @@ _PROTOTYPES = {
     "cslam_ekf_batch_get_landmarks": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
     # launches of the look-ahead windows' rows kernel (zero where the row-major panel mirror serves the blocks kernel)
     "cslam_ekf_rows_launches": [C.c_void_p, C.POINTER(C.c_longlong)],
+    # whole tiles and strips of the last f32 P-GEMM launch (the tail phase, CSLAM_PGEMM_TAIL)
+    "cslam_ekf_pgemm_split": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "cslam_ekf_batch_pgemm_split": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     # the batched scan generator and the two batch calls that consume its scans
     "cslam_sim_batch_create": [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_void_p)],
     "cslam_sim_batch_destroy": [C.c_void_p],

@@ -34,6 +34,7 @@
 #include "ekf_options.hpp"
 #include "ekf_pending_store.hpp"
 #include "ekf_pgemm_limbs.hpp"
+#include "ekf_pgemm_tiles.hpp"
 #include "ekf_pose_kernels.hpp"
 #include "ekf_staging.hpp"
 #include "host_linalg.hpp"
@@ -137,6 +138,7 @@ struct EkfBase
     int         n        = 3;
     int         sync_mode = 1;
     int         pgemm_wgs     = 0;  // > 0: cap on the persistent P-GEMM grid (cslam_ekf_set_pgemm_workgroups: co-running instances)
+    int         split_whole = 0, split_strips = 0; // whole tiles and strips of the last psym4 launch (cslam_ekf_pgemm_split)
     // (the owners live in the base, so they are destroyed after every buffer and event of Ekf<T>)
     Stream      stream_own, stream_b_own, stream_f_own;
     hipStream_t stream   = nullptr; // A: everything except the P-GEMM (= stream_own.get())
@@ -230,6 +232,12 @@ struct Ekf : EkfBase
     DevBuf<int2> dTiles;
     int   tiles_built = 0;
     int   n_sym_tiles = 0;
+    // the work lists of ekf_downdate_psym4_f32 with its tail phase (ekf_pgemm_tiles.hpp), one per chunk class: whole
+    // tiles, then strips.  Built by ensure_tile_list for (tile rows, valid strips of the last tile row, grid); a class
+    // without strips uses dTiles.
+    DevBuf<int2> dWork[3];
+    int   work_whole[3] = {0, 0, 0}, work_strips[3] = {0, 0, 0};
+    int   work_tiles = 0, work_valid = 0, work_grid = 0;
     int   num_cus     = 256;
     // status
     int sticky_host = 0; // flags raised by host-side decisions (FALLBACK/SKIPPED)
@@ -1111,6 +1119,7 @@ struct Ekf : EkfBase
     int  launch_downdate(const T* W, int k, hipStream_t st);
     bool launch_corr_fast(int k, const T* Wp, int kc);          // PHT -= Wp*Y^T on MFMA (f32)
     int  ensure_tile_list(int tiles);
+    int  pgemm_grid() const;
     bool launch_gain_fast(int k, int n_pad, T* slot, const T* Gt, const T* U, const T* M); // MFMA gain
 
     // one batch of m observations with device-resident Z / idf (slam.h:235-266 via EKF.cpp:93-129).
@@ -2281,30 +2290,87 @@ struct Ekf : EkfBase
 template <typename T>
 int Ekf<T>::ensure_tile_list(int tiles)
 {
-    if (tiles == tiles_built)
+    if (tiles != tiles_built)
+    {
+        std::vector<int2> h;
+        h.reserve((size_t)tiles * (tiles + 1) / 2);
+        for (int tj = 0; tj < tiles; tj++)
+        {
+            for (int ti = tj; ti < tiles; ti++)
+            {
+                h.push_back(make_int2(ti, tj));
+            }
+        }
+        if (int rc = sync_all()) // (a P-GEMM in flight still reads the old list)
+        {
+            return rc;
+        }
+        DevBuf<int2> list;
+        CSLAM_TRY(list.alloc(h.size()));
+        dTiles = std::move(list);
+        CSLAM_HIP_TRY(hipMemcpy(dTiles.get(), h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
+        tiles_built = tiles;
+        n_sym_tiles = (int)h.size();
+    }
+    // the tail phase's lists: they also depend on the grid and on how many 32-row strips of the last tile row hold
+    // rows below n
+    if (sizeof(T) != 4 || opt.pgemm_tail == 0 || !opt.lower)
     {
         return CSLAM_OK;
     }
-    std::vector<int2> h;
-    h.reserve((size_t)tiles * (tiles + 1) / 2);
-    for (int tj = 0; tj < tiles; tj++)
+    const int G     = pgemm_grid();
+    const int valid = pgemm_valid_strips(tiles, n);
+    if (tiles == work_tiles && valid == work_valid && G == work_grid)
     {
-        for (int ti = tj; ti < tiles; ti++)
+        return CSLAM_OK;
+    }
+    PgemmWork w[3];
+    bool      any = false;
+    for (int c = 0; c < 3; c++)
+    {
+        // (a forced count leaves one tile whole: a workgroup enters the tail phase from the whole-tile loop)
+        w[c] = pgemm_build_work(tiles, n, G, c, std::min(opt.pgemm_tail, n_sym_tiles - 1));
+        any  = any || w[c].strips > 0 || work_strips[c] > 0;
+    }
+    if (any)
+    {
+        if (int rc = sync_all()) // (a P-GEMM in flight still reads the old lists)
         {
-            h.push_back(make_int2(ti, tj));
+            return rc;
         }
     }
-    if (int rc = sync_all()) // (a P-GEMM in flight still reads the old list)
+    for (int c = 0; c < 3; c++)
     {
-        return rc;
+        static_assert(sizeof(PgemmEntry) == sizeof(int2), "a work-list entry is an int2");
+        DevBuf<int2> list;
+        if (w[c].strips > 0)
+        {
+            CSLAM_TRY(list.alloc(w[c].list.size()));
+            CSLAM_HIP_TRY(hipMemcpy(list.get(), w[c].list.data(), w[c].list.size() * sizeof(int2), hipMemcpyHostToDevice));
+        }
+        dWork[c]       = std::move(list);
+        work_whole[c]  = w[c].strips > 0 ? w[c].whole : 0;
+        work_strips[c] = w[c].strips;
     }
-    DevBuf<int2> list;
-    CSLAM_TRY(list.alloc(h.size()));
-    dTiles = std::move(list);
-    CSLAM_HIP_TRY(hipMemcpy(dTiles.get(), h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
-    tiles_built = tiles;
-    n_sym_tiles = (int)h.size();
+    work_tiles = tiles;
+    work_valid = valid;
+    work_grid  = G;
     return CSLAM_OK;
+}
+
+// workgroups of the persistent P-GEMM grid: two per CU, minus `pgemm_spare` in two-stream mode -- a few CUs keep one
+// workgroup (64 of 160 KB LDS) so that the one-workgroup factor kernel of the NEXT update (53 KB LDS, stream A) finds
+// room while this P-GEMM fills the chip; look-ahead windows: the main stream's queue mask excludes the compute units
+// of the factor chain's stream (la_cus, see la_ensure)
+template <typename T>
+int Ekf<T>::pgemm_grid() const
+{
+    int G = std::min(n_sym_tiles, std::max(1, 2 * (num_cus - la_cus) - (opt.pipeline ? opt.pgemm_spare : 0)));
+    if (pgemm_wgs > 0)
+    {
+        G = std::min(G, pgemm_wgs);
+    }
+    return G;
 }
 
 template <>
@@ -2319,16 +2385,7 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
         return rc;
     }
     const dim3 block(256);
-    // Persistent grid: two workgroups per CU, minus `pgemm_spare` in two-stream mode -- a few CUs keep one workgroup
-    // (64 of 160 KB LDS) so that the one-workgroup factor kernel of the NEXT update (53 KB LDS, stream A) finds room
-    // while this P-GEMM fills the chip.
-    // (two-stream mode: a few CUs keep one workgroup; look-ahead windows: the main stream's queue mask excludes the
-    // compute units of the factor chain's stream, see la_ensure)
-    int G = std::min(n_sym_tiles, std::max(1, 2 * (num_cus - la_cus) - (opt.pipeline ? opt.pgemm_spare : 0)));
-    if (pgemm_wgs > 0)
-    {
-        G = std::min(G, pgemm_wgs);
-    }
+    int G = pgemm_grid(); // the persistent grid
     const bool nt = opt.psym_nt >= 0 ? opt.psym_nt != 0 : (size_t)n_sym_tiles * 65536 > ((size_t)230 << 20);
     if (limbs_take(k8))
     {
@@ -2399,6 +2456,18 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
         // per-XCD tile queues (see the kernel): env CSLAM_XCD_QUEUES (every queue needs workgroups: small grids stay on
         // the single queue)
         const bool xq = opt.xcd_queues != 0 && G >= 64;
+        // the tail phase (single queue only): this chunk class's list of whole tiles and strips in place of dTiles
+        const int   cc      = pgemm_chunk_class(k8);
+        const bool  tail    = !xq && work_strips[cc] > 0;
+        const int2* wl      = tail ? (const int2*)dWork[cc].get() : (const int2*)dTiles.get();
+        const int   n_whole = tail ? work_whole[cc] : n_sym_tiles;
+        const int   n_strip = tail ? work_strips[cc] : 0;
+        if (tail)
+        {
+            G = std::min(G, n_whole); // (the list was built for pgemm_grid(); every workgroup starts with a whole tile)
+        }
+        split_whole         = n_whole;
+        split_strips        = n_strip;
         if (xq)
         {
             if ((rc = ensure_tiles_morton(tiles, stream)))
@@ -2409,11 +2478,11 @@ int Ekf<float>::launch_downdate(const float* W, int k, hipStream_t stream)
         }
 #define CSLAM_LAUNCH_PSYM4(MODE, NCH, KC)                                                                             \
     hipLaunchKernelGGL((ekf_downdate_psym4_f32<MODE, NCH, KC>), dim3(G), block, 0, stream, dP.get(), ldp, W, ldp, k,         \
-                       xq ? (const int2*)dTilesM.get() : (const int2*)dTiles.get(), n_sym_tiles,                                  \
+                       xq ? (const int2*)dTilesM.get() : wl, n_whole,                                                             \
                        xq ? dTicketX.get() + 8 * limb_parity : dTicket.get() + (launch_parity & 1),                              \
                        xq ? dTicketX.get() + 8 * (limb_parity ^ 1) : dTicket.get() + ((launch_parity + 1) & 1),                  \
                        (unsigned long long*)nullptr, xq ? (const int*)dSegOff.get() : (const int*)nullptr, 0u, 0u, 0u, 0u,           \
-                       la_sig_add ? la.done.get() : (unsigned*)nullptr, la_sig_add, 1, 0)
+                       la_sig_add ? la.done.get() : (unsigned*)nullptr, la_sig_add, 1, 0, n_strip)
         if (k8 <= 64)
         {
             if (nt) { CSLAM_LAUNCH_PSYM4(1, 2, 32); } else { CSLAM_LAUNCH_PSYM4(0, 2, 32); }
@@ -2777,6 +2846,18 @@ int cslam_ekf_set_pgemm_workgroups(cslam_ekf_t h, int workgroups)
         return fail(CSLAM_ERR_BAD_ARG, "set_pgemm_workgroups: negative");
     }
     B(h)->pgemm_wgs = workgroups;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_pgemm_split(cslam_ekf_t h, int* whole_tiles, int* strips)
+{
+    CSLAM_NEED(h);
+    if (!whole_tiles || !strips)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pgemm_split: null");
+    }
+    *whole_tiles = B(h)->split_whole;
+    *strips      = B(h)->split_strips;
     return CSLAM_OK;
 }
 

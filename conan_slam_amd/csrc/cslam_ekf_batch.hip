@@ -33,6 +33,7 @@
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_options.hpp"
+#include "ekf_pgemm_tiles.hpp"
 #include "ekf_pose_kernels.hpp"
 #include "ekf_score_kernels.hpp"
 #include "sim_scan_view.hpp"
@@ -125,6 +126,12 @@ struct cslam_ekf_batch
     DevBuf<int2>     dTiles;
     DevBuf<int>      dTicket;
     std::vector<int> tile_off, tile_cnt;
+    // the tail phase (CSLAM_PGEMM_TAIL != 0; ekf_pgemm_tiles.hpp): whole tiles + strips for every row-tile count T, every
+    // number v = 1 .. 4 of strips of the last tile row that hold rows below n, and every chunk class c, at
+    // dWork + work_off[(T * 4 + v - 1) * 3 + c].  Built at create like dTiles, for the same reason.
+    DevBuf<int2>     dWork;
+    std::vector<int> work_off, work_whole, work_strips;
+    int              split_whole = 0, split_strips = 0; // the last launch (cslam_ekf_batch_pgemm_split)
     int              parity = 0;
     int              ncap   = 0; // n at max_landmarks
     // the calls of the reference's loop (cslam_ekf_batch_predict / observe_heading / update / augment): as the single
@@ -261,6 +268,41 @@ struct cslam_ekf_batch
         }
         CSLAM_TRY(dTiles.alloc(h.size()));
         CSLAM_HIP_TRY(hipMemcpy(dTiles.get(), h.data(), h.size() * sizeof(int2), hipMemcpyHostToDevice));
+        if (opt.pgemm_tail != 0)
+        {
+            static_assert(sizeof(PgemmEntry) == sizeof(int2), "a work-list entry is an int2");
+            std::vector<PgemmEntry> wl;
+            work_off.assign(((size_t)tiles + 1) * 12, 0);
+            work_whole.assign(((size_t)tiles + 1) * 12, 0);
+            work_strips.assign(((size_t)tiles + 1) * 12, 0);
+            for (int T = std::max(1, row_tiles()); T <= tiles; T++)
+            {
+                const int G = std::min(tile_cnt[T], 2 * (num_cus - I));
+                for (int v = 1; v <= 4; v++)
+                {
+                    for (int c = 0; c < 3; c++)
+                    {
+                        // (a forced count leaves one tile of every instance whole: a workgroup enters the tail phase from
+                        // the whole-tile loop)
+                        const PgemmWork w = pgemm_build_work_batch(I, T, (T - 1) * kTile + v * kPgemmStrip, G, c,
+                                                                   std::min(opt.pgemm_tail, T * (T + 1) / 2 - 1));
+                        const size_t    at = ((size_t)T * 4 + v - 1) * 3 + c;
+                        work_off[at]       = (int)wl.size();
+                        work_whole[at]     = w.whole;
+                        work_strips[at]    = w.strips;
+                        if (w.strips > 0)
+                        {
+                            wl.insert(wl.end(), w.list.begin(), w.list.end());
+                        }
+                    }
+                }
+            }
+            if (!wl.empty())
+            {
+                CSLAM_TRY(dWork.alloc(wl.size()));
+                CSLAM_HIP_TRY(hipMemcpy(dWork.get(), wl.data(), wl.size() * sizeof(int2), hipMemcpyHostToDevice));
+            }
+        }
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_batch<16>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)la_chain_lds<float>(16)));
         CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_la_chain_batch<32>),
@@ -302,9 +344,19 @@ struct cslam_ekf_batch
                                            (size_t)I, stream));
         }
         const int      T       = std::max(1, row_tiles());
-        const int2*    tl      = dTiles.get() + tile_off[T];
-        const int      n_tiles = tile_cnt[T];
-        const int      G       = std::min(n_tiles, 2 * (num_cus - I));
+        int            G       = std::min(tile_cnt[T], 2 * (num_cus - I));
+        // the tail phase: this (T, valid strips, chunk class)'s list of whole tiles and strips in place of list T
+        const size_t   wat     = ((size_t)T * 4 + pgemm_valid_strips(T, n) - 1) * 3 + pgemm_chunk_class(k8);
+        const bool     tail    = !work_strips.empty() && work_strips[wat] > 0;
+        const int2*    tl      = tail ? dWork.get() + work_off[wat] : dTiles.get() + tile_off[T];
+        const int      n_tiles = tail ? work_whole[wat] : tile_cnt[T];
+        const int      n_strip = tail ? work_strips[wat] : 0;
+        if (tail)
+        {
+            G = std::min(G, n_tiles); // (every workgroup starts with a whole tile)
+        }
+        split_whole            = n_tiles;
+        split_strips           = n_strip;
         const unsigned sPb    = (unsigned)((size_t)ldp * ldp * 4);
         const unsigned sWb    = (unsigned)(sW() * 4);
         const unsigned p_span = (unsigned)((size_t)I * ldp * ldp * 4);
@@ -319,7 +371,7 @@ struct cslam_ekf_batch
     hipLaunchKernelGGL((ekf_downdate_psym4_f32<0, NCH, KC, false, true>), dim3(G), dim3(256), 0, stream, dP.get(), ldp, W, ldp, \
                        kp, tl, n_tiles, dTicket.get() + parity, dTicket.get() + (parity ^ 1),                  \
                        (unsigned long long*)nullptr, (const int*)nullptr, sPb, sWb, p_span, w_span,                   \
-                       sig_add ? dDone.get() : (unsigned*)nullptr, sig_add, I, (int)labatch::kDoneBlock)
+                       sig_add ? dDone.get() : (unsigned*)nullptr, sig_add, I, (int)labatch::kDoneBlock, n_strip)
         if (k8 <= 64)
         {
             CSLAM_LAUNCH_PSYM4B(2, 32);
@@ -1221,6 +1273,17 @@ int cslam_ekf_batch_get_pgemm_time(cslam_ekf_batch_t h, double* ms_sum, int* lau
     }
     *ms_sum   = s;
     *launches = (int)h->prof_used;
+    return CSLAM_OK;
+}
+
+int cslam_ekf_batch_pgemm_split(cslam_ekf_batch_t h, int* whole_tiles, int* strips)
+{
+    if (!h || !whole_tiles || !strips)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_batch_pgemm_split: bad arguments");
+    }
+    *whole_tiles = h->split_whole;
+    *strips      = h->split_strips;
     return CSLAM_OK;
 }
 

@@ -2380,7 +2380,7 @@ ekf_downdate_psym4_f32(float* __restrict__ P, int ldp, const float* __restrict__
                        int* __restrict__ ticket_reset, unsigned long long* __restrict__ hwids,
                        const int* __restrict__ seg_off = nullptr, unsigned sP = 0, unsigned sW = 0, unsigned p_span = 0,
                        unsigned w_span = 0, unsigned* __restrict__ signal = nullptr, unsigned sig_add = 0, int sig_count = 0,
-                       int sig_stride = 0)
+                       int sig_stride = 0, int nstrips = 0)
 {
     // Look-ahead windows: the kernels launched before this one on the stream have finished and their results are visible
     // device-wide (kernel boundary): tell the `sig_count` factor chains that wait for them (ekf_la_chain_kernel /
@@ -2633,6 +2633,133 @@ ekf_downdate_psym4_f32(float* __restrict__ P, int ldp, const float* __restrict__
         return have_next;
     };
 
+    // ---- the tail phase (nstrips > 0; single queue only): tile_list[ntiles .. ntiles + nstrips) are STRIPS, 32 rows x 128
+    // columns of a tile (ekf_pgemm_tiles.hpp: x as in a tile entry, y = tile column | strip << 16), and the list indices run
+    // on past the whole tiles: a static index (t + G) or a ticket (2 G + ticket) at or beyond ntiles is a claim on a
+    // strip; the grid is at most ntiles, so every workgroup has a whole tile and enters the tail from the whole-tile loop.
+    // A separate, simple body: wave w owns columns 32 w .. 32 w + 31 of the strip, one MFMA per k-pair, the chunks
+    // one after the other (the panel DMA of chunk c + 1 in flight under the MFMAs of chunk c), no memory operation inside
+    // the MFMA loops.  Every element sees the same instruction on the same operand pairs in the same order as in a whole
+    // tile, then one subtraction: the bits are those of the whole-tile loop.
+    // (The lane's coordinates are formed again here, from the lane count, and hidden from the optimiser: shared with the
+    // whole-tile loop's they would stay in registers across it and raise its VGPR count.)
+    auto lane_again = [&]() -> int {
+        int l = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        asm volatile("" : "+v"(l));
+        return l;
+    };
+    auto strip = [&](int2 e) {
+        const int      lane2 = lane_again();
+        const int      lj    = lane2 & 31;
+        const int      lh    = lane2 >> 5;
+        const int      s     = e.y >> 16;
+        const int2     tl    = make_int2(e.x, e.y & 0xFFFF);
+        const unsigned sbase = tile_base(tl) + (unsigned)(s * 32 * 4);
+        const unsigned loff  = lane_off - (unsigned)(12 * lj); // ((wave * 32 + 4 * lh) * ldp + lj) * 4
+        constexpr int  nd    = 2 * (KC / 8); // VM operations of one dma_chunk
+        float          pr[16];
+        f32x16         acc;
+        auto mfmas = [&](auto B) {
+            constexpr int bsel = decltype(B)::value;
+            const float*  sB   = bsel == 0 ? s_b0 : s_b1;
+            const float*  sA   = bsel == 0 ? s_a0 : s_a1;
+#pragma unroll
+            for (int g = 0; g < KC / 2; g++)
+            {
+                const float b = sB[(2 * g + lh) * 128 + 32 * s + lj];
+                const float a = sA[(2 * g + lh) * 128 + wave * 32 + lj];
+                acc           = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
+            }
+        };
+        __builtin_amdgcn_s_barrier(); // everybody is done with both buffer pairs
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+        {
+            pr[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsP, loff, sbase + row_off(r), kAuxLd));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        dma_chunk(tl, std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_barrier(0);
+        dma_chunk(tl, std::integral_constant<int, 1>{});
+        __builtin_amdgcn_sched_barrier(0);
+        acc = f32x16{0};
+        __builtin_amdgcn_s_waitcnt(0x0F70 | nd); // all but chunk 1's panels have landed
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        mfmas(std::integral_constant<int, 0>{});
+        if constexpr (NCH == 4)
+        {
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier(); // pair 0 is free
+            __builtin_amdgcn_sched_barrier(0);
+            dma_chunk(tl, std::integral_constant<int, 2>{});
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0x0F70 | nd);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas(std::integral_constant<int, 1>{});
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier(); // pair 1 is free
+            __builtin_amdgcn_sched_barrier(0);
+            dma_chunk(tl, std::integral_constant<int, 3>{});
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_waitcnt(0x0F70 | nd);
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas(std::integral_constant<int, 0>{});
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0x0F70);
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+        mfmas(std::integral_constant<int, 1>{});
+#pragma unroll
+        for (int r = 0; r < 16; r++)
+        {
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pr[r] - acc[r]), rsP, loff, sbase + row_off(r),
+                                                  kAuxSt);
+        }
+    };
+    // c0, c1: the two list indices the workgroup holds when it gets here (thread 0's values count; c0 < c1)
+    auto strips_run = [&](int c0, int c1) {
+        const int  end = ntiles + nstrips;
+        const bool t0  = wave == 0 && lane_again() == 0; // thread 0
+        __builtin_amdgcn_s_waitcnt(0x0070); // (a panel DMA of the whole-tile loop may still be in flight)
+        __builtin_amdgcn_s_barrier();
+        if (t0)
+        {
+            s_next = make_int2(c0, c1);
+        }
+        __syncthreads();
+        const int2 cl    = s_next;
+        const int  second = __builtin_amdgcn_readfirstlane(cl.y);
+        int        idx   = __builtin_amdgcn_readfirstlane(cl.x);
+        for (int stage = 0;; stage++)
+        {
+            if (idx >= ntiles && idx < end)
+            {
+                strip(tile_list[idx]);
+            }
+            if (stage == 0)
+            {
+                idx = second;
+                continue;
+            }
+            if (idx >= end)
+            {
+                break; // (tickets only grow: nothing is left for this workgroup)
+            }
+            __syncthreads(); // everybody has read s_next
+            if (t0)
+            {
+                s_next.x = 2 * G + __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __syncthreads();
+            idx = __builtin_amdgcn_readfirstlane(s_next.x);
+        }
+    };
+
     const int t = xq ? (int)(blockIdx.x >> 3) : (int)blockIdx.x; // rank on the queue
     if (blockIdx.x == 0 && tid < (xq ? 8 : 1))
     {
@@ -2640,7 +2767,7 @@ ekf_downdate_psym4_f32(float* __restrict__ P, int ldp, const float* __restrict__
     }
     if (t >= ntiles)
     {
-        return;
+        return; // (with strips the host launches no more workgroups than whole tiles: the tail is entered from the loop)
     }
     int2     cur   = tile_list[t];
     unsigned cbase = tile_base(cur);
@@ -2654,11 +2781,13 @@ ekf_downdate_psym4_f32(float* __restrict__ P, int ldp, const float* __restrict__
     int  tk = 0;
     int2 nxt;
     bool hn = process(std::true_type{}, cur, cbase, 0u, t + G, tk, nxt);
+    int  held = t - G; // the claim that found the whole tiles exhausted, as a raw ticket (index 2 G + held)
     while (hn)
     {
         const unsigned rbase = cbase;
         cur                  = nxt;
         cbase                = tile_base(cur);
+        held                 = __builtin_amdgcn_readfirstlane(tk); // (thread 0's ticket: wave 0 carries it)
         hn                   = process(std::false_type{}, cur, cbase, rbase, tk, tk, nxt);
     }
     // the last tile's results
@@ -2671,6 +2800,10 @@ ekf_downdate_psym4_f32(float* __restrict__ P, int ldp, const float* __restrict__
     {
         __builtin_amdgcn_s_waitcnt(0x0F70);
         hwids[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memrealtime();
+    }
+    if (nstrips > 0)
+    {
+        strips_run(2 * G + held, 2 * G + tk); // both are at or beyond ntiles: claims on strips, not to be dropped
     }
 }
 

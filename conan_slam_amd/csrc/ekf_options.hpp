@@ -11,6 +11,10 @@ namespace cslam
 {
 inline int env_int(const char* name, int dflt) { const char* s = getenv(name); return s ? atoi(s) : dflt; }
 inline int env_flag(const char* name, int dflt) { const char* s = getenv(name); return s ? (atoi(s) ? 1 : 0) : dflt; }
+// CSLAM_PGEMM_TAIL, the tail phase of the f32 P-GEMM (ekf_pgemm_tiles.hpp): tiles handed out as 32-row strips.  -1: the
+// value's own meaning is "by the rule" (a negative value reads as that), 0: no strips, N > 0: exactly min(N, tiles) tiles
+constexpr int kPgemmTailMax = 1 << 20;
+inline int env_pgemm_tail(int dflt) { return std::max(-1, std::min(kPgemmTailMax, env_int("CSLAM_PGEMM_TAIL", dflt))); }
 
 struct EkfOptions
 {
@@ -47,6 +51,7 @@ struct EkfOptions
     // 0 - 4 % slower (profiles/r02_pmc_xcd_queues.txt)
     int xcd_queues = 0;
     int psym_nt    = -1; // CSLAM_PSYM_NT=0|1: non-temporal P accesses in the P-GEMM (-1: by footprint)
+    int pgemm_tail = -1; // CSLAM_PGEMM_TAIL: tiles the P-GEMM hands out as strips (-1: by the rule, 0: none, N: exactly N)
     // f64 P-GEMM: columns of W1 staged per pass: 16, register-staged and double-buffered (see the kernel).  The
     // synchronous staging loop (other values of CSLAM_F64_KCM, a multiple of 4 in 4..64) measured at N = 1000, k = 64:
     // 8 / 16 / 32 -> 22.8 / 21.9 / 22.9 us, 64 (the whole panel at once, 96 KB of LDS, one workgroup per CU) -> 30.5 us.
@@ -78,6 +83,7 @@ struct EkfOptions
         o.limbs_kmin       = kmin < 0 ? o.limbs_kmin : std::max(57, kmin); // (a negative value keeps the default)
         o.xcd_queues       = env_flag("CSLAM_XCD_QUEUES", o.xcd_queues);
         o.psym_nt          = env_flag("CSLAM_PSYM_NT", o.psym_nt);
+        o.pgemm_tail       = env_pgemm_tail(o.pgemm_tail);
         o.f64_kcm          = std::max(4, std::min(64, (env_int("CSLAM_F64_KCM", o.f64_kcm) + 3) / 4 * 4));
         if (getenv("CSLAM_F64_CB"))
         {
@@ -94,6 +100,7 @@ struct EkfBatchOptions
     int wide_pairs = 2; // 32-row blocks per wide workgroup (CSLAM_BATCH_WIDE_PAIRS=1: one, the first form)
     int la_k64     = 1; // CSLAM_LA_K64=0: the general wide kernel for m = 32 too (A/B)
     int stamps     = 0; // CSLAM_BATCH_STAMPS set: see LaBatchWin::stamps (printed after 300 windows)
+    int pgemm_tail = -1; // CSLAM_PGEMM_TAIL as above (by the rule: measured to pay at 8 x N = 2000)
 
     static EkfBatchOptions from_env()
     {
@@ -102,6 +109,7 @@ struct EkfBatchOptions
         o.wide_pairs = env_int("CSLAM_BATCH_WIDE_PAIRS", o.wide_pairs) == 1 ? 1 : 2;
         o.la_k64     = env_flag("CSLAM_LA_K64", o.la_k64);
         o.stamps     = getenv("CSLAM_BATCH_STAMPS") ? 1 : 0;
+        o.pgemm_tail = env_pgemm_tail(o.pgemm_tail);
         return o;
     }
 };

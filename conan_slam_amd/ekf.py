@@ -119,6 +119,12 @@ class EKF:
     def synchronize(self):
         check(self._L.cslam_ekf_synchronize(self._h))
 
+    def pgemm_split(self):
+        """(whole tiles, strips) of the handle's last f32 P-GEMM launch of at most 128 columns (cslam_ekf_pgemm_split)"""
+        w, s = C.c_int(0), C.c_int(0)
+        check(self._L.cslam_ekf_pgemm_split(self._h, C.byref(w), C.byref(s)))
+        return w.value, s.value
+
     def lookahead_windows(self) -> int:
         """look-ahead windows this handle has launched (cslam_ekf_lookahead_windows)"""
         w = C.c_longlong(0)
@@ -471,6 +477,12 @@ class EKFBatch:
         w = C.c_longlong(0)
         check(self._L.cslam_ekf_batch_info(self._h, None, None, C.byref(w)))
         return w.value
+
+    def pgemm_split(self):
+        """(whole tiles, strips) of the batch's last P-GEMM launch (cslam_ekf_batch_pgemm_split)"""
+        w, s = C.c_int(0), C.c_int(0)
+        check(self._L.cslam_ekf_batch_pgemm_split(self._h, C.byref(w), C.byref(s)))
+        return w.value, s.value
 
     def set_profiling(self, every: int):
         check(self._L.cslam_ekf_batch_set_profiling(self._h, C.c_int(every)))

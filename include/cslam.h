@@ -193,6 +193,10 @@ int cslam_ekf_rows_launches(cslam_ekf_t h, long long* launches);
  * kernels queue behind it; with e.g. 2 * CUs / instances each instance keeps to its share and their kernels interleave. */
 int cslam_ekf_set_pgemm_workgroups(cslam_ekf_t h, int workgroups);
 
+/* Whole 128 x 128 tiles and 32-row strips of the handle's last f32 covariance-downdate launch of at most 128 columns (the
+ * kernel's tail phase, CSLAM_PGEMM_TAIL; strips = 0: the launch without it).  Lets a test confirm that the strip path ran. */
+int cslam_ekf_pgemm_split(cslam_ekf_t h, int* whole_tiles, int* strips);
+
 /* Monte-Carlo driver (BASELINE configs[4]; the reference's unit is one filter loop, test/main.cpp:132-200): runs
  * `steps` x { predict(v[t], swa[t], Q, wb, dt); update(Z_t, R, idf_t, batch) } on each of `count` INDEPENDENT filter
  * handles at once, one host thread and one stream pair per handle.  dZ[i] / d_idf[i]: device-resident inputs of
@@ -232,6 +236,8 @@ int cslam_ekf_batch_info(cslam_ekf_batch_t h, int* instances, int* n, long long*
  * get: synchronises, sum of milliseconds and number of the launches timed since profiling was switched on. */
 int cslam_ekf_batch_set_profiling(cslam_ekf_batch_t h, int every);
 int cslam_ekf_batch_get_pgemm_time(cslam_ekf_batch_t h, double* ms_sum, int* launches);
+/* As cslam_ekf_pgemm_split, of the batch's last covariance-downdate launch (all instances together). */
+int cslam_ekf_batch_pgemm_split(cslam_ekf_batch_t h, int* whole_tiles, int* strips);
 
 /* ---- the reference's filter loop through the batch (test/main.cpp:132-200: predict + observeHeading per control step,
  *      update + augment per observation step), one call per reference call, every call one state for all instances.
