@@ -117,6 +117,22 @@ PF_DRAW_SYMBOLS = ("cslam_pf_seed_draws", "cslam_pf_get_draws", "cslam_pf_sample
 PF_DRAW_OBS_MAX = 32  # kPfDrawObsMax of csrc/pf_draw_kernels.hpp: observations that travel as kernel arguments
 
 
+# The particle filter's score and trajectory log kept on the device (test/main.cpp:330, slam.h:493-511, 513-539): the
+# totals use the SCORE_* indices above; a series record is 4 floats, a track record 5 doubles.
+PF_SCORE_MEAN, PF_SCORE_BEST = 0, 1
+PF_SCORE_SERIES, PF_SCORE_TRACK = 4, 5
+_PROTOTYPES.update({
+    "cslam_pf_score_reset": [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double],
+    "cslam_pf_score_set_truth": [C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_pf_score": [C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_pf_score_sharded": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_pf_get_scores": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                            C.POINTER(C.c_longlong)],
+})
+PF_SCORE_SYMBOLS = ("cslam_pf_score_reset", "cslam_pf_score_set_truth", "cslam_pf_score", "cslam_pf_score_sharded",
+                    "cslam_pf_get_scores")
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
     text = open(header_path).read()

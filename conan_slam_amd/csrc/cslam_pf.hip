@@ -21,6 +21,7 @@
 #include "pf_draw_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
+#include "pf_score_kernels.hpp"
 #include "pf_staging.hpp"
 
 using namespace cslam;
@@ -70,6 +71,12 @@ struct PfBase
     virtual int best_particle(Comm* c, int pick, long long* index, void* w, void* Xv, void* Pv, void* XF, void* PF) = 0;
     virtual int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF)              = 0;
     virtual int get_all_features(void* XF_all)                                                                      = 0;
+    // the score of the estimate, kept on the device (pf_score_kernels.hpp); c == nullptr: this handle alone
+    virtual int score_reset(int estimator, int series_capacity, double gate_pose, double gate_lm)                    = 0;
+    virtual int score_set_truth(const double* lm_true, int count)                                                   = 0;
+    virtual int score(Comm* c, const double* xv_true, int with_map)                                                 = 0;
+    virtual int get_scores(double* totals, float* series, double* track, int capacity_records, int* records,
+                           long long* calls)                                                                        = 0;
     // per-particle data association (pf_assoc_kernels.hpp) and the consumers of its table
     virtual int associate(const void* Z, int m, const void* R, double gate1, double gate2)                          = 0;
     virtual int get_association(int* idf, int* kind, double* summary)                                               = 0;
@@ -103,6 +110,7 @@ struct Pf : PfBase
     PfResampleBufs<T>  rs;
     PfShardedBufs<T>   sh;
     PfEstimateBufs<T>  est;
+    PfScoreBufs        sc;
     PfAssocTables<T>   assoc;
     PfDraws<T>         draws;
 
@@ -858,14 +866,9 @@ struct Pf : PfBase
         return CSLAM_OK;
     }
 
-    int best_particle(Comm* c, int pick, long long* index, void* w, void* Xv, void* Pv, void* XF, void* PF) override
+    // the launches of the best-particle read: the block [hdr | rec] of the pick in est.out, nothing fetched
+    int launch_best(Comm* c, int pick)
     {
-        if (pick != kEstPickMax && pick != kEstPickMin)
-        {
-            return fail(CSLAM_ERR_BAD_ARG, "pf_best_particle: pick %d is neither CSLAM_PF_PICK_MAX nor _MIN", pick);
-        }
-        CSLAM_TRY(use_device());
-        CSLAM_TRY(est_comm_ok(c, "pf_best_particle_sharded"));
         const int    nch = est_chunks(), len = 13 + 6 * nf, world = c ? c->world : 1;
         const size_t od  = est_out_doubles();
         // (everything that can fail is allocated before the first collective)
@@ -891,6 +894,19 @@ struct Pf : PfBase
                                est.bestRecAll.get(), world, len, pick, est.out.get(), est.rec(est.out.get()));
             CSLAM_HIP_TRY(hipGetLastError());
         }
+        return CSLAM_OK;
+    }
+
+    int best_particle(Comm* c, int pick, long long* index, void* w, void* Xv, void* Pv, void* XF, void* PF) override
+    {
+        if (pick != kEstPickMax && pick != kEstPickMin)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_best_particle: pick %d is neither CSLAM_PF_PICK_MAX nor _MIN", pick);
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(est_comm_ok(c, "pf_best_particle_sharded"));
+        CSLAM_TRY(launch_best(c, pick));
+        const int  len = 13 + 6 * nf;
         const bool map = nf > 0 && (XF || PF);
         CSLAM_TRY(est.fetch(est.out.get(), map ? (size_t)len : 13, stream));
         if (index)
@@ -901,11 +917,9 @@ struct Pf : PfBase
         return CSLAM_OK;
     }
 
-    int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF) override
+    // the launches of the mixture moments (map: with every feature's): the block [hdr | rec] in est.out, nothing fetched
+    int launch_estimate(Comm* c, bool map)
     {
-        CSLAM_TRY(use_device());
-        CSLAM_TRY(est_comm_ok(c, "pf_estimate_sharded"));
-        const bool   map = nf > 0 && (XF || PF);
         const int    nch = est_chunks(), world = c ? c->world : 1;
         const int    stride = kEstSumHdr + (map ? kEstSumFeat * nf : 0);
         CSLAM_TRY(est_grow_common((size_t)nch * (kEstP1 + kEstP2Pose + (map ? (size_t)kEstP2Feat * nf : 0)),
@@ -935,7 +949,16 @@ struct Pf : PfBase
                                stride, nf, map ? 1 : 0, out, est.rec(out));
             CSLAM_HIP_TRY(hipGetLastError());
         }
-        CSLAM_TRY(est.fetch(out, map ? (size_t)(13 + 6 * nf) : 13, stream));
+        return CSLAM_OK;
+    }
+
+    int estimate(Comm* c, double* w_sum, double* neff, void* Xv, void* Pv, void* XF, void* PF) override
+    {
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(est_comm_ok(c, "pf_estimate_sharded"));
+        const bool map = nf > 0 && (XF || PF);
+        CSLAM_TRY(launch_estimate(c, map));
+        CSLAM_TRY(est.fetch(est.out.get(), map ? (size_t)(13 + 6 * nf) : 13, stream));
         if (w_sum)
         {
             *w_sum = est.h_hdr()[0];
@@ -964,6 +987,128 @@ struct Pf : PfBase
         CSLAM_HIP_TRY(hipMemcpyAsync(est.hEst.get(), est.feat.get(), count * sizeof(T), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         std::memcpy(XF_all, est.hEst.get(), count * sizeof(T));
+        return CSLAM_OK;
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // The score of the estimate and its trajectory log, kept in HBM (pf_score_kernels.hpp).  A score call queues the
+    // launches of the read path above -- up to, but without, the fetch -- and the two score kernels behind them on the
+    // estimate block; only get_scores synchronises and copies.
+    // ------------------------------------------------------------------------------------------------
+    int score_reset(int estimator, int series_capacity, double gate_pose, double gate_lm) override
+    {
+        if (!PfScoreBook::reset_args_ok(estimator, series_capacity))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_score_reset: estimator %d (CSLAM_PF_SCORE_MEAN or _BEST), series_capacity %d (>= 0)",
+                        estimator, series_capacity);
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(sc.ensure_base(CSLAM_SCORE_FIELDS, nfcap, stream));
+        CSLAM_TRY(sc.ensure_log(series_capacity, stream));
+        CSLAM_HIP_TRY(hipMemsetAsync(sc.base.totals.get(), 0, CSLAM_SCORE_FIELDS * sizeof(double), stream));
+        if (sc.log.series)
+        {
+            CSLAM_HIP_TRY(hipMemsetAsync(sc.log.series.get(), 0, sc.log.series.count() * sizeof(float), stream));
+            CSLAM_HIP_TRY(hipMemsetAsync(sc.log.track.get(), 0, sc.log.track.count() * sizeof(double), stream));
+        }
+        sc.book.reset(estimator, series_capacity, gate_pose, gate_lm);
+        return CSLAM_OK;
+    }
+
+    int score_set_truth(const double* lm_true, int count) override
+    {
+        if (!PfScoreBook::truth_args_ok(count, nfcap) || (count > 0 && !lm_true))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_score_set_truth: count %d outside 0..max_features=%d, or null rows", count, nfcap);
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(sc.ensure_base(CSLAM_SCORE_FIELDS, nfcap, stream));
+        if (count > 0)
+        {
+            // (behind whatever score call still reads the old rows; the host array is consumed before the return)
+            CSLAM_HIP_TRY(hipMemcpyAsync(sc.base.truth.get(), lm_true, (size_t)2 * count * sizeof(double),
+                                         hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        }
+        sc.book.set_truth_count(count);
+        return CSLAM_OK;
+    }
+
+    int score(Comm* c, const double* xv_true, int with_map) override
+    {
+        const char* who = c ? "pf_score_sharded" : "pf_score";
+        if (!xv_true || !std::isfinite(xv_true[0]) || !std::isfinite(xv_true[1]) || !std::isfinite(xv_true[2]))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: xv_true is null or not finite", who);
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(est_comm_ok(c, who));
+        // (everything that can fail is allocated before the first collective: the score's here, the read path's in its
+        // launch helpers)
+        CSLAM_TRY(sc.ensure_base(CSLAM_SCORE_FIELDS, nfcap, stream));
+        const PfScoreBook& bk    = sc.book;
+        const int          count = bk.scored(nf, with_map);
+        if (bk.estimator() == CSLAM_PF_SCORE_BEST)
+        {
+            CSLAM_TRY(launch_best(c, kEstPickMax));
+        }
+        else
+        {
+            CSLAM_TRY(launch_estimate(c, count > 0));
+        }
+        const double* hdr    = est.out.get();
+        const T*      rec    = est.rec(est.out.get());
+        const int     blocks = PfScoreBook::blocks(count);
+        if (count > 0)
+        {
+            hipLaunchKernelGGL(pf_score_landmarks_kernel<T>, dim3(blocks), dim3(256), 0, stream, rec, nf, count,
+                               sc.base.truth.get(), bk.gate_lm(), sc.base.parts.get());
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(pf_score_finish_kernel<T>, dim3(1), dim3(64), 0, stream, hdr, rec, sc.base.parts.get(), blocks,
+                           xv_true[0], xv_true[1], xv_true[2], bk.gate_pose(), bk.estimator(), sc.base.totals.get(),
+                           sc.log.series.get(), sc.log.track.get(), (double)bk.next_record());
+        CSLAM_HIP_TRY(hipGetLastError());
+        sc.book.called();
+        return CSLAM_OK;
+    }
+
+    int get_scores(double* totals, float* series, double* track, int capacity_records, int* records, long long* calls) override
+    {
+        if (capacity_records < 0)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_get_scores: capacity_records %d", capacity_records);
+        }
+        CSLAM_TRY(use_device());
+        const PfScoreBook& bk = sc.book;
+        const size_t       n  = (size_t)bk.records_to_copy(capacity_records);
+        if (totals && !sc.allocated())
+        {
+            std::fill(totals, totals + CSLAM_SCORE_FIELDS, 0.0);
+        }
+        else if (totals)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(totals, sc.base.totals.get(), CSLAM_SCORE_FIELDS * sizeof(double),
+                                         hipMemcpyDeviceToHost, stream));
+        }
+        if (series && n > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(series, sc.log.series.get(), n * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        if (track && n > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(track, sc.log.track.get(), n * kPfScoreTrack * sizeof(double), hipMemcpyDeviceToHost,
+                                         stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        if (records)
+        {
+            *records = bk.records();
+        }
+        if (calls)
+        {
+            *calls = bk.calls();
+        }
         return CSLAM_OK;
     }
 
@@ -1673,6 +1818,42 @@ int cslam_pf_get_all_features(cslam_pf_t h, void* XF_all)
 {
     CSLAM_NEED(h);
     return B(h)->get_all_features(XF_all);
+}
+
+/* the score of the estimate test/main.cpp:330 prints (slam.h:493-511; the map: slam.h:513-539), kept on the device */
+int cslam_pf_score_reset(cslam_pf_t h, int estimator, int series_capacity, double gate_pose, double gate_lm)
+{
+    CSLAM_NEED(h);
+    return B(h)->score_reset(estimator, series_capacity, gate_pose, gate_lm);
+}
+
+int cslam_pf_score_set_truth(cslam_pf_t h, const double* lm_true, int count)
+{
+    CSLAM_NEED(h);
+    return B(h)->score_set_truth(lm_true, count);
+}
+
+int cslam_pf_score(cslam_pf_t h, const double* xv_true, int with_map)
+{
+    CSLAM_NEED(h);
+    return B(h)->score(nullptr, xv_true, with_map);
+}
+
+int cslam_pf_score_sharded(cslam_pf_t h, cslam_comm_t comm, const double* xv_true, int with_map)
+{
+    CSLAM_NEED(h);
+    if (!comm)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pf_score_sharded: null communicator");
+    }
+    return B(h)->score(reinterpret_cast<Comm*>(comm), xv_true, with_map);
+}
+
+int cslam_pf_get_scores(cslam_pf_t h, double* totals, float* series, double* track, int capacity_records, int* records,
+                        long long* calls)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_scores(totals, series, track, capacity_records, records, calls);
 }
 
 /* EKF.cpp:131-144, 235-326 on every particle's own state */

@@ -173,6 +173,59 @@ struct PfEstimateBufs
     }
 };
 
+// The score kept on the device (pf_score_kernels.hpp) and its book.  Two levels, each all-or-nothing: the base (totals,
+// the landmark kernel's scratch and the truth rows, sized for max_features once) and the log (series and track, sized by
+// the largest series_capacity a reset has asked for).  A handle that never calls a score function allocates neither.
+struct PfScoreBufs
+{
+    struct Base
+    {
+        DevBuf<double> totals; // [fields]
+        DevBuf<double> parts;  // [blocks(max_features)][5]
+        DevBuf<double> truth;  // [max_features][2]
+    };
+    struct Log
+    {
+        DevBuf<float>  series; // [capacity][4]
+        DevBuf<double> track;  // [capacity][5]
+    };
+    Base        base;
+    Log         log;
+    PfScoreBook book;
+
+    bool allocated() const { return (bool)base.totals; }
+
+    // the base, with zeroed totals (a handle that has never been reset scores from zero)
+    int ensure_base(int fields, int nfcap, hipStream_t stream)
+    {
+        if (allocated())
+        {
+            return CSLAM_OK;
+        }
+        const size_t cf = (size_t)std::max(nfcap, 1);
+        Base         b;
+        CSLAM_TRY(b.totals.alloc_zeroed((size_t)fields, stream));
+        CSLAM_TRY(b.parts.alloc((size_t)PfScoreBook::blocks((int)cf) * 5));
+        CSLAM_TRY(b.truth.alloc(2 * cf));
+        base = std::move(b);
+        return CSLAM_OK;
+    }
+    // room for series_capacity records (the old log is released after the stream has been waited for)
+    int ensure_log(int series_capacity, hipStream_t stream)
+    {
+        if (PfScoreBook::series_fits(log.series.count() / 4, series_capacity))
+        {
+            return CSLAM_OK;
+        }
+        Log l;
+        CSLAM_TRY(l.series.alloc((size_t)series_capacity * 4));
+        CSLAM_TRY(l.track.alloc((size_t)series_capacity * 5));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still writes the old log
+        log = std::move(l);
+        return CSLAM_OK;
+    }
+};
+
 // The tables of the per-particle association and what they describe (PfAssocMemo: growing the tables forgets it).
 template <typename T>
 struct PfAssocTables

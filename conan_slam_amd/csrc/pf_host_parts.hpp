@@ -1,7 +1,8 @@
 // pf_host_parts.hpp -- the arithmetic and bookkeeping of the particle handle that needs no GPU: the layout of the device
 // staging area, the memo of what it holds, the validity of the association tables, and the small host loops of the
-// fused step, the sharded exchange and the strata table.  No HIP include: tests/host/pf_host_parts_check.cpp builds it
-// with plain g++ (and under the address and undefined-behaviour sanitizers).
+// fused step, the sharded exchange and the strata table, and the book of the device-side score.  No HIP include:
+// tests/host/pf_host_parts_check.cpp and pf_score_book_check.cpp build it with plain g++ (and under the address and
+// undefined-behaviour sanitizers).
 #pragma once
 
 #include <algorithm>
@@ -195,5 +196,60 @@ inline bool pf_seed_args_ok(long long first_global, long long n_global, int np, 
     *n_strata = (n_global <= 0x7fffffffLL) ? n_global : 0;
     return !(first_global < 0 || n_global >= (1LL << 32) || first_global > n_global - np);
 }
+
+// The bookkeeping of the score kept on the device (cslam_pf_score*): which estimate is scored, the gates, how many
+// records the series and the track hold, how many truth rows there are, and the calls since the last reset.  The
+// default state is that of reset(0, 0, 0, 0): a score call without a prior reset behaves as after it.
+class PfScoreBook
+{
+  public:
+    static constexpr double kGatePose = 7.8147; // the 95 % chi-square points of 3 and 2 degrees of freedom
+    static constexpr double kGateLm   = 5.9915;
+    static constexpr int    kLanes    = 256; // features per workgroup of the landmark kernel
+
+    static bool reset_args_ok(int estimator, int series_capacity)
+    {
+        return (estimator == 0 || estimator == 1) && series_capacity >= 0;
+    }
+    // (the arguments have passed reset_args_ok; a gate <= 0, or NaN, selects its default).  The truth rows are kept.
+    void reset(int estimator, int series_capacity, double gate_pose, double gate_lm)
+    {
+        estimator_ = estimator;
+        capacity_  = series_capacity;
+        gate_pose_ = gate_pose > 0.0 ? gate_pose : kGatePose;
+        gate_lm_   = gate_lm > 0.0 ? gate_lm : kGateLm;
+        calls_     = 0;
+    }
+    static bool truth_args_ok(int count, int max_features) { return count >= 0 && count <= max_features; }
+    void        set_truth_count(int count) { truth_ = count; }
+
+    int       estimator() const { return estimator_; }
+    int       capacity() const { return capacity_; }
+    int       truth_count() const { return truth_; }
+    double    gate_pose() const { return gate_pose_; }
+    double    gate_lm() const { return gate_lm_; }
+    long long calls() const { return calls_; }
+
+    // features one call scores: min(nf, truth rows) with the map, none without
+    int scored(int nf, int with_map) const { return with_map ? std::min(nf, truth_) : 0; }
+    // workgroups (= scratch slots) of the landmark kernel for c features
+    static int blocks(int c) { return (c + kLanes - 1) / kLanes; }
+    // the record the NEXT call writes, or -1 when the series is full or absent
+    long long next_record() const { return calls_ < (long long)capacity_ ? calls_ : -1; }
+    void      called() { calls_++; }
+    // records held, and how many of them a read into room for capacity_records copies
+    int records() const { return (int)std::min(calls_, (long long)capacity_); }
+    int records_to_copy(int capacity_records) const { return std::max(0, std::min(records(), capacity_records)); }
+    // does a series allocated for `have` records serve a reset to series_capacity?  (it only ever grows)
+    static bool series_fits(size_t have, int series_capacity) { return (size_t)series_capacity <= have; }
+
+  private:
+    int       estimator_ = 0;
+    int       capacity_  = 0;
+    int       truth_     = 0;
+    double    gate_pose_ = kGatePose;
+    double    gate_lm_   = kGateLm;
+    long long calls_     = 0;
+};
 
 } // namespace cslam

@@ -187,6 +187,9 @@ class LoopbackComm:
 BestParticle = namedtuple("BestParticle", "index w Xv Pv XF PF")
 Estimate = namedtuple("Estimate", "w_sum neff Xv Pv XF PF")  # XF / PF are None when the map was not asked for
 _PICKS = {"max": _capi.PF_PICK_MAX, "min": _capi.PF_PICK_MIN}
+# what scores() returns: totals [SCORE_FIELDS] float64, series [records, 4] float32, track [records, 5] float64, calls
+PfScores = namedtuple("PfScores", "totals series track calls")
+_ESTIMATORS = {"mean": _capi.PF_SCORE_MEAN, "best": _capi.PF_SCORE_BEST}
 
 
 # ------------------------------------------------------------------------------------------------
@@ -560,6 +563,46 @@ class ParticleShard:
     def estimate_sharded(self, comm, want_map: bool = True) -> Estimate:
         """estimate over the set sharded across comm.world ranks: identical bits on every rank."""
         return self._estimate(comm, want_map)
+
+    # ---- the score of the estimate and its trajectory log, kept on the device (cslam_pf_score*)
+    def score_reset(self, estimator: str = "mean", series_capacity: int = 0, gate_pose: float = 0.0, gate_lm: float = 0.0):
+        """Zero the totals, the series, the track and the call count; estimator "mean" scores what estimate() returns,
+        "best" what best_particle("max") returns.  A gate <= 0 selects the 95 % chi-square point.  Keeps the truth."""
+        est = _ESTIMATORS[estimator] if isinstance(estimator, str) else int(estimator)
+        check(self._L.cslam_pf_score_reset(self._h, C.c_int(est), C.c_int(int(series_capacity)),
+                                           C.c_double(float(gate_pose)), C.c_double(float(gate_lm))))
+
+    def score_set_truth(self, lm_true):
+        """Row j of lm_true ([count, 2]) is the true position of state feature j + 1."""
+        t = np.ascontiguousarray(np.asarray(lm_true, dtype=np.float64).reshape(-1, 2))
+        check(self._L.cslam_pf_score_set_truth(self._h, _vp(t) if t.size else None, C.c_int(t.shape[0])))
+
+    @staticmethod
+    def _xv_true(xv_true):
+        return np.ascontiguousarray(np.asarray(xv_true, dtype=np.float64).reshape(3))
+
+    def score(self, xv_true, with_map: bool = True):
+        """One score step of the current estimate against the true pose (cslam_pf_score): asynchronous, nothing returns."""
+        x = self._xv_true(xv_true)
+        check(self._L.cslam_pf_score(self._h, _vp(x), C.c_int(1 if with_map else 0)))
+
+    def score_sharded(self, comm, xv_true, with_map: bool = True):
+        """score over the set sharded across comm.world ranks: every rank ends with identical totals, series and track."""
+        x = self._xv_true(xv_true)
+        check(self._L.cslam_pf_score_sharded(self._h, comm._h, _vp(x), C.c_int(1 if with_map else 0)))
+
+    def scores(self, capacity_records: int | None = None) -> PfScores:
+        """The one synchronising call of the score (cslam_pf_get_scores): totals, the series and track records held (at
+        most capacity_records of them) and the number of score calls since the reset."""
+        rec, calls = C.c_int(0), C.c_longlong(0)
+        check(self._L.cslam_pf_get_scores(self._h, None, None, None, C.c_int(0), C.byref(rec), C.byref(calls)))
+        n = rec.value if capacity_records is None else min(rec.value, int(capacity_records))
+        totals = np.zeros(_capi.SCORE_FIELDS, np.float64)
+        series = np.zeros((n, _capi.PF_SCORE_SERIES), np.float32)
+        track = np.zeros((n, _capi.PF_SCORE_TRACK), np.float64)
+        check(self._L.cslam_pf_get_scores(self._h, _vp(totals), _vp(series) if n else None, _vp(track) if n else None,
+                                          C.c_int(n), C.byref(rec), C.byref(calls)))
+        return PfScores(totals, series, track, int(calls.value))
 
     def all_features(self) -> np.ndarray:
         """Slam::extractFeaturesFromParticles -- slam.h:513-539: 2 x (n_local * nf), particle p's block at column p * nf."""

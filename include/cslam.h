@@ -285,7 +285,8 @@ int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, flo
  *      observation step -- the pose test/main.cpp:136 prints against the true pose, and the blocks EKF.cpp:131-144 reads
  *      against a true position per state feature.  All error and NEES arithmetic is f64 on the device from the f32
  *      state; the sums are formed in a fixed order without atomics, so the totals of a run are reproducible bit for
- *      bit.  f32 batch only: the single handle, the f64 engine and the particle filter have no scorer.
+ *      bit.  f32 batch only: the single handle and the f64 engine have no scorer; the particle filter has its own,
+ *      cslam_pf_score* below, with the same rules and the same total indices.
  * Indices into one instance's totals (doubles): */
 enum { CSLAM_SCORE_POSE_N, CSLAM_SCORE_POSE_BAD, CSLAM_SCORE_POSE_IN, CSLAM_SCORE_POSE_ERR2 /* sum ex^2+ey^2 */,
        CSLAM_SCORE_POSE_EPHI2 /* sum wrapped heading error^2 */, CSLAM_SCORE_POSE_NEES /* sum e^T Pvv^-1 e */,
@@ -585,6 +586,55 @@ int cslam_pf_best_particle_sharded(cslam_pf_t h, cslam_comm_t comm, int pick, lo
                                    void* Pv, void* XF, void* PF);
 int cslam_pf_estimate_sharded(cslam_pf_t h, cslam_comm_t comm, double* w_sum, double* neff, void* Xv, void* Pv, void* XF,
                               void* PF);
+
+/* ---- the score and the trajectory log of the estimate, kept on the device (conan_slam_amd/csrc/pf_score_kernels.hpp).
+ * The reference's PF loop prints its estimate on every iteration (test/main.cpp:330, from slam.h:493-511; the map:
+ * slam.h:513-539), and a Monte-Carlo study scores that estimate against the truth after every step.  These calls do both
+ * without draining the stream once per step: a score call queues the kernels of cslam_pf_estimate (or
+ * cslam_pf_best_particle) up to, but without, the fetch, and two score kernels behind them that read the estimate as it
+ * lies in HBM, i.e. the values those calls would have returned, rounded to the handle's dtype.  Totals, series and track
+ * are read once, at the end.  All error and NEES arithmetic is f64 on the device; the sums are formed in a fixed order
+ * without atomics, so two identical runs give identical bits.  The rules, the gates and the CSLAM_SCORE_* indices are
+ * those of cslam_ekf_batch_score with one instance.  The particle store is never written. */
+#define CSLAM_PF_SCORE_MEAN 0 /* the mixture moments of cslam_pf_estimate */
+#define CSLAM_PF_SCORE_BEST 1 /* the maximum-weight particle, cslam_pf_best_particle(CSLAM_PF_PICK_MAX) */
+/* Zeroes the totals, the series, the track and the call count, and chooses which estimate the following calls score
+ * (replaces scoring state kept on the host beside test/main.cpp:330; slam.h:493-511).  series_capacity >= 0 records of
+ * series and track alike (0: totals only).  A gate <= 0 selects the 95 % chi-square point: 7.8147 for the pose, 5.9915
+ * for a landmark.  The truth rows are kept.  A score call without a prior reset behaves as after
+ * score_reset(h, CSLAM_PF_SCORE_MEAN, 0, 0, 0).  A bad estimator or a negative capacity: CSLAM_ERR_BAD_ARG, nothing
+ * changed.  A handle that never calls a score function allocates nothing for it. */
+int cslam_pf_score_reset(cslam_pf_t h, int estimator, int series_capacity, double gate_pose, double gate_lm);
+/* The truth the map part of the estimate (test/main.cpp:330, slam.h:493-511) is scored against: the true position of
+ * state feature j + 1 is row j of lm_true (host, [count][2] doubles; the features slam.h:513-539 assembles), copied into
+ * a device buffer sized for max_features before the call returns.  Features beyond `count` are not scored.  count < 0 or
+ * count > max_features: CSLAM_ERR_BAD_ARG, nothing changed. */
+int cslam_pf_score_set_truth(cslam_pf_t h, const double* lm_true /* host [count][2] */, int count);
+/* One score step against the true pose xv_true (host [3], finite; it travels as kernel arguments): the estimate
+ * test/main.cpp:330 prints (slam.h:493-511) -- Xv, Pv and, when with_map != 0, XF, PF of the first
+ * c = min(n_features, truth count) features (slam.h:513-539) -- scored by the pose, landmark and series rules written at
+ * cslam_ekf_batch_score above.  with_map == 0 scores no feature: the landmark totals are untouched and series fields 2
+ * and 3 are NaN.  A degenerate weight sum makes the estimate NaN, which counts POSE_BAD += 1 and LM_BAD += c.
+ *   track     while there is room, one record of five doubles per call: (Xv[0], Xv[1], Xv[2], W, Neff) for
+ *             CSLAM_PF_SCORE_MEAN, (Xv[0], Xv[1], Xv[2], w_best, index) for CSLAM_PF_SCORE_BEST -- bit for bit what
+ *             cslam_pf_estimate / cslam_pf_best_particle would have returned at that point, widened to double.
+ * Returns when its kernels are enqueued on the handle's stream: no synchronise, no device-to-host copy, no staged
+ * host-to-device copy (cslam_pf_stage_copies does not move).  A NULL or non-finite xv_true: CSLAM_ERR_BAD_ARG, nothing
+ * changed. */
+int cslam_pf_score(cslam_pf_t h, const double* xv_true /* host [3] */, int with_map);
+/* cslam_pf_score (test/main.cpp:330, slam.h:493-511, slam.h:513-539) over a set SHARDED as for cslam_pf_estimate_sharded:
+ * summaries, all-gather and combine as there, then the same score kernels on the merged block.  Every rank makes the
+ * same call (same reset, same truth) and ends with identical totals, series and track; CSLAM_PF_SCORE_BEST records the
+ * GLOBAL index.  A communicator of one rank gives the unsharded call's bits.  Everything that can fail is allocated
+ * before the first collective. */
+int cslam_pf_score_sharded(cslam_pf_t h, cslam_comm_t comm, const double* xv_true /* host [3] */, int with_map);
+/* The one synchronising call of the score: copies the totals [CSLAM_SCORE_FIELDS], up to capacity_records series records
+ * [records][4] and track records [records][5] (the read-out that replaces one cslam_pf_estimate per step:
+ * test/main.cpp:330, slam.h:493-511).  *records = min(calls, series_capacity) is the number of records held (at most
+ * capacity_records of them are copied), *calls counts every score call since the reset (calls beyond the series
+ * capacity still enter the totals).  Any output pointer may be NULL. */
+int cslam_pf_get_scores(cslam_pf_t h, double* totals /* [CSLAM_SCORE_FIELDS] */, float* series /* [records][4] */,
+                        double* track /* [records][5] */, int capacity_records, int* records, long long* calls);
 
 /* ------------------------------------------------------------------------------------------------
  * Device-side observation generator and known-association table: the per-step host work of

@@ -20,6 +20,8 @@
 //   HipPF::extractStates     slam.h:493-511                          -> cslam_pf_best_particle
 //   HipPF::extractFeatures   slam.h:513-539                          -> cslam_pf_get_all_features
 //   HipPF::extractMap        (the mixture's feature means)           -> cslam_pf_estimate
+//   HipPF::scoreReset / scoreTruth / score / scores   (the estimate test/main.cpp:330 prints, scored and logged on the
+//                            device; slam.h:493-511, 513-539)        -> cslam_pf_score_reset / _set_truth / _score / _get_scores
 //
 // Ownership: the reference passes X and P by reference into every call; here the handle owns them in HBM.  X is
 // refreshed after every call (the driver reads it every iteration, test/main.cpp:136); P is refreshed on demand
@@ -431,6 +433,60 @@ class HipPF : public PF
             report(cslam_pf_estimate(h_, nullptr, nullptr, nullptr, nullptr, XF.data(), nullptr), "HipPF::extractMap");
         }
         return XF;
+    }
+
+    // ---- the score of the estimate and its trajectory log, kept on the device: a study that scores the line
+    //      test/main.cpp:330 prints (slam.h:493-511, the map slam.h:513-539) after every step without reading it back
+    /// estimator: CSLAM_PF_SCORE_MEAN (what extractMap's estimate is) or CSLAM_PF_SCORE_BEST (what extractStates returns)
+    void scoreReset(int estimator = CSLAM_PF_SCORE_MEAN, int seriesCapacity = 0, double gatePose = 0.0, double gateLm = 0.0)
+    {
+        report(cslam_pf_score_reset(h_, estimator, seriesCapacity, gatePose, gateLm), "HipPF::scoreReset");
+    }
+    /// lmTrue: 2 x count, column j the true position of state feature j + 1 (the layout of the reference's landmarks)
+    void scoreTruth(const Eigen::MatrixXf& lmTrue)
+    {
+        const int           count = static_cast<int>(lmTrue.cols());
+        std::vector<double> rows(static_cast<size_t>(2 * (count > 0 ? count : 1)));
+        for (int j = 0; j < count; j++)
+        {
+            rows[static_cast<size_t>(2 * j)]     = static_cast<double>(lmTrue(0, j));
+            rows[static_cast<size_t>(2 * j + 1)] = static_cast<double>(lmTrue(1, j));
+        }
+        report(cslam_pf_score_set_truth(h_, rows.data(), count), "HipPF::scoreTruth");
+    }
+    /// one score step against the true pose (3); asynchronous, nothing returns
+    void score(const Eigen::VectorXf& xvTrue, bool withMap = true)
+    {
+        const double x[3] = {static_cast<double>(xvTrue(0)), static_cast<double>(xvTrue(1)), static_cast<double>(xvTrue(2))};
+        if (comm_)
+        {
+            report(cslam_pf_score_sharded(h_, comm_, x, withMap ? 1 : 0), "HipPF::score");
+        }
+        else
+        {
+            report(cslam_pf_score(h_, x, withMap ? 1 : 0), "HipPF::score");
+        }
+    }
+    /// the one synchronising read: totals [CSLAM_SCORE_FIELDS]; series (4 floats) and track (5 doubles) per record held;
+    /// returns the number of score calls since the reset
+    long long scores(std::vector<double>& totals, std::vector<float>* series = nullptr, std::vector<double>* track = nullptr)
+    {
+        int       records = 0;
+        long long calls   = 0;
+        totals.assign(static_cast<size_t>(CSLAM_SCORE_FIELDS), 0.0);
+        report(cslam_pf_get_scores(h_, nullptr, nullptr, nullptr, 0, &records, &calls), "HipPF::scores");
+        if (series)
+        {
+            series->assign(static_cast<size_t>(4 * records), 0.f);
+        }
+        if (track)
+        {
+            track->assign(static_cast<size_t>(5 * records), 0.0);
+        }
+        report(cslam_pf_get_scores(h_, totals.data(), series && records ? series->data() : nullptr,
+                                   track && records ? track->data() : nullptr, records, &records, &calls),
+               "HipPF::scores");
+        return calls;
     }
 
   private:
