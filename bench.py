@@ -7,7 +7,13 @@ observations per batch update (k = 64).  A "step" is one predict() + one batch u
 (EKF.cpp:406-455, 481-496) on synthetic inputs (conan_slam_amd/synth.py) that are already
 resident in HBM when the timed region starts; nothing returns to the host inside the timed region.
 
-  --workload ekf  (default) the headline line above; sub-records: `per_call` (median wall time of a call with X
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what the headline figure needs and no more: it sets up,
+warms up (a short warm-up is preceded by the cold pass and the preheat, which the state of the timed steps depends on),
+times the K steps, writes --dump-outputs and prints the line; its `roofline` is priced on the launches sampled inside the
+timed region.  Everything that takes a run of its own -- the sub-records below, the bracketed roofline pass, the
+single-instance run of `--workload mc`, the CPU baselines -- is measured with `--full` only.
+
+  --workload ekf  (default) the headline line above; with --full the sub-records: `per_call` (median wall time of a call with X
                   returned to the host each call), `dropin` (what INTEGRATION.md's adapter does: sync mode,
                   host Z / idf, X read back after predict and after update), `reference_loop` (the cadence of the
                   reference's driver, test/main.cpp:132-200: 6 x (predict + observeHeading) + update + augment).
@@ -24,7 +30,7 @@ The JSON line also carries
   roofline      the covariance downdate kernel (P -= W1 W1^T, slam.h:260), timed live with HIP events on the stream
                 it is launched on; `achieved` prices a launch on the bytes the symmetric block-lower algorithm must
                 move (DESIGN.md 6), the full-storage figure of SURVEY 8d is a separate, clearly named field;
-  cpu_baseline  the CPU oracle's dense-order port of the same step (oracle/slam_oracle_fast.c) on one core, plus a
+  cpu_baseline  (--full) the CPU oracle's dense-order port of the same step (oracle/slam_oracle_fast.c) on one core, plus a
                 courtesy all-cores numpy/OpenBLAS row; this host, bounded sample, rank 0 / N = 1 only.
 """
 from __future__ import annotations
@@ -67,6 +73,11 @@ def parse_args():
                          "launches the HIP runtime stalls the enqueueing thread once for 30-60 ms while the GPU idles "
                          "(tools/drift_probe.py; f64 N=1000: warm-up 20/400/1000 + 1000 steps -> 80 / 123 / 68.7 us per "
                          "step).  A long warm-up gets that one-time event out of the way")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure, each in a run of its own after the timed steps: "
+                         "ekf: the bracketed roofline pass, immediate_mode, per_call, dropin, reference_loop, ref_exact_healthy; "
+                         "mc: single_instance and concurrency_gain; every workload: cpu_baseline.  Off by default: a plain run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--preheat-ms", type=float, default=400.0,
                     help="ekf: when --warmup is short (< 400 steps), the same step loop is first run untimed for about this "
                          "long, so that the W warm-up + K timed steps meet a GPU at its working clocks (a cold MI355X runs "
@@ -94,9 +105,11 @@ def parse_args():
     ap.add_argument("--features", type=int, default=1000)
     ap.add_argument("--pf-obs", type=int, default=8)
     ap.add_argument("--force-resample", action="store_true", help="pf: resample on every step (worst case exchange)")
-    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the per_call / dropin / reference_loop sub-records")
+    ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0, help="--full: time budget of the cpu_baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline record")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="--full without the ekf sub-records (bracketed pass, immediate_mode, per_call, dropin, reference_loop, "
+                         "ref_exact_healthy)")
     ap.add_argument("--stage-profile", action="store_true", help="extra untimed pass with events around every stage")
     ap.add_argument("--no-lookahead", action="store_true",
                     help="ekf: CSLAM_LOOKAHEAD=0 -- every update runs its own gather / factor / gain chain (round 2's engine)")
@@ -108,7 +121,7 @@ def parse_args():
                          "state) as DIR/<name>.npy, float32 / float64, at most 64 MB in all: a covariance as its diagonal, "
                          "its pose columns and a fixed, seeded sample of its entries (all of them up to 2^21).  The inputs "
                          "depend on the arguments only, so two builds can be compared output for output (bench_outputs/ "
-                         "is git-ignored for this).  The timed steps are unaffected; the sub-records measured after them "
+                         "is git-ignored for this).  The timed steps are unaffected; the --full sub-records measured after them "
                          "follow the read-back, which leaves the GPU idle for a moment")
     return ap.parse_args()
 
@@ -410,11 +423,12 @@ def ekf_main(args):
     if conan_slam_amd.device_count() == 0:
         raise SystemExit("bench.py needs an MI355X: the engine has no CPU fallback")
 
-    extras = (world == 1 and not args.no_extras and not args.sequential)
+    extras = (args.full and world == 1 and not args.no_extras and not args.sequential)
     n_bracket, n_call, n_drop = (64, 64, 48) if extras else (0, 0, 0)
     pre_cap = 8000 if (args.warmup < 400 and args.preheat_ms > 0) else 0  # input slots for the preheat loop
     # short invocations (the driver's `--steps 20 --warmup 5`) are first run COLD -- W warm-up + K timed steps on a GPU
-    # that has just been handed to this process -- and reported as `cold_steps_per_sec`; then comes the preheat
+    # that has just been handed to this process -- and reported as `cold_steps_per_sec`; then comes the preheat.  (Both
+    # belong to a plain run as well: the filter state the timed steps start from, hence --dump-outputs, depends on them)
     n_cold = (args.warmup + args.steps) if (pre_cap and world == 1) else 0
     pre_cap += n_cold
     total = pre_cap + args.warmup + args.steps
@@ -471,7 +485,8 @@ def ekf_main(args):
     barrier()    #  and the K timed steps pay for all of their own, the final flush included)
     # HIP events around a sample of the P-GEMM launches of the timed region, on the stream they run on: one launch in 16
     # (an event pair costs ~11 us of stream time around the kernel it brackets; a short run -- the driver's 20 steps are
-    # ten launches -- keeps one in-region sample and is priced on the bracketed pass that follows, see `bracketed_pass`)
+    # ten launches -- keeps one in-region sample: a plain run prices its roofline on that one launch, event overhead
+    # included (`launches_timed` says how many); --full prices it on the bracketed pass that follows, see `bracketed_pass`)
     eng.set_profiling(3)
     barrier()
     t0 = time.perf_counter()
@@ -507,7 +522,7 @@ def ekf_main(args):
     t_next = total
     bracket = None
     if extras:
-        # every P-GEMM launch bracketed (untimed pass, the filter simply continues): median and spread
+        # --full: every P-GEMM launch bracketed (untimed pass, the filter simply continues): median and spread
         eng.set_profiling(2)
         for t in range(t_next, t_next + n_bracket):
             step(t)
@@ -519,8 +534,9 @@ def ekf_main(args):
         bracket = {"launch_us_mean": b_ms / max(b_cnt, 1) * 1e3, "launches": b_cnt}
         if dd_cnt < 16 and b_cnt >= 16:
             # a short timed region samples only a handful of launches (an event pair costs ~11 us of stream time, so
-            # not every launch of the timed region is bracketed): the roofline is then priced on the bracketed pass
-            # (every launch of 64 further steps), the in-region sample is kept beside it
+            # not every launch of the timed region is bracketed): with --full the roofline is then priced on the bracketed
+            # pass (every launch of 64 further steps), the in-region sample is kept beside it; a plain run has no such
+            # pass and keeps the in-region sample as its price
             bracket["timed_region_sample_us"] = dd_s * 1e6 if dd_s else None
             bracket["timed_region_sample_launches"] = dd_cnt
             dd_s, dd_cnt = (b_ms / b_cnt) * 1e-3, b_cnt
@@ -640,7 +656,7 @@ def ekf_main(args):
             out["reference_loop_ref_exact"] = reference_loop(args, torch, w, N, Q_REF_EXACT)
     if extras:
         out["ref_exact_healthy"] = ref_exact_healthy(args, torch, N, dtype)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         w.P0 = None
         out["cpu_baseline"] = cpu_baseline(N, args.obs, dtype, args.dtype, args.quirks, args.cpu_baseline_seconds)
         if out["cpu_baseline"]["value"]:
@@ -806,7 +822,7 @@ def mc_main(args):
         if args.defer > 0:
             e.set_deferred(args.defer)
         w.P0 = None
-        inp = DeviceInputs(torch, w, 2 * total)
+        inp = DeviceInputs(torch, w, 2 * total if args.full else total)  # (the second half feeds --full's single-instance run)
         engs.append(e)
         dZs.append(inp)
     w0 = Workload(N, m, dtype, seed=0, build_p=False)
@@ -861,14 +877,16 @@ def mc_main(args):
         if dist is not None:
             dist.destroy_process_group()
         return
-    # the same number of steps on ONE instance alone with the whole chip (the filter simply continues)
-    engs[0].set_pgemm_workgroups(0)
-    run([0], total, args.warmup)
-    sync([0])
-    t1 = time.perf_counter()
-    run([0], total + args.warmup, args.steps)
-    sync([0])
-    el1 = time.perf_counter() - t1
+    el1 = None
+    if args.full:
+        # the same number of steps on ONE instance alone with the whole chip (the filter simply continues)
+        engs[0].set_pgemm_workgroups(0)
+        run([0], total, args.warmup)
+        sync([0])
+        t1 = time.perf_counter()
+        run([0], total + args.warmup, args.steps)
+        sync([0])
+        el1 = time.perf_counter() - t1
     dd_ms = sum(d[0] for d in dd)
     dd_cnt = sum(d[1] for d in dd)
     dd_s = dd_ms / dd_cnt * 1e-3 if dd_cnt else None
@@ -883,18 +901,19 @@ def mc_main(args):
                    "deferred_columns": args.defer,
                    "parallelism": f"{I} instances/GPU x {world} GPU(s), no collective",
                    "baseline_config": "BASELINE.json configs[4]" if (N, I * max(world, 1)) == (2000, 64) or N == 2000 else "custom"},
-        "single_instance": {"value": args.steps / el1, "unit": "update steps/s", "ms_per_step": el1 / args.steps * 1e3,
-                            "note": "one of the instances run alone on the same GPU (same driver)"},
-        "concurrency_gain": (I * args.steps / elapsed) / (args.steps / el1) if world == 1 else None,
         "roofline": roofline_record(n, (2 * m) * max(1, args.defer // (2 * m)) if args.defer > 0 else 2 * m, args.dtype, storage,
                                     dd_s, dd_cnt, N,
                                     {"note": "P-GEMM launches of all instances (sampled 1 in 16), co-running with the "
                                              "other instances' kernels"}),
         "factor_flags": flags,
     }
+    if el1 is not None:
+        out["single_instance"] = {"value": args.steps / el1, "unit": "update steps/s", "ms_per_step": el1 / args.steps * 1e3,
+                                  "note": "one of the instances run alone on the same GPU (same driver)"}
+        out["concurrency_gain"] = (I * args.steps / elapsed) / (args.steps / el1) if world == 1 else None
     for e in engs:
         e.close()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(N, m, dtype, args.dtype, args.quirks, args.cpu_baseline_seconds)
         out["cpu_baseline"]["note"] = "one instance on one core; the reference would run the 64 instances one after another"
     print(json.dumps(out), flush=True)
@@ -904,7 +923,7 @@ def mc_main(args):
 
 def mc_batched(args, rank, local_rank, world, torch, dist, N, m, I, quirks):
     """configs[4] through the batched engine (cslam_ekf_batch_*): the I runs of a GPU advance in lockstep, every stage
-    one launch for all of them; then ONE run alone through a single handle for the concurrency gain."""
+    one launch for all of them; with --full then ONE run alone through a single handle for the concurrency gain."""
     import ctypes as C
 
     from conan_slam_amd import EKF, EKFBatch, _capi
@@ -923,7 +942,7 @@ def mc_batched(args, rank, local_rank, world, torch, dist, N, m, I, quirks):
     for i in range(I):
         w = Workload(N, m, dtype, seed=100 + rank * I + i)
         bs[i // per].set_state(i % per, w.X0, w.P0)
-        if i == 0:
+        if i == 0 and args.full:
             first = (w.X0.copy(), w.P0)
         w.P0 = None
         inps.append(DeviceInputs(torch, w, total))
@@ -972,31 +991,33 @@ def mc_batched(args, rank, local_rank, world, torch, dist, N, m, I, quirks):
         if dist is not None:
             dist.destroy_process_group()
         return
-    # one run alone with the whole chip, through a single handle (its best mode at this size: deferral window 128)
-    L = _capi.lib()
-    e = EKF(N, dtype=dtype, device=local_rank, quirks=quirks, sync_mode=False)
-    e.set_state(*first)
-    e.set_deferred(128 if 2 * m == 64 else 0)
-    vs = (C.c_double * (2 * total))(*v)
-    ss = (C.c_double * (2 * total))(*sw)
-    QE, RE = np.asfortranarray(w0.QE), np.asfortranarray(w0.RE)
+    el1 = None
+    if args.full:
+        # one run alone with the whole chip, through a single handle (its best mode at this size: deferral window 128)
+        L = _capi.lib()
+        e = EKF(N, dtype=dtype, device=local_rank, quirks=quirks, sync_mode=False)
+        e.set_state(*first)
+        e.set_deferred(128 if 2 * m == 64 else 0)
+        vs = (C.c_double * (2 * total))(*v)
+        ss = (C.c_double * (2 * total))(*sw)
+        QE, RE = np.asfortranarray(w0.QE), np.asfortranarray(w0.RE)
 
-    def run1(t0, count):
-        hs = (C.c_void_p * 1)(e._h)
-        zs = (C.c_void_p * 1)(inps[0].z(t0))
-        ids = (C.c_void_p * 1)(inps[0].i(t0))
-        _capi.check(L.cslam_ekf_run_many(hs, C.c_int(1), C.c_int(count), C.cast(C.byref(vs, t0 * 8), C.POINTER(C.c_double)),
-                                         C.cast(C.byref(ss, t0 * 8), C.POINTER(C.c_double)), QE.ctypes.data_as(C.c_void_p),
-                                         C.c_double(w0.wb), C.c_double(w0.dt), zs, ids, C.c_int(m),
-                                         RE.ctypes.data_as(C.c_void_p), C.c_int(1)))
-        e.flush()
-        e.synchronize()
+        def run1(t0, count):
+            hs = (C.c_void_p * 1)(e._h)
+            zs = (C.c_void_p * 1)(inps[0].z(t0))
+            ids = (C.c_void_p * 1)(inps[0].i(t0))
+            _capi.check(L.cslam_ekf_run_many(hs, C.c_int(1), C.c_int(count), C.cast(C.byref(vs, t0 * 8), C.POINTER(C.c_double)),
+                                             C.cast(C.byref(ss, t0 * 8), C.POINTER(C.c_double)), QE.ctypes.data_as(C.c_void_p),
+                                             C.c_double(w0.wb), C.c_double(w0.dt), zs, ids, C.c_int(m),
+                                             RE.ctypes.data_as(C.c_void_p), C.c_int(1)))
+            e.flush()
+            e.synchronize()
 
-    run1(0, W)
-    t1 = time.perf_counter()
-    run1(W, K)
-    el1 = time.perf_counter() - t1
-    e.close()
+        run1(0, W)
+        t1 = time.perf_counter()
+        run1(W, K)
+        el1 = time.perf_counter() - t1
+        e.close()
     k_launch = 4 * m  # two updates' panels per launch
     dd_s = dd_ms / dd_cnt * 1e-3 if dd_cnt else None
     rec = roofline_record(n, k_launch, "f32", "lower", dd_s / per if dd_s else None, dd_cnt, N,
@@ -1020,16 +1041,17 @@ def mc_batched(args, rank, local_rank, world, torch, dist, N, m, I, quirks):
                    "engine": "cslam_ekf_batch (look-ahead windows of two updates, one launch per stage for all instances)",
                    "parallelism": f"{I} instances/GPU x {world} GPU(s), no collective",
                    "baseline_config": "BASELINE.json configs[4]" if N == 2000 else "custom"},
-        "single_instance": {"value": K / el1, "unit": "update steps/s", "ms_per_step": el1 / K * 1e3,
-                            "note": "instance 0 run alone on the same GPU through a single handle (cslam_ekf_run_many, "
-                                    "deferral window 128)"},
-        "concurrency_gain": (I * K / elapsed) / (K / el1) if world == 1 else None,
         "roofline": rec,
         "factor_flags": flags,
     }
+    if el1 is not None:
+        out["single_instance"] = {"value": K / el1, "unit": "update steps/s", "ms_per_step": el1 / K * 1e3,
+                                  "note": "instance 0 run alone on the same GPU through a single handle (cslam_ekf_run_many, "
+                                          "deferral window 128)"}
+        out["concurrency_gain"] = (I * K / elapsed) / (K / el1) if world == 1 else None
     for b in bs:
         b.close()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(N, m, dtype, "f32", args.quirks, args.cpu_baseline_seconds)
         out["cpu_baseline"]["note"] = "one instance on one core; the reference would run the 64 instances one after another"
     print(json.dumps(out), flush=True)
@@ -1182,7 +1204,7 @@ def pf_main(args):
                                  "/ step time; the step is a latency chain of small kernels, not bandwidth-bound "
                                  "(DESIGN.md 5)"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = pf_cpu_baseline(Np, Nf, m, args.cpu_baseline_seconds)
             out["gpu_over_cpu_single_core"] = out["value"] / out["cpu_baseline"]["value"]
         print(json.dumps(out), flush=True)

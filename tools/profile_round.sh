@@ -35,13 +35,13 @@ python3 tools/trace_timeline.py $(find $O/stats_ekf_classic -name run_kernel_tra
 python3 tools/trace_timeline.py $(find $O/stats_f64 -name run_kernel_trace.csv | head -1) 0.6 24 > $O/timeline_f64.txt 2>&1 || true
 python3 tools/trace_timeline.py $(find $O/stats_mc -name run_kernel_trace.csv | head -1) 0.3 24 > $O/timeline_mc_batch.txt 2>&1 || true
 tools/probes/mfma_peak_probe > $O/mfma_peak.txt 2>&1 || true
-python3 bench.py > $O/bench_ekf.json 2> $O/bench.err
+python3 bench.py --full > $O/bench_ekf.json 2> $O/bench.err
 python3 bench.py --no-lookahead --no-cpu-baseline --no-extras > $O/bench_ekf_classic.json 2>> $O/bench.err || true
-python3 bench.py --dtype f64 --landmarks 1000 > $O/bench_f64_n1000.json 2>> $O/bench.err || true
-python3 bench.py --workload pf --force-resample > $O/bench_pf.json 2>> $O/bench.err || true
-python3 bench.py --workload mc > $O/bench_mc.json 2>> $O/bench.err || true
-python3 bench.py --workload mc --mc-engine handles --no-cpu-baseline > $O/bench_mc_handles.json 2>> $O/bench.err || true
+python3 bench.py --full --dtype f64 --landmarks 1000 > $O/bench_f64_n1000.json 2>> $O/bench.err || true
+python3 bench.py --full --workload pf --force-resample > $O/bench_pf.json 2>> $O/bench.err || true
+python3 bench.py --full --workload mc > $O/bench_mc.json 2>> $O/bench.err || true
+python3 bench.py --full --workload mc --mc-engine handles --no-cpu-baseline > $O/bench_mc_handles.json 2>> $O/bench.err || true
 python3 bench.py --sequential --obs 8 --no-cpu-baseline --no-extras > $O/bench_sequential.json 2>> $O/bench.err || true
-python3 bench.py --steps 20 --warmup 5 > $O/bench_driver_shape.json 2>> $O/bench.err || true
+python3 bench.py --full --steps 20 --warmup 5 > $O/bench_driver_shape.json 2>> $O/bench.err || true
 for f in bench_ekf bench_ekf_classic bench_f64_n1000 bench_pf bench_mc bench_mc_handles bench_sequential bench_driver_shape; do python3 -c "
 import json;d=json.loads(open('$O/$f.json').read().strip().split('\n')[-1]);print('$f', round(d['value']), round(d['ms_per_step'],5), (d.get('roofline') or {}).get('frac'))" || true; done
