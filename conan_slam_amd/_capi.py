@@ -133,6 +133,22 @@ PF_SCORE_SYMBOLS = ("cslam_pf_score_reset", "cslam_pf_score_set_truth", "cslam_p
                     "cslam_pf_get_scores")
 
 
+# The single EKF handle's pose read and its score and trajectory log kept on the device (test/main.cpp:136,
+# EKF.cpp:131-144): the totals use the SCORE_* indices above; a series record is 4 floats, a track record 5 doubles
+# (X[0], X[1], X[2], trace(P), n).
+EKF_SCORE_SERIES, EKF_SCORE_TRACK = 4, 5
+_PROTOTYPES.update({
+    "cslam_ekf_get_pose": [C.c_void_p, C.c_void_p, C.c_void_p],
+    "cslam_ekf_score_reset": [C.c_void_p, C.c_int, C.c_double, C.c_double],
+    "cslam_ekf_score_set_truth": [C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_ekf_score": [C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_ekf_get_scores": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                             C.POINTER(C.c_longlong)],
+})
+EKF_SCORE_SYMBOLS = ("cslam_ekf_get_pose", "cslam_ekf_score_reset", "cslam_ekf_score_set_truth", "cslam_ekf_score",
+                     "cslam_ekf_get_scores")
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
     text = open(header_path).read()

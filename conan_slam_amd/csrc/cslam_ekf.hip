@@ -36,8 +36,11 @@
 #include "ekf_pgemm_limbs.hpp"
 #include "ekf_pgemm_tiles.hpp"
 #include "ekf_pose_kernels.hpp"
+#define CSLAM_SCORE_SINGLE_ONLY // (the batch score kernels belong to cslam_ekf_batch.hip)
+#include "ekf_score_kernels.hpp"
 #include "ekf_staging.hpp"
 #include "host_linalg.hpp"
+#include "pf_host_parts.hpp"
 
 namespace cslam
 {
@@ -153,6 +156,13 @@ struct EkfBase
     virtual int get_x(void* X, int cap)                                                        = 0;
     virtual int get_landmarks(int first, int count, void* x, void* pll, void* pvl)             = 0;
     virtual int trace(double* tr)                                                              = 0;
+    virtual int get_pose(void* x, void* pvv)                                                   = 0;
+    // the score kept on the device (ekf_score_kernels.hpp)
+    virtual int score_reset(int series_capacity, double gate_pose, double gate_lm)             = 0;
+    virtual int score_set_truth(const double* lm_true, int count)                              = 0;
+    virtual int score(const double* xv_true, int with_map)                                     = 0;
+    virtual int get_scores(double* totals, float* series, double* track, int capacity_records, int* records,
+                           long long* calls)                                                   = 0;
     virtual int predict(double v, double swa, const void* Q, double wb, double dt)             = 0;
     virtual int update(const void* Z, int m, const void* R, const int* idf, int batch, bool on_device) = 0;
     virtual int augment(const void* Z, int q, const void* R)                                   = 0;
@@ -754,6 +764,180 @@ struct Ekf : EkfBase
             s += (double)d;
         }
         *tr = s;
+        return CSLAM_OK;
+    }
+
+    // The pose X[0:3] and the 3 x 3 pose block (arguments checked by cslam_ekf_get_pose, queued work launched by
+    // resolve_predict).  Both are exact as they stand: the pending panels hold zeros in rows 0..2 and the block lives in
+    // the stripe, P[r, c] = Pv[c ldp + r].  No flush, no P-GEMM, no copy of P: 12 scalars.
+    int get_pose(void* x, void* pvv) override
+    {
+        int rc = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        CSLAM_HIP_TRY(hipMemcpyAsync(x, dX.get(), 3 * sizeof(T), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipMemcpy2DAsync(pvv, 3 * sizeof(T), dPv.get(), (size_t)ldp * sizeof(T), 3 * sizeof(T), (size_t)3,
+                                       hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+
+    // ---------------------------------------------------------------- the score, kept on the device
+    // (ekf_score_kernels.hpp: ekf_score_landmarks / ekf_score_finish).  Two levels, each all-or-nothing, as the particle
+    // handle's: the base (totals, the landmark kernel's slots and the truth rows, sized for max_landmarks once, by the
+    // first score call or score_reset) and the log (series and track, sized by the largest series_capacity a reset has
+    // asked for).  A handle that never scores allocates neither; set_state leaves both alone.  The book is the particle
+    // handle's (pf_host_parts.hpp) with the estimator left at 0: the same argument rules, gate defaults and record count.
+    struct ScoreBufs
+    {
+        struct Base
+        {
+            DevBuf<double> totals; // [CSLAM_SCORE_FIELDS]
+            DevBuf<double> parts;  // [blocks(max_landmarks)][kScorePartsSingle]
+            DevBuf<double> truth;  // [max_landmarks][2]
+        };
+        struct Log
+        {
+            DevBuf<float>  series; // [capacity][4]
+            DevBuf<double> track;  // [capacity][kScoreTrack]
+        };
+        Base        base;
+        Log         log;
+        PfScoreBook book;
+        bool        allocated() const { return (bool)base.totals; }
+    };
+    ScoreBufs sc;
+
+    int ensure_score()
+    {
+        if (sc.allocated())
+        {
+            return CSLAM_OK;
+        }
+        const size_t             cf = (size_t)std::max(nmax, 1);
+        typename ScoreBufs::Base b;
+        CSLAM_TRY(b.totals.alloc_zeroed((size_t)CSLAM_SCORE_FIELDS, stream));
+        CSLAM_TRY(b.parts.alloc((size_t)PfScoreBook::blocks((int)cf) * kScorePartsSingle));
+        CSLAM_TRY(b.truth.alloc(2 * cf));
+        sc.base = std::move(b);
+        return CSLAM_OK;
+    }
+
+    int score_reset(int series_capacity, double gate_pose, double gate_lm) override
+    {
+        if (!PfScoreBook::reset_args_ok(0, series_capacity))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "ekf_score_reset: series_capacity %d (>= 0)", series_capacity);
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(ensure_score());
+        if (!PfScoreBook::series_fits(sc.log.series.count() / 4, series_capacity))
+        {
+            typename ScoreBufs::Log l;
+            CSLAM_TRY(l.series.alloc((size_t)series_capacity * 4));
+            CSLAM_TRY(l.track.alloc((size_t)series_capacity * kScoreTrack));
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still writes the old log
+            sc.log = std::move(l);
+        }
+        CSLAM_HIP_TRY(hipMemsetAsync(sc.base.totals.get(), 0, CSLAM_SCORE_FIELDS * sizeof(double), stream));
+        if (sc.log.series)
+        {
+            CSLAM_HIP_TRY(hipMemsetAsync(sc.log.series.get(), 0, sc.log.series.count() * sizeof(float), stream));
+            CSLAM_HIP_TRY(hipMemsetAsync(sc.log.track.get(), 0, sc.log.track.count() * sizeof(double), stream));
+        }
+        sc.book.reset(0, series_capacity, gate_pose, gate_lm);
+        return CSLAM_OK;
+    }
+
+    int score_set_truth(const double* lm_true, int count) override
+    {
+        if (!PfScoreBook::truth_args_ok(count, nmax) || (count > 0 && !lm_true))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "ekf_score_set_truth: count %d outside 0..max_landmarks=%d, or null rows", count, nmax);
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(ensure_score());
+        if (count > 0)
+        {
+            // (behind whatever score call still reads the old rows; the host array is consumed before the return)
+            CSLAM_HIP_TRY(hipMemcpyAsync(sc.base.truth.get(), lm_true, (size_t)2 * count * sizeof(double),
+                                         hipMemcpyHostToDevice, stream));
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        }
+        sc.book.set_truth_count(count);
+        return CSLAM_OK;
+    }
+
+    // One score step (xv_true checked by cslam_ekf_score, queued work launched by resolve_predict).  What get_landmarks
+    // does before its kernel, then the two kernels on the main stream: no flush, no synchronise, no copy, and after the
+    // first call no allocation.  The pending columns stay pending, so the run continues bit for bit as without the call.
+    int score(const double* xv_true, int with_map) override
+    {
+        int rc = use_device();
+        if (rc || (rc = ensure_score()) || (rc = wait_pgemm()))
+        {
+            return rc;
+        }
+        const PfScoreBook& bk     = sc.book;
+        const int          nl     = (n - 3) / 2;
+        const int          blocks = with_map ? PfScoreBook::blocks(nl) : 0;
+        if (blocks > 0)
+        {
+            const int* sg = (pend.kp > 0 && pend.hd_cols[pend.wcur] > 0) ? signs(pend.wcur) : (const int*)nullptr;
+            hipLaunchKernelGGL(ekf_score_landmarks<T>, dim3(blocks), dim3(256), 0, stream, (const T*)dX.get(),
+                               (const T*)dPv.get(), (const T*)dP.get(), ldp, opt.lower, (const T*)wbase(pend.wcur), pend.kp, sg,
+                               nl, bk.scored(nl, 1), (const double*)sc.base.truth.get(), bk.gate_lm(), sc.base.parts.get());
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(ekf_score_finish<T>, dim3(1), dim3(64), 0, stream, (const T*)dX.get(), (const T*)dPv.get(), ldp, n,
+                           (const double*)sc.base.parts.get(), blocks, with_map ? 1 : 0, xv_true[0], xv_true[1], xv_true[2],
+                           bk.gate_pose(), sc.base.totals.get(), sc.log.series.get(), sc.log.track.get(), bk.next_record());
+        CSLAM_HIP_TRY(hipGetLastError());
+        sc.book.called();
+        return CSLAM_OK;
+    }
+
+    // The one synchronising call of the score: copies on the main stream and waits for it.  Nothing is flushed and
+    // nothing queued is launched (a held predict, the pose queue and a queued look-ahead update stay as they are), so
+    // the rest of the run does not depend on where the scores are read.
+    int get_scores(double* totals, float* series, double* track, int capacity_records, int* records, long long* calls) override
+    {
+        if (capacity_records < 0)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "ekf_get_scores: capacity_records %d", capacity_records);
+        }
+        CSLAM_TRY(use_device());
+        const PfScoreBook& bk = sc.book;
+        const size_t       c  = (size_t)bk.records_to_copy(capacity_records);
+        if (totals && !sc.allocated())
+        {
+            std::fill(totals, totals + CSLAM_SCORE_FIELDS, 0.0);
+        }
+        else if (totals)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(totals, sc.base.totals.get(), CSLAM_SCORE_FIELDS * sizeof(double),
+                                         hipMemcpyDeviceToHost, stream));
+        }
+        if (series && c > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(series, sc.log.series.get(), c * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        }
+        if (track && c > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(track, sc.log.track.get(), c * kScoreTrack * sizeof(double), hipMemcpyDeviceToHost,
+                                         stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        if (records)
+        {
+            *records = bk.records();
+        }
+        if (calls)
+        {
+            *calls = bk.calls();
+        }
         return CSLAM_OK;
     }
 
@@ -2754,6 +2938,67 @@ int cslam_ekf_get_landmarks(cslam_ekf_t h, int first, int count, void* x, void* 
         return rc;
     }
     return B(h)->get_landmarks(first, count, x, pll, pvl);
+}
+
+// The entry points of the pose read and the score answer a null handle as cslam_ekf_create answers its caller: without a
+// usable GPU there is no handle to pass, and the status says so (CSLAM_ERR_NO_DEVICE); with one, a null handle is a bad
+// argument.
+#define CSLAM_NEED_OR_NO_DEVICE(h)                                                                              \
+    if (!(h))                                                                                                   \
+    {                                                                                                           \
+        int c__ = 0;                                                                                            \
+        if (hipGetDeviceCount(&c__) != hipSuccess || c__ == 0)                                                  \
+        {                                                                                                       \
+            return fail(CSLAM_ERR_NO_DEVICE, "%s: no HIP device (this engine has no CPU fallback)", __func__);  \
+        }                                                                                                       \
+        return fail(CSLAM_ERR_BAD_ARG, "%s: null handle", __func__);                                            \
+    }
+
+int cslam_ekf_get_pose(cslam_ekf_t h, void* x, void* pvv)
+{
+    CSLAM_NEED_OR_NO_DEVICE(h);
+    if (!x || !pvv)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "get_pose: null output");
+    }
+    if (int rc = B(h)->resolve_predict()) // (as get_landmarks)
+    {
+        return rc;
+    }
+    return B(h)->get_pose(x, pvv);
+}
+
+int cslam_ekf_score_reset(cslam_ekf_t h, int series_capacity, double gate_pose, double gate_lm)
+{
+    CSLAM_NEED_OR_NO_DEVICE(h);
+    return B(h)->score_reset(series_capacity, gate_pose, gate_lm);
+}
+
+int cslam_ekf_score_set_truth(cslam_ekf_t h, const double* lm_true, int count)
+{
+    CSLAM_NEED_OR_NO_DEVICE(h);
+    return B(h)->score_set_truth(lm_true, count);
+}
+
+int cslam_ekf_score(cslam_ekf_t h, const double* xv_true, int with_map)
+{
+    CSLAM_NEED_OR_NO_DEVICE(h);
+    if (!xv_true || !std::isfinite(xv_true[0]) || !std::isfinite(xv_true[1]) || !std::isfinite(xv_true[2]))
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "ekf_score: xv_true is null or not finite");
+    }
+    if (int rc = B(h)->resolve_predict()) // (as get_landmarks: the held predict, the pose queue, a queued look-ahead update)
+    {
+        return rc;
+    }
+    return B(h)->score(xv_true, with_map);
+}
+
+int cslam_ekf_get_scores(cslam_ekf_t h, double* totals, float* series, double* track, int capacity_records, int* records,
+                         long long* calls)
+{
+    CSLAM_NEED_OR_NO_DEVICE(h);
+    return B(h)->get_scores(totals, series, track, capacity_records, records, calls);
 }
 
 int cslam_ekf_get_n(cslam_ekf_t h, int* n)

@@ -163,10 +163,53 @@ class EKF:
         # (column-major blocks per landmark)
         return x, pll.reshape(count, 2, 2).transpose(0, 2, 1).copy(), pvl.reshape(count, 2, 3).transpose(0, 2, 1).copy()
 
+    def pose(self):
+        """(x [3], pvv [3, 3]): the pose and the 3 x 3 pose block after launching what is queued, read from the pose
+        stripe without the covariance downdate or a copy of P (cslam_ekf_get_pose).  Synchronises."""
+        x = np.empty(3, dtype=self.dtype)
+        pv = np.empty(9, dtype=self.dtype)
+        check(self._L.cslam_ekf_get_pose(self._h, _vp(x), _vp(pv)))
+        return x, pv.reshape(3, 3).T.copy()  # (column-major)
+
     def factor_status(self, clear: bool = False) -> int:
         f = C.c_int(0)
         check(self._L.cslam_ekf_factor_status(self._h, C.byref(f), C.c_int(1 if clear else 0)))
         return f.value
+
+    # ------------------------------------------------------------------ the score, kept on the device
+    def score_reset(self, series_capacity: int = 0, gate_pose: float = 0.0, gate_lm: float = 0.0):
+        """Zero the totals, the series and the track (room for `series_capacity` records, one per score call) and the call
+        count.  A gate <= 0 is the 95 % chi-square point (7.8147 for the pose, 5.9915 for a landmark).  Keeps the truth."""
+        check(self._L.cslam_ekf_score_reset(self._h, C.c_int(int(series_capacity)), C.c_double(float(gate_pose)),
+                                            C.c_double(float(gate_lm))))
+
+    def score_set_truth(self, lm_true):
+        """Row j of lm_true ([count, 2]) is the true position of state feature j + 1.  Features beyond count are not scored."""
+        t = np.ascontiguousarray(np.asarray(lm_true, dtype=np.float64).reshape(-1, 2))
+        check(self._L.cslam_ekf_score_set_truth(self._h, _vp(t) if t.size else None, C.c_int(t.shape[0])))
+
+    def score(self, xv_true, with_map: bool = True):
+        """One score step against the true pose (x, y, phi): pose error and NEES, map error and landmark NEES enter the
+        totals on the device, and the call's series and track records are written.  Launches what is queued as landmarks()
+        does; does not synchronise, copies nothing back and leaves the run bit for bit as without the call
+        (cslam_ekf_score)."""
+        x = np.ascontiguousarray(np.asarray(xv_true, dtype=np.float64).reshape(3))
+        check(self._L.cslam_ekf_score(self._h, _vp(x), C.c_int(1 if with_map else 0)))
+
+    def scores(self, capacity_records: int = None):
+        """-> (totals [SCORE_FIELDS] float64, series [records, 4] float32, track [records, 5] float64, calls): the one
+        synchronising call of the score (cslam_ekf_get_scores).  The fields of totals are _capi.SCORE_FIELD_NAMES; a
+        series record holds pose err^2, pose NEES, mean landmark err^2 and mean landmark NEES of one call (NaN where there
+        is none), a track record X[0], X[1], X[2], trace(P) and n."""
+        rec, calls = C.c_int(0), C.c_longlong(0)
+        check(self._L.cslam_ekf_get_scores(self._h, None, None, None, C.c_int(0), C.byref(rec), C.byref(calls)))
+        n = rec.value if capacity_records is None else min(rec.value, int(capacity_records))
+        totals = np.zeros(_capi.SCORE_FIELDS, np.float64)
+        series = np.zeros((n, _capi.EKF_SCORE_SERIES), np.float32)
+        track = np.zeros((n, _capi.EKF_SCORE_TRACK), np.float64)
+        check(self._L.cslam_ekf_get_scores(self._h, _vp(totals), _vp(series) if n else None, _vp(track) if n else None,
+                                           C.c_int(n), C.byref(rec), C.byref(calls)))
+        return totals, series, track, int(calls.value)
 
     # ------------------------------------------------------------------ the hot path
     def predict(self, v, swa, Q, wb, dt):

@@ -111,6 +111,12 @@ int cslam_ekf_get_n(cslam_ekf_t h, int* n);
  * returns CSLAM_OK at once; a bad range returns CSLAM_ERR_BAD_ARG and changes nothing.  Synchronises. */
 int cslam_ekf_get_landmarks(cslam_ekf_t h, int first, int count, void* x, void* pll, void* pvl);
 int cslam_ekf_trace(cslam_ekf_t h, double* trace);                 /* synchronises */
+/* The pose X[0:3] and the full 3 x 3 pose block P[0:3, 0:3] (column-major), in the handle's dtype: the single-handle
+ * sibling of cslam_ekf_batch_get_poses (the pose test/main.cpp:136 prints; the block EKF.cpp:131-144 reads through
+ * H*P*H^T; what Slam::predict, slam.h:841-847, propagates).  Queued work is launched first exactly as get_landmarks does;
+ * the block is read from the pose stripe, which is always current: no covariance downdate, no P-GEMM, no copy of P, and
+ * the run continues bit for bit as without the read.  Both outputs are required (NULL: CSLAM_ERR_BAD_ARG).  Synchronises. */
+int cslam_ekf_get_pose(cslam_ekf_t h, void* x /* [3] */, void* pvv /* [9] */);            /* synchronises; no flush */
 int cslam_ekf_synchronize(cslam_ekf_t h);
 int cslam_ekf_factor_status(cslam_ekf_t h, int* flags, int clear); /* synchronises */
 
@@ -285,8 +291,8 @@ int cslam_ekf_batch_get_landmarks(cslam_ekf_batch_t h, int first, int count, flo
  *      observation step -- the pose test/main.cpp:136 prints against the true pose, and the blocks EKF.cpp:131-144 reads
  *      against a true position per state feature.  All error and NEES arithmetic is f64 on the device from the f32
  *      state; the sums are formed in a fixed order without atomics, so the totals of a run are reproducible bit for
- *      bit.  f32 batch only: the single handle and the f64 engine have no scorer; the particle filter has its own,
- *      cslam_pf_score* below, with the same rules and the same total indices.
+ *      bit.  The single handle (f32 and f64) has the same scorer, cslam_ekf_score* below, and the particle filter its
+ *      own, cslam_pf_score* further down: the same rules and the same total indices.
  * Indices into one instance's totals (doubles): */
 enum { CSLAM_SCORE_POSE_N, CSLAM_SCORE_POSE_BAD, CSLAM_SCORE_POSE_IN, CSLAM_SCORE_POSE_ERR2 /* sum ex^2+ey^2 */,
        CSLAM_SCORE_POSE_EPHI2 /* sum wrapped heading error^2 */, CSLAM_SCORE_POSE_NEES /* sum e^T Pvv^-1 e */,
@@ -322,6 +328,50 @@ int cslam_ekf_batch_score(cslam_ekf_batch_t h, const float* xv_true /* host [3] 
  * series capacity still enter the totals).  Any output pointer may be NULL. */
 int cslam_ekf_batch_get_scores(cslam_ekf_batch_t h, double* totals /* [I][CSLAM_SCORE_FIELDS] */,
                                float* series /* [records][I][4] */, int capacity_records, int* records, long long* calls);
+
+/* ---- the same score for the single handle, f32 and f64 (ekf_score_landmarks / ekf_score_finish in
+ *      conan_slam_amd/csrc/ekf_score_kernels.hpp), with a trajectory log.  A consistency study of one filter otherwise
+ *      reads cslam_ekf_get_landmarks and cslam_ekf_get_pose after every step (a synchronise each) or cslam_ekf_trace /
+ *      cslam_ekf_get_state (which apply the pending columns early and so change the rounding of every later step).  These
+ *      calls read X, the pose stripe and the deferred form P = Ps - Wp diag(s) Wp^T as they stand -- the sign words of
+ *      heading columns stored with S < 0 included -- and never write the filter's state.  The rules, the gates, the f64
+ *      arithmetic, the fixed summation order and the CSLAM_SCORE_* indices are those of cslam_ekf_batch_score with one
+ *      instance; the truth rows and the true pose are doubles for both dtypes, as for cslam_pf_score. */
+/* Zeroes the totals, the series, the track and the call count (scoring state a study keeps on the host beside
+ * test/main.cpp:136; the blocks of EKF.cpp:131-144; per step of slam.h:841-847).  series_capacity >= 0 records of 4
+ * floats and 5 doubles (0: totals only).  A gate <= 0 selects the 95 % chi-square point: 7.8147 for the pose, 5.9915 for a
+ * landmark.  The truth rows are kept.  A score call without a prior reset behaves as after score_reset(h, 0, 0, 0).  A
+ * negative capacity: CSLAM_ERR_BAD_ARG, nothing changed.  A handle that never calls a score function allocates nothing
+ * for it; cslam_ekf_set_state leaves the score state alone. */
+int cslam_ekf_score_reset(cslam_ekf_t h, int series_capacity, double gate_pose, double gate_lm);
+/* The true position of state feature j + 1 is row j of lm_true (host [count][2] doubles; the features of
+ * EKF.cpp:131-144, scored beside the pose of test/main.cpp:136 after a step of slam.h:841-847), copied into a device
+ * buffer sized for max_landmarks before the call returns.  Features beyond `count` are not scored.  count < 0 or
+ * count > max_landmarks: CSLAM_ERR_BAD_ARG, nothing changed. */
+int cslam_ekf_score_set_truth(cslam_ekf_t h, const double* lm_true /* host [count][2] */, int count);
+/* One score step against the true pose xv_true (host [3], finite; it travels as kernel arguments; the pose of
+ * test/main.cpp:136, the blocks of EKF.cpp:131-144, after the step of slam.h:841-847).  Launches what is queued exactly as
+ * cslam_ekf_get_landmarks does -- a held predict, the pose queue, a queued look-ahead update as a window of one; a call
+ * at a window boundary finds nothing queued -- waits on the stream (not the host) for a P-GEMM in flight, then queues the
+ * two score kernels on the main stream and returns: no covariance downdate, no synchronise, no copy, and after the first
+ * call no allocation.  The run continues bit for bit as without the call.
+ *   totals    the pose and c = min(N, truth count) landmarks, by the pose, landmark and series rules written at
+ *             cslam_ekf_batch_score above.  with_map == 0: the landmark kernel is not launched, the landmark totals are
+ *             untouched and series fields 2 and 3 are NaN.
+ *   track     while there is room, one record of 5 doubles per call: X[0], X[1], X[2] widened bit for bit, trace(P) --
+ *             the pose diagonal from the stripe plus p00 + p11 of EVERY landmark of the state from the deferred form,
+ *             summed in f64 in a fixed order; NaN when with_map == 0 -- and n.
+ * A NULL or non-finite xv_true: CSLAM_ERR_BAD_ARG, nothing changed. */
+int cslam_ekf_score(cslam_ekf_t h, const double* xv_true /* host [3] */, int with_map);
+/* The one synchronising call of the score: copies the totals [CSLAM_SCORE_FIELDS], up to capacity_records series records
+ * [records][4] and track records [records][5] on the main stream and waits for it (the read-out that replaces a get_pose
+ * / get_landmarks pair per step: test/main.cpp:136, EKF.cpp:131-144, slam.h:841-847).  It applies no pending column and
+ * launches nothing that is queued -- a held predict and a queued look-ahead update stay queued -- so the rest of the run
+ * does not depend on where the scores are read.  *records = min(calls, series_capacity) is the number of records held (at
+ * most capacity_records of them are copied), *calls counts every score call since the reset.  Any output pointer may be
+ * NULL; a negative capacity_records: CSLAM_ERR_BAD_ARG. */
+int cslam_ekf_get_scores(cslam_ekf_t h, double* totals /* [CSLAM_SCORE_FIELDS] */, float* series /* [records][4] */,
+                         double* track /* [records][5] */, int capacity_records, int* records, long long* calls);
 /* Slam::observeHeading (slam.h:788, EKF.cpp:328-352, josephUpdate slam.h:700-725) on every instance.  phi is common,
  * as in the reference driver, which observes the true heading.  Deliberate difference from the single handle: an
  * instance whose S = P22 + R is <= 0 or non-finite (an indefinite P; a healthy filter never has one) skips the heading

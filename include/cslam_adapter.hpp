@@ -14,6 +14,9 @@
 //   HipEKF::augment          slam.h:190-191   EKF.cpp:9-26           -> cslam_ekf_augment  (addOneNewFeature too)
 //   HipEKF::observeHeading   slam.h:788       EKF.cpp:328-352        -> cslam_ekf_observe_heading
 //   HipEKF::dataAssociate    slam.h:482-487   EKF.cpp:235-326        -> cslam_ekf_associate
+//   HipEKF::pose / scoreReset / scoreTruth / score / scores   (the pose test/main.cpp:136 prints and the blocks
+//                            EKF.cpp:131-144 reads, scored and logged on the device)
+//                                                                    -> cslam_ekf_get_pose / _score_reset / _score_set_truth / _score / _get_scores
 //   HipPF::resampleParticles slam.h:871-872   PF.cpp:473-500         -> cslam_pf_resample_local / _sharded
 //   HipPF (particle-set forms of) predict / observeHeading / sampleProposal / featureUpdate / addOneNewFeature
 //                            slam.h:858-863, 796, 881-884, 549-552, 134; PF.cpp:419-471, 382-417, 502-544, 222-277, 9-60
@@ -158,6 +161,70 @@ class HipEKF : public EKF
             }
         }
         return out;
+    }
+
+    /// the pose and its 3 x 3 covariance block without touching P (no downdate, no copy of P): what a host scorer reads
+    /// beside the line test/main.cpp:136 prints
+    void pose(Eigen::VectorXf& x, Eigen::MatrixXf& Pvv)
+    {
+        x.resize(3);
+        Pvv.resize(3, 3);
+        float pv[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        report(cslam_ekf_get_pose(h_, x.data(), pv), "HipEKF::pose");
+        for (int c = 0; c < 3; c++)
+        {
+            for (int r = 0; r < 3; r++)
+            {
+                Pvv(r, c) = pv[3 * c + r];
+            }
+        }
+    }
+
+    // ---- the score of the filter and its trajectory log, kept on the device: a consistency study scores the pose
+    //      test/main.cpp:136 prints and the blocks EKF.cpp:131-144 reads after every step without reading them back
+    void scoreReset(int seriesCapacity = 0, double gatePose = 0.0, double gateLm = 0.0)
+    {
+        report(cslam_ekf_score_reset(h_, seriesCapacity, gatePose, gateLm), "HipEKF::scoreReset");
+    }
+    /// lmTrue: 2 x count, column j the true position of state feature j + 1 (the layout of the reference's landmarks)
+    void scoreTruth(const Eigen::MatrixXf& lmTrue)
+    {
+        const int           count = static_cast<int>(lmTrue.cols());
+        std::vector<double> rows(static_cast<size_t>(2 * (count > 0 ? count : 1)));
+        for (int j = 0; j < count; j++)
+        {
+            rows[static_cast<size_t>(2 * j)]     = static_cast<double>(lmTrue(0, j));
+            rows[static_cast<size_t>(2 * j + 1)] = static_cast<double>(lmTrue(1, j));
+        }
+        report(cslam_ekf_score_set_truth(h_, rows.data(), count), "HipEKF::scoreTruth");
+    }
+    /// one score step against the true pose (3); asynchronous, nothing returns.  (The engine's X and P are scored: a
+    /// caller that edited its own copies calls invalidate() and makes a hot-path call first.)
+    void score(const Eigen::VectorXf& xvTrue, bool withMap = true)
+    {
+        const double x[3] = {static_cast<double>(xvTrue(0)), static_cast<double>(xvTrue(1)), static_cast<double>(xvTrue(2))};
+        report(cslam_ekf_score(h_, x, withMap ? 1 : 0), "HipEKF::score");
+    }
+    /// the one synchronising read: totals [CSLAM_SCORE_FIELDS]; series (4 floats) and track (5 doubles: x, y, phi,
+    /// trace(P), n) per record held; returns the number of score calls since the reset
+    long long scores(std::vector<double>& totals, std::vector<float>* series = nullptr, std::vector<double>* track = nullptr)
+    {
+        int       records = 0;
+        long long calls   = 0;
+        totals.assign(static_cast<size_t>(CSLAM_SCORE_FIELDS), 0.0);
+        report(cslam_ekf_get_scores(h_, nullptr, nullptr, nullptr, 0, &records, &calls), "HipEKF::scores");
+        if (series)
+        {
+            series->assign(static_cast<size_t>(4 * records), 0.f);
+        }
+        if (track)
+        {
+            track->assign(static_cast<size_t>(5 * records), 0.0);
+        }
+        report(cslam_ekf_get_scores(h_, totals.data(), series && records ? series->data() : nullptr,
+                                    track && records ? track->data() : nullptr, records, &records, &calls),
+               "HipEKF::scores");
+        return calls;
     }
 
   private:
