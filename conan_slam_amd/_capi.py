@@ -149,6 +149,17 @@ EKF_SCORE_SYMBOLS = ("cslam_ekf_get_pose", "cslam_ekf_score_reset", "cslam_ekf_s
                      "cslam_ekf_get_scores")
 
 
+# The single EKF handle's data association read from the deferred covariance (EKF.cpp:131-144, 235-326, slam.h:482-487):
+# host answer plus the reference's split left on the device.
+_PROTOTYPES.update({
+    "cslam_ekf_associate_deferred": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                     C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "cslam_ekf_association_device_ptrs": [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.POINTER(C.c_void_p)],
+})
+EKF_ASSOC_DEFERRED_SYMBOLS = ("cslam_ekf_associate_deferred", "cslam_ekf_association_device_ptrs")
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
     text = open(header_path).read()

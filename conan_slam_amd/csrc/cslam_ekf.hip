@@ -29,6 +29,7 @@
 #include "device_owners.hpp"
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
+#include "ekf_assoc_deferred_kernels.hpp"
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_options.hpp"
@@ -168,6 +169,10 @@ struct EkfBase
     virtual int augment(const void* Z, int q, const void* R)                                   = 0;
     virtual int observe_heading(double phi, int use)                                           = 0;
     virtual int associate(const void* Z, int m, const void* R, double g1, double g2, int* idf_out, int* kind) = 0;
+    virtual int associate_deferred(const void* Z, int m, const void* R, double g1, double g2, int* idf_out, int* kind,
+                                   int* counts)                                                = 0;
+    virtual int association_device_ptrs(const void** dZF, const int** d_idf, const void** dZN,
+                                        const int** d_counts)                                  = 0;
     virtual int factor_status(int* flags, int clear)                                           = 0;
     virtual int set_profiling(int on)                                                          = 0;
     virtual int get_stage_times(double* ms, int* launches)                                     = 0;
@@ -1030,6 +1035,113 @@ struct Ekf : EkfBase
         CSLAM_HIP_TRY(hipMemcpyAsync(kind_out, dAssocOut.get() + m, (size_t)m * sizeof(int), hipMemcpyDeviceToHost,
                                      stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+
+    // The same answer read from the deferred form P = Ps - Wp diag(s) Wp^T as it stands (ekf_assoc_deferred_kernels.hpp):
+    // no flush, so pend.kp, the pending region, the sign words and P are what they were (arguments checked by
+    // cslam_ekf_associate_deferred, queued work launched by resolve_predict).  Two-stream mode: ordered behind the P-GEMMs
+    // in flight, as get_landmarks is.  One buffer set, replaced as a whole when m or the workgroup count outgrows it:
+    //   dAdT  Z (2 M) | ZF (2 M) | ZN (2 M) | pnd (M G) | pnis (M G)
+    //   dAdI  counts (4) | idf (M) | kind (M) | idf_f (M) | pj (M G)     -- of which counts | idf[m] | kind[m] are written
+    //         contiguously for the m of the call, so that ONE copy into the pinned hAd brings the host results back
+    DevBuf<T>      dAdT;
+    DevBuf<int>    dAdI;
+    PinnedBuf<int> hAd;  // counts (4) | idf (M) | kind (M)
+    PinnedBuf<T>   hAdZ; // staging of Z (2 M)
+    int            ad_mcap = 0, ad_gcap = 0;
+    bool           ad_valid = false; // the device lists hold the split of a call
+    int associate_deferred(const void* Zv, int m, const void* Rv, double g1, double g2, int* idf_out, int* kind_out,
+                           int* counts_out) override
+    {
+        int rc = use_device();
+        if (rc || (rc = wait_pgemm()))
+        {
+            return rc;
+        }
+        const int nf = (n - 3) / 2;
+        const int G  = (nf + 255) / 256;
+        if (m > ad_mcap || G > ad_gcap)
+        {
+            const int    M = std::max(m, ad_mcap), Gc = std::max(std::max(G, ad_gcap), 1);
+            const size_t mg = (size_t)M * Gc;
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // (nothing reads the old lists any more)
+            DevBuf<T>      t;
+            DevBuf<int>    i;
+            PinnedBuf<int> hi;
+            PinnedBuf<T>   hz;
+            CSLAM_TRY(t.alloc((size_t)6 * M + 2 * mg));
+            CSLAM_TRY(i.alloc((size_t)4 + 3 * M + mg));
+            CSLAM_TRY(hi.alloc((size_t)4 + 2 * M));
+            CSLAM_TRY(hz.alloc((size_t)2 * M));
+            dAdT     = std::move(t);
+            dAdI     = std::move(i);
+            hAd      = std::move(hi);
+            hAdZ     = std::move(hz);
+            ad_mcap  = M;
+            ad_gcap  = Gc;
+            ad_valid = false;
+        }
+        const size_t M = (size_t)ad_mcap, mg = M * ad_gcap;
+        T *          dZ = dAdT.get(), *dZF = dZ + 2 * M, *dZN = dZ + 4 * M, *pnd = dZ + 6 * M, *pnis = pnd + mg;
+        int *        d_counts = dAdI.get(), *d_idf = d_counts + 4, *d_kind = d_idf + m, *d_idf_f = d_counts + 4 + 2 * M,
+            *pj = d_idf_f + M;
+        const T* R = static_cast<const T*>(Rv);
+        memcpy(hAdZ.get(), Zv, (size_t)2 * m * sizeof(T));
+        CSLAM_HIP_TRY(hipMemcpyAsync(dZ, hAdZ.get(), (size_t)2 * m * sizeof(T), hipMemcpyHostToDevice, stream));
+        if (G > 0)
+        {
+            const int* sg = (pend.kp > 0 && pend.hd_cols[pend.wcur] > 0) ? signs(pend.wcur) : (const int*)nullptr;
+            hipLaunchKernelGGL(ekf_assoc_pair_kernel<T>, dim3(G), dim3(256), 0, stream, (const T*)dX.get(), (const T*)dP.get(),
+                               (const T*)dPv.get(), ldp, n, R[0], R[1], R[2], R[3], opt.lower, (const T*)wbase(pend.wcur), ldp,
+                               pend.kp, sg, (const T*)dZ, m, (T)g1, pnd, pj, pnis);
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(ekf_assoc_resolve_kernel<T>, dim3(1), dim3(kSimThreads), 0, stream, (const T*)pnd, (const int*)pj,
+                           (const T*)pnis, G, (const T*)dZ, m, (T)g2, d_idf, d_kind, dZF, d_idf_f, dZN, d_counts);
+        CSLAM_HIP_TRY(hipGetLastError());
+        ad_valid = true;
+        CSLAM_HIP_TRY(hipMemcpyAsync(hAd.get(), d_counts, ((size_t)4 + 2 * m) * sizeof(int), hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        const int* h = hAd.get();
+        if (counts_out)
+        {
+            std::copy(h, h + 3, counts_out);
+        }
+        if (idf_out)
+        {
+            std::copy(h + 4, h + 4 + m, idf_out);
+        }
+        if (kind_out)
+        {
+            std::copy(h + 4 + m, h + 4 + 2 * m, kind_out);
+        }
+        return CSLAM_OK;
+    }
+
+    int association_device_ptrs(const void** dZF, const int** d_idf, const void** dZN, const int** d_counts) override
+    {
+        if (!ad_valid)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "association_device_ptrs: no association has been made on this handle");
+        }
+        const size_t M = (size_t)ad_mcap;
+        if (dZF)
+        {
+            *dZF = dAdT.get() + 2 * M;
+        }
+        if (dZN)
+        {
+            *dZN = dAdT.get() + 4 * M;
+        }
+        if (d_idf)
+        {
+            *d_idf = dAdI.get() + 4 + 2 * M;
+        }
+        if (d_counts)
+        {
+            *d_counts = dAdI.get();
+        }
         return CSLAM_OK;
     }
 
@@ -3075,6 +3187,36 @@ int cslam_ekf_associate(cslam_ekf_t h, const void* Z, int m, const void* R, doub
         return rc;
     }
     return B(h)->associate(Z, m, R, gate1, gate2, idf_out, kind_out);
+}
+
+int cslam_ekf_associate_deferred(cslam_ekf_t h, const void* Z, int m, const void* R, double gate1, double gate2,
+                                 int* idf_out, int* kind_out, int* counts_out)
+{
+    CSLAM_NEED(h);
+    if (m < 0 || !R || (m > 0 && !Z))
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "associate_deferred: bad arguments (m=%d)", m);
+    }
+    if (m == 0)
+    {
+        if (counts_out)
+        {
+            counts_out[0] = counts_out[1] = counts_out[2] = 0;
+        }
+        return CSLAM_OK;
+    }
+    if (int rc = B(h)->resolve_predict()) // (as get_landmarks: the held predict, the pose queue, a queued look-ahead update)
+    {
+        return rc;
+    }
+    return B(h)->associate_deferred(Z, m, R, gate1, gate2, idf_out, kind_out, counts_out);
+}
+
+int cslam_ekf_association_device_ptrs(cslam_ekf_t h, const void** dZF, const int** d_idf, const void** dZN,
+                                      const int** d_counts)
+{
+    CSLAM_NEED(h);
+    return B(h)->association_device_ptrs(dZF, d_idf, dZN, d_counts);
 }
 
 int cslam_ekf_observe_heading(cslam_ekf_t h, double phi, int use_heading)

@@ -273,6 +273,41 @@ class EKF:
             ZN = np.asfortranarray(Z[:, kind == 2])
         return ZF, ZN, idf[kind == 1].astype(np.int32)
 
+    def associate_deferred(self, Z, R, gate1, gate2, with_counts: bool = False):
+        """associate() read from the deferred covariance as it stands (cslam_ekf_associate_deferred): nothing pending is
+        applied and the run continues bit for bit as without the call.  -> (idf[m], kind[m]), and with_counts also
+        counts[3] = (associated, new, dropped).  The split stays on the device: association_device_ptrs()."""
+        Z = np.asarray(Z, dtype=self.dtype, order="F").reshape(2, -1, order="F")
+        R = np.asarray(R, dtype=self.dtype, order="F")
+        m = Z.shape[1]
+        idf = np.zeros(max(m, 1), dtype=np.int32)
+        kind = np.zeros(max(m, 1), dtype=np.int32)
+        counts = np.zeros(3, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        check(self._L.cslam_ekf_associate_deferred(self._h, _vp(Z) if m else None, C.c_int(m), _vp(R),
+                                                   C.c_double(float(gate1)), C.c_double(float(gate2)),
+                                                   idf.ctypes.data_as(ip), kind.ctypes.data_as(ip), counts.ctypes.data_as(ip)))
+        return (idf[:m], kind[:m], counts) if with_counts else (idf[:m], kind[:m])
+
+    def data_associate_deferred(self, Z, R, gate1, gate2):
+        """data_associate() on associate_deferred(): (ZF, ZN, idf), with the same REF_EXACT rule for ZN."""
+        Z = np.asarray(Z, dtype=self.dtype, order="F").reshape(2, -1, order="F")
+        idf, kind = self.associate_deferred(Z, R, gate1, gate2)
+        ZF = np.asfortranarray(Z[:, kind == 1])
+        if self.quirks == Q_REF_EXACT:
+            ZN = np.zeros((0, 0), dtype=self.dtype)
+        else:
+            ZN = np.asfortranarray(Z[:, kind == 2])
+        return ZF, ZN, idf[kind == 1].astype(np.int32)
+
+    def association_device_ptrs(self):
+        """(dZF, d_idf, dZN, d_counts): raw device pointers of the split the last associate_deferred() call with m > 0 left
+        in HBM -- ZF (2 x mf), idf (mf int32), ZN (2 x mn), counts (3 int32) -- valid until the next such call; dZF and d_idf
+        are fit for update_device(dZF, mf, R, d_idf) (cslam_ekf_association_device_ptrs)."""
+        p = [C.c_void_p(None) for _ in range(4)]
+        check(self._L.cslam_ekf_association_device_ptrs(self._h, *(C.byref(q) for q in p)))
+        return tuple(q.value or 0 for q in p)
+
     # reference-style aliases
     observeHeading = observe_heading
     dataAssociate = data_associate

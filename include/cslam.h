@@ -162,6 +162,32 @@ int cslam_ekf_observe_heading(cslam_ekf_t h, double phi, int use_heading);
 int cslam_ekf_associate(cslam_ekf_t h, const void* Z, int m, const void* R, double gate1, double gate2, int* idf_out,
                         int* kind_out);
 
+/* The same association -- Slam::dataAssociate, EKF.cpp:235-326 with EKF::computeAssociation EKF.cpp:131-144 -- read from
+ * the deferred form of the covariance (P = Ps - Wp diag(s) Wp^T over the pending columns) WITHOUT applying it: nothing is
+ * flushed, the pending columns, their signs and P stay as they are, and the run continues bit for bit as without the
+ * call.  Rule and measure are those of cslam_ekf_associate: kind 1 / 2 / 0, idf 1-based or 0, all four entries of R read,
+ * strict comparisons, a NaN takes part in none, an empty map gives kind 2 everywhere.  Queued work is launched first
+ * exactly as cslam_ekf_get_landmarks does (a held predict, the pose queue, a queued look-ahead update as a window of
+ * one); two-stream mode (CSLAM_PIPELINE=1) waits for the P-GEMMs in flight.
+ * Host results: idf_out[m], kind_out[m], counts_out[3] = {mf, mn, dropped}; any of the three may be NULL.  They come
+ * back in one copy; the call synchronises the chain stream.  The split the reference returns (slam.h:482-487) stays on
+ * the device, in observation order: ZF (2 x mf, kind 1), their features idf_f (mf), ZN (2 x mn, kind 2) and the counts,
+ * see cslam_ekf_association_device_ptrs.  CSLAM_Q_REF_EXACT does not empty ZN here (EKF.cpp:307 stays a policy of the
+ * callers, as for cslam_ekf_associate).
+ * m = 0 returns CSLAM_OK at once with counts 0, launches nothing and leaves the device lists of the previous call as they
+ * are; m < 0, a NULL R, or a NULL Z with m > 0 returns CSLAM_ERR_BAD_ARG and changes nothing.  Any m is allowed. */
+int cslam_ekf_associate_deferred(cslam_ekf_t h, const void* Z, int m, const void* R, double gate1, double gate2,
+                                 int* idf_out, int* kind_out, int* counts_out /* [3]: mf, mn, dropped */);
+
+/* The device lists of the last cslam_ekf_associate_deferred call with m > 0 (the ZF / idf / ZN of Slam::dataAssociate,
+ * EKF.cpp:235-326, slam.h:482-487), in the handle's dtype: dZF (2 x mf), d_idf (mf ints, 1-based), dZN (2 x mn),
+ * d_counts (3 ints).  Any output may be NULL.  The pointers are valid until the next associate_deferred call on the
+ * handle, which rewrites (and may move) them.  They are fit for cslam_ekf_update_device(h, dZF, mf, R, d_idf, batch)
+ * under the lifetime rules stated there: the next associate_deferred call launches what is queued and is ordered behind
+ * it on the handle's chain stream.  Before any such call: CSLAM_ERR_BAD_ARG. */
+int cslam_ekf_association_device_ptrs(cslam_ekf_t h, const void** dZF, const int** d_idf, const void** dZN,
+                                      const int** d_counts);
+
 /* Deferred downdates.  slam.h:260 (P = P - W1*W1^T) is linear in the W1 panels, so the engine may keep
  * P = Ps - Wp*Wp^T with up to max_pending_columns columns of not-yet-applied panels and apply them in ONE
  * P-GEMM (k = pending columns): every reader of P adds the rank-k correction for the columns it touches, so

@@ -13,7 +13,8 @@
 //   HipEKF::update           slam.h:938-943   EKF.cpp:481-496        -> cslam_ekf_update   (batchUpdate / singleUpdate too)
 //   HipEKF::augment          slam.h:190-191   EKF.cpp:9-26           -> cslam_ekf_augment  (addOneNewFeature too)
 //   HipEKF::observeHeading   slam.h:788       EKF.cpp:328-352        -> cslam_ekf_observe_heading
-//   HipEKF::dataAssociate    slam.h:482-487   EKF.cpp:235-326        -> cslam_ekf_associate
+//   HipEKF::dataAssociate    slam.h:482-487   EKF.cpp:235-326        -> cslam_ekf_associate, or, after
+//                            setDeferredAssociation(true),              -> cslam_ekf_associate_deferred (nothing flushed)
 //   HipEKF::pose / scoreReset / scoreTruth / score / scores   (the pose test/main.cpp:136 prints and the blocks
 //                            EKF.cpp:131-144 reads, scored and logged on the device)
 //                                                                    -> cslam_ekf_get_pose / _score_reset / _score_set_truth / _score / _get_scores
@@ -140,8 +141,16 @@ class HipEKF : public EKF
         push(X, P);
         const int        m = static_cast<int>(Z.cols());
         std::vector<int> idf(static_cast<size_t>(m > 0 ? m : 1)), kind(static_cast<size_t>(m > 0 ? m : 1));
-        report(cslam_ekf_associate(h_, Z.data(), m, R.data(), gate1, gate2, idf.data(), kind.data()),
-               "HipEKF::dataAssociate");
+        if (deferredAssociation_)
+        {
+            report(cslam_ekf_associate_deferred(h_, Z.data(), m, R.data(), gate1, gate2, idf.data(), kind.data(), nullptr),
+                   "HipEKF::dataAssociate");
+        }
+        else
+        {
+            report(cslam_ekf_associate(h_, Z.data(), m, R.data(), gate1, gate2, idf.data(), kind.data()),
+                   "HipEKF::dataAssociate");
+        }
         int nf = 0;
         for (int i = 0; i < m; i++)
         {
@@ -162,6 +171,11 @@ class HipEKF : public EKF
         }
         return out;
     }
+
+    /// on: dataAssociate reads the deferred covariance as it stands (cslam_ekf_associate_deferred: the pending downdate
+    /// stays pending, the run continues bit for bit as without the call); off (the default): cslam_ekf_associate
+    void setDeferredAssociation(bool on) { deferredAssociation_ = on; }
+    bool deferredAssociation() const { return deferredAssociation_; }
 
     /// the pose and its 3 x 3 covariance block without touching P (no downdate, no copy of P): what a host scorer reads
     /// beside the line test/main.cpp:136 prints
@@ -230,6 +244,7 @@ class HipEKF : public EKF
   private:
     cslam_ekf_t h_        = nullptr;
     bool        uploaded_ = false;
+    bool        deferredAssociation_ = false;
 
     static void report(int rc, const char* who)
     {

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Step rate of a single-handle filter that associates every step: cslam_ekf_associate (flushes the pending covariance
+downdate, two copies back) against cslam_ekf_associate_deferred (reads the deferred form, leaves the split on the device),
+and the known-association loop without any association as the floor.  set_deferred(128), default look-ahead, m
+observations of mapped landmarks per step.
+
+    (a) predict + associate          + update(batch) with the association's own host lists
+    (b) predict + associate_deferred + update_device from association_device_ptrs()
+    (c) predict + update_device with known correspondences (no association)
+
+(a) and (b) are alternated --rounds times on fresh handles; every run is timed with events on the handle's chain stream
+around --steps steps after --warmup steps, and ends in a synchronise.  Prints one JSON line per run and a summary line.
+For the device time of ekf_assoc_pair_kernel run one loop under the profiler,
+`rocprofv3 --kernel-trace --stats -- python tools/ekf_assoc_timing.py --only b --rounds 1`, and set it against
+`pair_bytes`: the 2 nf kp panel scalars and 25 nf entries of P the kernel has to read.
+
+    python tools/ekf_assoc_timing.py [--landmarks 5000] [--dtype f32] [--m 32] [--steps 200] [--warmup 20] [--rounds 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from conan_slam_amd import EKF, Q_TEXTBOOK  # noqa: E402
+
+GATES = (4.0, 25.0)
+
+
+def _state(N, dtype, seed):
+    rng = np.random.default_rng(seed)
+    X = np.concatenate([[0.0, 0.0, 0.1], rng.uniform(-500, 500, 2 * N)]).astype(dtype)
+    P = np.eye(3 + 2 * N, dtype=dtype, order="F")
+    P[:3, :3] *= 1e-2
+    return X, P
+
+
+def _scans(X, N, m, steps, dtype, seed):
+    """per step: (idf [m], Z [2, m]) -- noisy observations of m mapped landmarks from the (standing) true pose"""
+    rng = np.random.default_rng(seed)
+    out = []
+    X = X.astype(np.float64)
+    for _ in range(steps):
+        idf = np.sort(rng.permutation(N)[:m] + 1).astype(np.int32)
+        fx = 3 + 2 * (idf - 1)
+        dx, dy = X[fx] - X[0], X[fx + 1] - X[1]
+        Z = np.stack([np.hypot(dx, dy) + 0.1 * rng.normal(size=m), np.arctan2(dy, dx) - X[2] + 0.002 * rng.normal(size=m)])
+        out.append((idf, np.asfortranarray(Z.astype(dtype))))
+    return out
+
+
+def run(loop, N, dtype, m, steps, warmup, seed=1):
+    import torch
+
+    Q = np.diag([0.18, 6e-4]).astype(dtype)
+    R = np.diag([0.08, 0.0024]).astype(dtype)
+    X, P = _state(N, dtype, 3)
+    scans = _scans(X, N, m, warmup + steps, dtype, seed)
+    e = EKF(N, dtype=dtype, quirks=Q_TEXTBOOK, sync_mode=False)
+    e.set_state(X, P)
+    e.set_deferred(128)
+    stream = torch.cuda.ExternalStream(e.streams()[0])
+    dev = [(torch.from_numpy(np.ascontiguousarray(Z.reshape(-1, order="F"))).cuda(), torch.from_numpy(idf).cuda())
+           for idf, Z in scans] if loop == "c" else None
+    torch.cuda.synchronize()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    associated = 0
+    for t, (idf_true, Z) in enumerate(scans):
+        if t == warmup:
+            e.synchronize()
+            t0.record(stream)
+        e.predict(0.0, 0.0, Q, 73.0, 0.01)   # (the vehicle stands: the scans stay scans of the estimated map)
+        if loop == "a":
+            idf, kind = e.associate(Z, R, *GATES)
+            sel = kind == 1
+            e.update(np.asfortranarray(Z[:, sel]), R, idf[sel], True)
+            associated += int(sel.sum()) if t >= warmup else 0
+        elif loop == "b":
+            idf, kind, counts = e.associate_deferred(Z, R, *GATES, with_counts=True)
+            dZF, d_idf, _, _ = e.association_device_ptrs()
+            e.update_device(dZF, int(counts[0]), R, d_idf, True)
+            associated += int(counts[0]) if t >= warmup else 0
+        else:
+            dZ, dI = dev[t]
+            e.update_device(dZ.data_ptr(), m, R, dI.data_ptr(), True)
+            associated += m if t >= warmup else 0
+    e.synchronize()
+    t1.record(stream)
+    t1.synchronize()
+    ms = t0.elapsed_time(t1)
+    trace = e.trace()
+    e.close()
+    return {"loop": loop, "landmarks": N, "dtype": np.dtype(dtype).name, "m": m, "steps": steps, "ms": round(ms, 3),
+            "steps_per_s": round(1e3 * steps / ms, 1), "associated": associated, "trace": trace}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--landmarks", type=int, default=5000)
+    ap.add_argument("--dtype", choices=["f32", "f64"], default="f32")
+    ap.add_argument("--m", type=int, default=32)
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--only", choices=["a", "b", "c"], default=None)
+    args = ap.parse_args()
+    dtype = np.float32 if args.dtype == "f32" else np.float64
+    res = {"a": [], "b": [], "c": []}
+    for r in range(args.rounds):
+        for loop in ([args.only] if args.only else ["a", "b"] + (["c"] if r in (0, args.rounds - 1) else [])):
+            out = run(loop, args.landmarks, dtype, args.m, args.steps, args.warmup)
+            res[loop].append(out["steps_per_s"])
+            print(json.dumps(out), flush=True)
+    size = np.dtype(dtype).itemsize
+    summary = {"workload": "ekf_assoc_timing", "landmarks": args.landmarks, "dtype": args.dtype, "m": args.m,
+               "pair_bytes": {f"kp{kp}": (2 * args.landmarks * kp + 25 * args.landmarks) * size for kp in (0, 64, 128)}}
+    for k, v in res.items():
+        if v:
+            summary[k] = {"runs": v, "median": float(np.median(v)), "min": min(v), "max": max(v)}
+    if res["a"] and res["b"]:
+        a, b = res["a"], res["b"]
+        summary["every_b_faster_than_every_a"] = bool(min(b) > max(a))
+        summary["median_gap_over_range_of_a"] = round((np.median(b) - np.median(a)) / max(max(a) - min(a), 1e-9), 2)
+    if res["b"] and res["c"]:
+        summary["b_over_c"] = round(float(np.median(res["b"]) / np.median(res["c"])), 3)
+    print(json.dumps(summary), flush=True)
+
+
+if __name__ == "__main__":
+    main()
