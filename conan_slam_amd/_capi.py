@@ -160,6 +160,14 @@ _PROTOTYPES.update({
 EKF_ASSOC_DEFERRED_SYMBOLS = ("cslam_ekf_associate_deferred", "cslam_ekf_association_device_ptrs")
 
 
+# The Monte-Carlo driver over single handles: one host thread and one stream pair per handle (ekf.run_many).  The handle
+# and pointer tables and the controls travel as plain addresses.
+_PROTOTYPES.update({
+    "cslam_ekf_run_many": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                           C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int],
+})
+
+
 def declared_symbols(header_path: str = HEADER_PATH):
     """Names of every function include/cslam.h declares (used by the export test)."""
     text = open(header_path).read()

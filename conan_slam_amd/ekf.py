@@ -341,6 +341,34 @@ class EKF:
         return out
 
 
+def run_many(engines, steps: int, v, swa, Q, wb: float, dt: float, dZ_ptrs, d_idf_ptrs, m: int, R, batch: bool = True):
+    """steps x {predict(v[t], swa[t], Q, wb, dt); update_device(Z_t, R, idf_t, batch)} on every EKF of `engines` at once,
+    one host thread and one stream pair per handle (cslam_ekf_run_many).  The handles may differ in size but share one
+    dtype: Q and R are read in it.  dZ_ptrs / d_idf_ptrs: one device pointer per engine (steps x 2m scalars / steps x m
+    int32, step-major).  An entry of None goes to the library as a null pointer, which answers ERR_BAD_ARG."""
+    engines = list(engines)
+    if len(dZ_ptrs) != len(engines) or len(d_idf_ptrs) != len(engines):
+        raise ValueError("run_many: not one input pointer per engine")
+    dtypes = {e.dtype for e in engines if e is not None}
+    if len(dtypes) > 1:
+        raise ValueError("run_many: the engines must share one dtype (Q and R are read in it)")
+    dtype = dtypes.pop() if dtypes else np.dtype(np.float32)
+    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+    swa = np.ascontiguousarray(swa, dtype=np.float64).reshape(-1)
+    if v.shape[0] < steps or swa.shape[0] < steps:
+        raise ValueError("run_many: controls shorter than `steps`")
+    Q = np.asfortranarray(np.asarray(Q, dtype=dtype).reshape(2, 2))
+    R = np.asfortranarray(np.asarray(R, dtype=dtype).reshape(2, 2))
+    cnt = len(engines)
+    hs = (C.c_void_p * cnt)(*[e._h if e is not None else None for e in engines])
+    zs = (C.c_void_p * cnt)(*[int(p) if p else None for p in dZ_ptrs])
+    ids = (C.c_void_p * cnt)(*[int(p) if p else None for p in d_idf_ptrs])
+    check(_capi.lib().cslam_ekf_run_many(hs, C.c_int(cnt), C.c_int(int(steps)), v.ctypes.data_as(C.POINTER(C.c_double)),
+                                         swa.ctypes.data_as(C.POINTER(C.c_double)), _vp(Q), C.c_double(float(wb)),
+                                         C.c_double(float(dt)), zs, ids, C.c_int(int(m)), _vp(R),
+                                         C.c_int(1 if batch else 0)))
+
+
 class EKFBatch:
     """`instances` independent f32 filters of `n_landmarks` landmarks each, advancing in lockstep (cslam_ekf_batch_*):
     the Monte-Carlo unit of BASELINE configs[4] (test/main.cpp:132-200 x I) with one launch per stage for all
