@@ -160,6 +160,18 @@ _PROTOTYPES.update({
 EKF_ASSOC_DEFERRED_SYMBOLS = ("cslam_ekf_associate_deferred", "cslam_ekf_association_device_ptrs")
 
 
+# The update with the observation count read on the device (slam.h:938-943, EKF.cpp:93-129) and the association call that
+# does not wait, which together run associate -> update with no host round trip in between.
+FACTOR_COUNT_CLAMPED = 64
+EKF_COUNTED_M_CAP = {F32: 64, F64: 32}  # largest m_cap cslam_ekf_update_counted accepts
+_PROTOTYPES.update({
+    "cslam_ekf_update_counted": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    "cslam_ekf_associate_deferred_async": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double],
+    "cslam_ekf_association_wait": [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+})
+EKF_COUNTED_SYMBOLS = ("cslam_ekf_update_counted", "cslam_ekf_associate_deferred_async", "cslam_ekf_association_wait")
+
+
 # The Monte-Carlo driver over single handles: one host thread and one stream pair per handle (ekf.run_many).  The handle
 # and pointer tables and the controls travel as plain addresses.
 _PROTOTYPES.update({

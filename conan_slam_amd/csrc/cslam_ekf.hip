@@ -30,6 +30,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
 #include "ekf_assoc_deferred_kernels.hpp"
+#include "ekf_counted_kernels.hpp"
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
 #include "ekf_options.hpp"
@@ -169,8 +170,12 @@ struct EkfBase
     virtual int augment(const void* Z, int q, const void* R)                                   = 0;
     virtual int observe_heading(double phi, int use)                                           = 0;
     virtual int associate(const void* Z, int m, const void* R, double g1, double g2, int* idf_out, int* kind) = 0;
+    virtual int update_counted(const void* dZ, int m_cap, const void* R, const int* d_idf, const int* d_count,
+                               int batch)                                                      = 0;
     virtual int associate_deferred(const void* Z, int m, const void* R, double g1, double g2, int* idf_out, int* kind,
                                    int* counts)                                                = 0;
+    virtual int associate_deferred_async(const void* Z, int m, const void* R, double g1, double g2) = 0;
+    virtual int association_wait(int* idf_out, int* kind, int* counts)                         = 0;
     virtual int association_device_ptrs(const void** dZF, const int** d_idf, const void** dZN,
                                         const int** d_counts)                                  = 0;
     virtual int factor_status(int* flags, int clear)                                           = 0;
@@ -332,9 +337,15 @@ struct Ekf : EkfBase
         {
             CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_mfma_big_f32<128>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_mfma_big_f32_counted<128>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         }
         else
         {
+            CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_mfma_f64_counted<64>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_mfma_f64_counted<32>),
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_mfma_f64<64>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             CSLAM_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&ekf_factor_mfma_f64<32>),
@@ -1051,8 +1062,97 @@ struct Ekf : EkfBase
     PinnedBuf<T>   hAdZ; // staging of Z (2 M)
     int            ad_mcap = 0, ad_gcap = 0;
     bool           ad_valid = false; // the device lists hold the split of a call
+    // An asynchronous call leaves its results on their way into hAd behind ev_ad; association_wait hands them out.
+    Event ev_ad;
+    bool  ad_async = false; // an asynchronous call is outstanding ...
+    int   ad_async_m = 0;   // ... for this many observations (0: nothing was enqueued)
+    bool  ad_ev_pending = false; // ev_ad has been recorded and not waited for since
     int associate_deferred(const void* Zv, int m, const void* Rv, double g1, double g2, int* idf_out, int* kind_out,
                            int* counts_out) override
+    {
+        ad_async = false; // (a later associate call discards outstanding results)
+        int rc   = associate_deferred_enqueue(Zv, m, Rv, g1, g2);
+        if (rc)
+        {
+            return rc;
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        ad_results(m, idf_out, kind_out, counts_out);
+        return CSLAM_OK;
+    }
+
+    int associate_deferred_async(const void* Zv, int m, const void* Rv, double g1, double g2) override
+    {
+        ad_async = false;
+        int rc   = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        if (m > 0)
+        {
+            if (!ev_ad && (rc = ev_ad.create(hipEventDisableTiming)))
+            {
+                return rc;
+            }
+            if ((rc = associate_deferred_enqueue(Zv, m, Rv, g1, g2)))
+            {
+                return rc;
+            }
+            CSLAM_HIP_TRY(hipEventRecord(ev_ad.get(), stream));
+            ad_ev_pending = true;
+        }
+        ad_async   = true;
+        ad_async_m = m;
+        return CSLAM_OK;
+    }
+
+    int association_wait(int* idf_out, int* kind_out, int* counts_out) override
+    {
+        if (!ad_async)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "association_wait: no asynchronous association is outstanding on this handle");
+        }
+        int rc = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        ad_async = false;
+        if (ad_async_m == 0)
+        {
+            if (counts_out)
+            {
+                counts_out[0] = counts_out[1] = counts_out[2] = 0;
+            }
+            return CSLAM_OK;
+        }
+        CSLAM_HIP_TRY(hipEventSynchronize(ev_ad.get()));
+        ad_ev_pending = false;
+        ad_results(ad_async_m, idf_out, kind_out, counts_out);
+        return CSLAM_OK;
+    }
+
+    // counts | idf[m] | kind[m] as the copy of the last call left them in hAd
+    void ad_results(int m, int* idf_out, int* kind_out, int* counts_out) const
+    {
+        const int* h = hAd.get();
+        if (counts_out)
+        {
+            std::copy(h, h + 3, counts_out);
+        }
+        if (idf_out)
+        {
+            std::copy(h + 4, h + 4 + m, idf_out);
+        }
+        if (kind_out)
+        {
+            std::copy(h + 4 + m, h + 4 + 2 * m, kind_out);
+        }
+    }
+
+    // everything of an association up to and including the one copy into the pinned hAd, on the handle's stream
+    int associate_deferred_enqueue(const void* Zv, int m, const void* Rv, double g1, double g2)
     {
         int rc = use_device();
         if (rc || (rc = wait_pgemm()))
@@ -1087,6 +1187,11 @@ struct Ekf : EkfBase
         int *        d_counts = dAdI.get(), *d_idf = d_counts + 4, *d_kind = d_idf + m, *d_idf_f = d_counts + 4 + 2 * M,
             *pj = d_idf_f + M;
         const T* R = static_cast<const T*>(Rv);
+        if (ad_ev_pending) // (an asynchronous call nobody waited for: its upload may still be reading hAdZ)
+        {
+            CSLAM_HIP_TRY(hipEventSynchronize(ev_ad.get()));
+            ad_ev_pending = false;
+        }
         memcpy(hAdZ.get(), Zv, (size_t)2 * m * sizeof(T));
         CSLAM_HIP_TRY(hipMemcpyAsync(dZ, hAdZ.get(), (size_t)2 * m * sizeof(T), hipMemcpyHostToDevice, stream));
         if (G > 0)
@@ -1102,20 +1207,6 @@ struct Ekf : EkfBase
         CSLAM_HIP_TRY(hipGetLastError());
         ad_valid = true;
         CSLAM_HIP_TRY(hipMemcpyAsync(hAd.get(), d_counts, ((size_t)4 + 2 * m) * sizeof(int), hipMemcpyDeviceToHost, stream));
-        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
-        const int* h = hAd.get();
-        if (counts_out)
-        {
-            std::copy(h, h + 3, counts_out);
-        }
-        if (idf_out)
-        {
-            std::copy(h + 4, h + 4 + m, idf_out);
-        }
-        if (kind_out)
-        {
-            std::copy(h + 4 + m, h + 4 + 2 * m, kind_out);
-        }
         return CSLAM_OK;
     }
 
@@ -1468,6 +1559,7 @@ struct Ekf : EkfBase
             return rc;
         }
         last_k = k;
+        last_counted = false;
         dbgS = dbgGt = dbgV = nullptr; // (debug_last_update reads the handle's own workspace again)
         if ((rc = prof.begin(CSLAM_STAGE_GATHER, stream)))
         {
@@ -1566,6 +1658,226 @@ struct Ekf : EkfBase
         {
             return rc;
         }
+        return CSLAM_OK;
+    }
+
+    // ---------------------------------------------------------------- the counted update (ekf_counted_kernels.hpp)
+    // batch_on_device(dZ, dIdf, c, R) with c = clamp(*d_count, 0, m_cap) read by every kernel in stream order: the host
+    // never learns c.  It therefore plans for m_cap -- workspace, kernel class, grids, the room in the pending store, the
+    // 2 m_cap columns it books -- and the gain kernel writes the columns beyond 2c as zeros.  The classic chain only:
+    // queued work (a look-ahead window, the pose queue) and a held predict are launched first and nothing is fused.
+    // Nothing in here waits for the device or copies from it.
+    bool last_counted = false; // the last update was a counted one: debug_last_update cannot know its k
+    int  update_counted(const void* dZv, int m_cap, const void* Rv, const int* dIdf, const int* d_count, int batch) override
+    {
+        const int m_max = sizeof(T) == 4 ? 64 : 32; // the ranges of the tuned factor and gain kernels
+        if (m_cap < 0 || m_cap > m_max || !Rv || !dZv || !dIdf || !d_count || !batch || sync_mode || opt.pipeline)
+        {
+            return fail(CSLAM_ERR_BAD_ARG,
+                        "update_counted: bad arguments (m_cap=%d of at most %d, batch=%d, sync_mode=%d, two streams=%d)", m_cap,
+                        m_max, batch, sync_mode, (int)opt.pipeline);
+        }
+        if (m_cap == 0)
+        {
+            return CSLAM_OK;
+        }
+        const T*  dZ = static_cast<const T*>(dZv);
+        const T*  R  = static_cast<const T*>(Rv);
+        const int m = m_cap, k = 2 * m_cap;
+        int       rc = use_device();
+        if (rc || (rc = ensure_k(k)) || (rc = resolve_predict())) // (drains a queued look-ahead update as a window of one)
+        {
+            return rc;
+        }
+        fuse_now = false;
+        const bool small_corr = pend.kp > 0 && pend.kp <= (opt.gather_corr_wide ? kGatherCorrMax : kGatherCorr);
+        const bool wide_corr  = small_corr && pend.kp > kGatherCorr;
+        const int  k8w        = round_up(k, 8);
+        if ((rc = ensure_w(std::max(k8w, kp_call_limit)))) // (may flush and move the store)
+        {
+            return rc;
+        }
+        // the deferral window and the flush rules of batch_on_device with k = 2 m_cap
+        const int window = std::min(pend.wcap, defer_max > 0 ? defer_max : (kp_call_limit > 0 ? kp_call_limit : pend.wcap));
+        if (pend.kp > 0 && (pend.kp + k > window || pend.kp + k8w > pend.wcap) && (rc = flush()))
+        {
+            return rc;
+        }
+        if ((rc = wait_pgemm()))
+        {
+            return rc;
+        }
+        last_k       = k;
+        last_counted = true;
+        dbgS = dbgGt = dbgV = nullptr;
+        if ((rc = prof.begin(CSLAM_STAGE_GATHER, stream)))
+        {
+            return rc;
+        }
+        sub_valid         = (k > 16 && k <= 64 && (pend.kp == 0 || small_corr) && ws.dSub.get() != nullptr);
+        const int  kc     = pend.kp;
+        const T*   Wc     = wbase(pend.wcur);
+        const int* sg     = (kc > 0 && pend.hd_cols[pend.wcur] > 0) ? signs(pend.wcur) : (const int*)nullptr;
+        const int  n_pad  = round_up(n, kTile);
+        {
+            T*       sub  = sub_valid ? ws.dSub.get() : nullptr;
+            const PredictArgs<T> pnone{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
+            const T* Wg   = kc > 0 ? Wc : (const T*)nullptr;
+            T*       yout = (kc > 0 && !small_corr) ? ws.dY.get() : (T*)nullptr;
+            if (wide_corr)
+            {
+                const dim3 wgrid((n + 255) / 256, (m + kGatherObsWide - 1) / kGatherObsWide);
+                hipLaunchKernelGGL((ekf_gather_counted_kernel<T, kGatherCorrMax, kGatherObsWide>), wgrid, dim3(256), 0, stream,
+                                   dX.get(), dP.get(), dPv.get(), ldp, n, dZ, dIdf, d_count, m_cap, ws.dPHT.get(), ldp,
+                                   opt.lower, sub, pnone, (T*)nullptr, Wg, ldp, kc, sg, dFlags.get(), yout);
+            }
+            else
+            {
+                const dim3 ggrid((n + 255) / 256, (m + kGatherObs - 1) / kGatherObs);
+                hipLaunchKernelGGL(ekf_gather_counted_kernel<T>, ggrid, dim3(256), 0, stream, dX.get(), dP.get(), dPv.get(),
+                                   ldp, n, dZ, dIdf, d_count, m_cap, ws.dPHT.get(), ldp, opt.lower, sub, pnone, (T*)nullptr, Wg,
+                                   ldp, kc, sg, dFlags.get(), yout);
+            }
+        }
+        CSLAM_HIP_TRY(hipGetLastError());
+        T* slot = wbase(pend.wcur) + (size_t)pend.kp * ldp;
+        if ((rc = own_region(pend.wcur)))
+        {
+            return rc;
+        }
+        if (kc > 0 && !small_corr) // PHT -= Wp * (H*Wp)^T (the gather kernel has published Y = H*Wp)
+        {
+            if constexpr (std::is_same<T, float>::value)
+            {
+                hipLaunchKernelGGL(ekf_corr_mfma_f32_counted, dim3(n_pad / 32, (k + 31) / 32), dim3(64), 0, stream, Wc, ldp, n,
+                                   kc, d_count, m_cap, (const T*)ws.dY.get(), ws.dPHT.get(), ldp);
+            }
+            else
+            {
+                hipLaunchKernelGGL(ekf_corr_mfma_f64_counted, dim3(n_pad / 16, (k + 15) / 16), dim3(64), 0, stream, Wc, ldp, n,
+                                   kc, d_count, m_cap, (const T*)ws.dY.get(), ws.dPHT.get(), ldp);
+            }
+            CSLAM_HIP_TRY(hipGetLastError());
+        }
+        if ((rc = prof.end(CSLAM_STAGE_GATHER, stream)) || (rc = prof.begin(CSLAM_STAGE_FACTOR, stream)) ||
+            (rc = launch_factor_counted(dZ, dIdf, d_count, m_cap, R)) || (rc = prof.end(CSLAM_STAGE_FACTOR, stream)) ||
+            (rc = prof.begin(CSLAM_STAGE_GAIN, stream)))
+        {
+            return rc;
+        }
+        if constexpr (std::is_same<T, float>::value)
+        {
+            hipLaunchKernelGGL(ekf_gain_mfma_f32_counted, dim3(n_pad / 32, (k + 31) / 32), dim3(64), 0, stream,
+                               (const T*)ws.dPHT.get(), ldp, n, d_count, m_cap, (const T*)ws.dGt.get(), (const T*)ws.dU.get(),
+                               slot, ldp, dX.get(), dPv.get(), ldp, (const T*)ws.dM.get(), ws.dWv.get());
+        }
+        else
+        {
+            hipLaunchKernelGGL(ekf_gain_mfma_f64_counted, dim3(n_pad / 16, (k + 15) / 16), dim3(64), 0, stream,
+                               (const T*)ws.dPHT.get(), ldp, n, d_count, m_cap, (const T*)ws.dGt.get(), (const T*)ws.dU.get(),
+                               slot, ldp, dX.get(), dPv.get(), ldp, (const T*)ws.dM.get(), ws.dWv.get());
+        }
+        CSLAM_HIP_TRY(hipGetLastError());
+        pose_fused_in_gain = true;
+        if ((rc = prof.end(CSLAM_STAGE_GAIN, stream)))
+        {
+            return rc;
+        }
+        last_slot = slot;
+        pend.appended(k);
+        if (defer_max == 0 && (rc = flush()))
+        {
+            return rc;
+        }
+        if (defer_max > 0 && pend.kp >= defer_max && (rc = flush())) // the window is full: apply it now
+        {
+            return rc;
+        }
+        return CSLAM_OK;
+    }
+
+    // the factor kernel class of launch_factor_args for k = 2 m_cap, in its counted form (always on the handle's workspace)
+    int launch_factor_counted(const T* dZ, const int* dIdf, const int* d_count, int m_cap, const T* R)
+    {
+        FactorArgs<T> a;
+        a.X   = dX.get();
+        a.n   = n;
+        a.Z   = dZ;
+        a.idf = dIdf;
+        a.m   = m_cap; // (the kernel replaces it with the count)
+        for (int i = 0; i < 4; i++)
+        {
+            a.R[i] = R[i];
+        }
+        a.PHT      = ws.dPHT.get();
+        a.ldw      = ldp;
+        a.dS       = ws.dS.get();
+        a.dG       = ws.dG.get();
+        a.dGt      = ws.dGt.get();
+        a.dV       = ws.dV.get();
+        a.dt       = ws.dt_.get();
+        a.flags    = dFlags.get();
+        a.scratchS = ws.dScrS.get();
+        a.scratchG = ws.dScrG.get();
+        a.textbook = (quirks & CSLAM_Q_LOWER_CHOL_GAIN) ? 0 : 1;
+        a.stamps   = nullptr;
+        a.sub      = sub_valid ? ws.dSub.get() : nullptr;
+        a.dM       = ws.dM.get();
+        a.pp       = PredictArgs<T>{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
+        a.P3       = dPv.get();
+        a.ldp3     = ldp;
+        a.pred_out = dPred.get();
+        a.lds_S    = 1;
+        a.lds_G    = 1;
+        m_valid    = true;
+        const int k = 2 * m_cap;
+        g_from_gt   = k > 16;
+        T* du       = ws.dU.get();
+        if (k <= 4)
+        {
+            hipLaunchKernelGGL((ekf_factor_small_counted_kernel<T, 4>), dim3(1), dim3(256), 0, stream, a, du, d_count, m_cap);
+        }
+        else if (k <= 16)
+        {
+            hipLaunchKernelGGL((ekf_factor_small_counted_kernel<T, 16>), dim3(1), dim3(256), 0, stream, a, du, d_count, m_cap);
+        }
+        else if constexpr (std::is_same<T, float>::value)
+        {
+            if (k <= 32)
+            {
+                hipLaunchKernelGGL((ekf_factor_mfma_f32_counted<32>), dim3(1), dim3(256), 0, stream, a, du, d_count, m_cap);
+            }
+            else if (k <= 64)
+            {
+                hipLaunchKernelGGL((ekf_factor_mfma_f32_counted<64>), dim3(1), dim3(256), 0, stream, a, du, d_count, m_cap);
+            }
+            else
+            {
+                constexpr int K   = 128;
+                const size_t  lds = (size_t)(K * (K + 1) + (3 + K) * (K + 1) + (K / 2) * 10 + 6 * K) * sizeof(float) +
+                                   (size_t)(K / 2 + 4) * sizeof(int) + 16;
+                hipLaunchKernelGGL((ekf_factor_mfma_big_f32_counted<128>), dim3(1), dim3(256), lds, stream, a, du, d_count,
+                                   m_cap);
+            }
+        }
+        else
+        {
+            auto lds64 = [](int K) {
+                return (size_t)(K * (K + 1) + (3 + K) * (K + 1) + (K / 2) * 10 + 6 * K) * sizeof(double) +
+                       (size_t)(K / 2 + 4) * sizeof(int) + 16;
+            };
+            if (k <= 32)
+            {
+                hipLaunchKernelGGL((ekf_factor_mfma_f64_counted<32>), dim3(1), dim3(256), lds64(32), stream, a, du, d_count,
+                                   m_cap);
+            }
+            else
+            {
+                hipLaunchKernelGGL((ekf_factor_mfma_f64_counted<64>), dim3(1), dim3(256), lds64(64), stream, a, du, d_count,
+                                   m_cap);
+            }
+        }
+        CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
 
@@ -1965,6 +2277,7 @@ struct Ekf : EkfBase
             return rc;
         }
         last_k = k;
+        last_counted = false;
         PredictArgs<T> pnone{0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, (T)0, 0};
         PredictArgs<T> pa   = fuse_now ? pp : pnone;
         T*             pred = fuse_now ? dPred.get() : (T*)nullptr;
@@ -2482,6 +2795,10 @@ struct Ekf : EkfBase
         {
             f |= CSLAM_FACTOR_INTERNAL;
         }
+        if (hFlags[0] & kFlagCountClamped)
+        {
+            f |= CSLAM_FACTOR_COUNT_CLAMPED;
+        }
         if ((hFlags[0] & kFlagLltFailed) && !(sticky_host & CSLAM_FACTOR_FALLBACK))
         {
             f |= CSLAM_FACTOR_SKIPPED; // async mode: the failed factorisation was not followed up
@@ -2519,6 +2836,10 @@ struct Ekf : EkfBase
         if (rc)
         {
             return rc;
+        }
+        if (last_slot && last_counted) // (its k = 2 * count was only ever known on the device)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "debug_last_update: the last update was a counted one");
         }
         const int k = last_slot ? last_k : 0;
         if (kout)
@@ -3217,6 +3538,36 @@ int cslam_ekf_association_device_ptrs(cslam_ekf_t h, const void** dZF, const int
 {
     CSLAM_NEED(h);
     return B(h)->association_device_ptrs(dZF, d_idf, dZN, d_counts);
+}
+
+int cslam_ekf_associate_deferred_async(cslam_ekf_t h, const void* Z, int m, const void* R, double gate1, double gate2)
+{
+    CSLAM_NEED(h);
+    if (m < 0 || !R || (m > 0 && !Z))
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "associate_deferred_async: bad arguments (m=%d)", m);
+    }
+    if (m > 0)
+    {
+        if (int rc = B(h)->resolve_predict()) // (as cslam_ekf_associate_deferred)
+        {
+            return rc;
+        }
+    }
+    return B(h)->associate_deferred_async(Z, m, R, gate1, gate2);
+}
+
+int cslam_ekf_association_wait(cslam_ekf_t h, int* idf_out, int* kind_out, int* counts_out)
+{
+    CSLAM_NEED(h);
+    return B(h)->association_wait(idf_out, kind_out, counts_out);
+}
+
+int cslam_ekf_update_counted(cslam_ekf_t h, const void* dZ, int m_cap, const void* R, const int* d_idf, const int* d_count,
+                             int batch)
+{
+    CSLAM_NEED(h);
+    return B(h)->update_counted(dZ, m_cap, R, d_idf, d_count, batch);
 }
 
 int cslam_ekf_observe_heading(cslam_ekf_t h, double phi, int use_heading)

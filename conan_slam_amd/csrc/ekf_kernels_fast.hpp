@@ -120,273 +120,7 @@ __device__ __forceinline__ bool wave_tri_inverse(const T (&row)[K], const T (&rd
 template <typename T, int K>
 __global__ void __launch_bounds__(256) ekf_factor_small_kernel(FactorArgs<T> a, T* __restrict__ du)
 {
-    constexpr int LD = K + 1;
-    __shared__ T   S[K * LD];
-    __shared__ T   coef[(K / 2) * 10];
-    __shared__ T   V[K];
-    __shared__ T   tvec[K];
-    __shared__ int fxs[K / 2];
-    __shared__ int sflg[2];
-    const int      k   = 2 * a.m;
-    const int      tid = threadIdx.x;
-
-    auto stamp = [&](int i) {
-        if (a.stamps && tid == 0)
-        {
-            a.stamps[i] = (long long)__builtin_readcyclecounter();
-        }
-    };
-    stamp(0);
-    if (tid == 0)
-    {
-        sflg[0] = 0;
-        sflg[1] = 0;
-    }
-    if (tid < K)
-    {
-        V[tid] = (T)0;
-    }
-    __syncthreads();
-    for (int o = tid; o < a.m; o += 256)
-    {
-        observe_model<T>(a.X, a.n, a.idf[o], a.Z[2 * o], a.Z[2 * o + 1], &coef[o * 10], &V[2 * o], &fxs[o]);
-        a.dV[2 * o]     = V[2 * o];
-        a.dV[2 * o + 1] = V[2 * o + 1];
-    }
-    __syncthreads();
-    // S = H*PHT + RR (slam.h:244): 5-term sums in ascending column order; identity padding.
-    // Two passes with compile-time trip counts: first every global load of the thread's elements is issued
-    // (they are independent L2 hits), then the sums are formed -- one round trip instead of one per element.
-    {
-        constexpr int NE = (K * K + 255) / 256;
-        const T       r00 = a.R[0], r10 = a.R[1], r01 = a.R[2], r11 = a.R[3]; // no indexed kernarg loads below
-        T             ph[NE][5];
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-        {
-            const int e  = tid + it * 256;
-            const int r  = e & (K - 1);
-            const int c  = e / K;
-            const bool in = (e < K * K) && (r < k) && (c < k);
-            const int rc = in ? r : 0, cc = in ? c : 0; // clamped: loads stay unconditional
-            const int fx = fxs[rc >> 1];
-            const T*  p  = a.PHT + (size_t)cc * a.ldw;
-            ph[it][0]    = p[0];
-            ph[it][1]    = p[1];
-            ph[it][2]    = p[2];
-            ph[it][3]    = p[fx];
-            ph[it][4]    = p[fx + 1];
-        }
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-        {
-            const int e = tid + it * 256;
-            if (e < K * K)
-            {
-                const int r = e & (K - 1);
-                const int c = e / K;
-                T         v;
-                if (r < k && c < k)
-                {
-                    const int ob = r >> 1, ra = r & 1;
-                    const T*  cf = &coef[ob * 10 + ra * 5];
-                    T         sm = cf[0] * ph[it][0];
-                    sm += cf[1] * ph[it][1];
-                    sm += cf[2] * ph[it][2];
-                    sm += cf[3] * ph[it][3];
-                    sm += cf[4] * ph[it][4];
-                    const int ri = ra + 2 * (c & 1);
-                    const T   rv = (ri == 0) ? r00 : ((ri == 1) ? r10 : ((ri == 2) ? r01 : r11));
-                    v = sm + (((c >> 1) == ob) ? rv : (T)0);
-                }
-                else
-                {
-                    v = (r == c) ? (T)1 : (T)0;
-                }
-                S[r + c * LD] = v;
-            }
-        }
-    }
-    __syncthreads();
-    // makeSymmetric (slam.h:776-779)
-    for (int e = tid; e < K * K; e += 256)
-    {
-        const int r = e & (K - 1);
-        const int c = e / K;
-        if (r > c)
-        {
-            T v           = (S[r + c * LD] + S[c + r * LD]) * (T)0.5;
-            S[r + c * LD] = v;
-            S[c + r * LD] = v;
-        }
-        else if (r == c)
-        {
-            T d           = S[r + c * LD];
-            S[r + c * LD] = (d + d) * (T)0.5;
-        }
-    }
-    __syncthreads();
-    for (int e = tid; e < K * K; e += 256)
-    {
-        const int r = e & (K - 1), c = e / K;
-        if (r < k && c < k)
-        {
-            a.dS[r + c * k] = S[r + c * LD];
-        }
-    }
-    __syncthreads();
-
-    stamp(1);
-    if (tid < 64) // ---------------- one wave: lane = row of S / column of inv(L)
-    {
-        const int lane = tid;
-        T         row[K];
-#pragma unroll
-        for (int c = 0; c < K; c++)
-        {
-            row[c] = (lane < K) ? S[lane + c * LD] : ((c == lane) ? (T)1 : (T)0);
-        }
-        T          rdiag[K]; // wave-uniform reciprocals of the diagonal of L
-        const bool failed = wave_cholesky<T, K>(row, rdiag, lane);
-        stamp(2);
-        T    x[K];
-        bool bad = false;
-        if (!failed)
-        {
-            bad = wave_tri_inverse<T, K>(row, rdiag, lane, k, x);
-        }
-        stamp(3);
-        const bool zero = failed || bad;
-        // G back into LDS (over S): REF_EXACT G = inv(L) -> G[r][c] = x[r] of lane c; TEXTBOOK G = inv(L)^T
-        if (lane < K)
-        {
-#pragma unroll
-            for (int r = 0; r < K; r++)
-            {
-                const T g = zero ? (T)0 : x[r];
-                if (a.textbook)
-                {
-                    S[lane + r * LD] = g; // G[c][r] = inv(L)[r][c]
-                }
-                else
-                {
-                    S[r + lane * LD] = g;
-                }
-            }
-        }
-        if (lane == 0)
-        {
-            sflg[0] = failed ? 1 : 0;
-            sflg[1] = (!failed && bad) ? 1 : 0;
-        }
-    }
-    __syncthreads();
-    // outputs: G, G^T (coalesced), t = G^T V, u = G t
-    for (int e = tid; e < K * K; e += 256)
-    {
-        const int r = e & (K - 1), c = e / K;
-        if (r < k && c < k)
-        {
-            a.dG[r + c * k] = S[r + c * LD];
-        }
-    }
-    for (int e = tid; e < K * K; e += 256)
-    {
-        const int c = e & (K - 1), r = e / K;
-        if (r < k && c < k)
-        {
-            a.dGt[c + r * k] = S[r + c * LD];
-        }
-    }
-    // t = G^T V and u = G t: 4 lanes per output element, partial sums combined in a fixed order
-    {
-        const int o = tid >> 2, part = tid & 3; // 256 threads = 64 outputs x 4 parts
-        T         s = (T)0;
-        if (o < K)
-        {
-#pragma unroll 4
-            for (int r = part; r < K; r += 4)
-            {
-                s += S[r + o * LD] * V[r]; // padding rows of V are zero
-            }
-        }
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        if (part == 0 && o < K)
-        {
-            if (o < k)
-            {
-                a.dt[o] = s;
-            }
-            tvec[o] = (o < k) ? s : (T)0;
-        }
-        __syncthreads();
-        T s2 = (T)0;
-        if (o < K)
-        {
-#pragma unroll 4
-            for (int c = part; c < K; c += 4)
-            {
-                s2 += S[o + c * LD] * tvec[c];
-            }
-        }
-        s2 += __shfl_xor(s2, 1);
-        s2 += __shfl_xor(s2, 2);
-        if (part == 0 && o < k)
-        {
-            du[o] = s2;
-        }
-        // M[:, c] = G (G^T PHT[c, :]^T), c = 0..2: lets the gain kernel apply the pose-stripe downdate itself
-        // (see ekf_factor_mfma_f32; the sequential update runs this kernel once per observation)
-        if (a.dM != nullptr)
-        {
-            for (int c = 0; c < 3; c++)
-            {
-                __syncthreads();
-                T s3 = (T)0;
-                if (o < K)
-                {
-#pragma unroll 4
-                    for (int r = part; r < K; r += 4)
-                    {
-                        s3 += S[r + o * LD] * ((r < k) ? a.PHT[(size_t)r * a.ldw + c] : (T)0);
-                    }
-                }
-                s3 += __shfl_xor(s3, 1);
-                s3 += __shfl_xor(s3, 2);
-                if (part == 0 && o < K)
-                {
-                    tvec[o] = (o < k) ? s3 : (T)0;
-                }
-                __syncthreads();
-                T s4 = (T)0;
-                if (o < K)
-                {
-#pragma unroll 4
-                    for (int q = part; q < K; q += 4)
-                    {
-                        s4 += S[o + q * LD] * tvec[q];
-                    }
-                }
-                s4 += __shfl_xor(s4, 1);
-                s4 += __shfl_xor(s4, 2);
-                if (part == 0 && o < k)
-                {
-                    a.dM[c * k + o] = s4;
-                }
-            }
-        }
-    }
-    stamp(4);
-    if (tid == 0)
-    {
-        const int code = (sflg[0] ? kFlagLltFailed : 0) | (sflg[1] ? kFlagZeroed : 0);
-        a.flags[1]     = code;
-        if (code)
-        {
-            atomicOr(&a.flags[0], code);
-        }
-    }
+#include "ekf_factor_small_kernel_body.inc" // (shared with ekf_counted_kernels.hpp)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1418,415 +1152,7 @@ __global__ void __launch_bounds__(256) ekf_factor_mfma_f64(FactorArgs<double> a,
 template <int K>
 __global__ void __launch_bounds__(256) ekf_factor_mfma_big_f32(FactorArgs<float> a, float* __restrict__ du)
 {
-    static_assert(K == 64 || K == 128, "two or four 32-wide tiles per dimension");
-    typedef float T;
-    constexpr int NB = K / 32;
-    constexpr int LD = K + 1;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_big[];
-    T*   S    = reinterpret_cast<T*>(smem_big);
-    T*   sub  = S + K * LD;
-    T*   Lm   = sub;
-    T*   coef = sub + (3 + K) * LD;
-    T*   V    = coef + (K / 2) * 10;
-    T*   rd   = V + K;
-    T*   t4   = rd + K;
-    int* fxs  = reinterpret_cast<int*>(t4 + 4 * K);
-    int* sflg = fxs + K / 2;
-    const int k   = 2 * a.m;
-    const int tid = threadIdx.x;
-    auto stamp = [&](int i) {
-        if (a.stamps && tid == 0)
-        {
-            a.stamps[i] = (long long)__builtin_readcyclecounter();
-        }
-    };
-    stamp(0);
-    const T   r00 = a.R[0], r10 = a.R[1], r01 = a.R[2], r11 = a.R[3];
-    if (tid == 0)
-    {
-        sflg[0] = 0;
-        sflg[1] = 0;
-        sflg[2] = 0;
-    }
-    if (tid < K)
-    {
-        V[tid] = (T)0;
-    }
-    __syncthreads();
-    for (int o = tid; o < a.m; o += 256)
-    {
-        observe_model<T>(a.X, a.n, a.idf[o], a.Z[2 * o], a.Z[2 * o + 1], &coef[o * 10], &V[2 * o], &fxs[o]);
-        a.dV[2 * o]     = V[2 * o];
-        a.dV[2 * o + 1] = V[2 * o + 1];
-    }
-    __syncthreads();
-    // the rows of PHT that H touches (rows 0..2, then the two rows of every observed landmark), straight from PHT:
-    // consecutive threads walk down one column
-    for (int e0 = 0; e0 < (3 + k) * k; e0 += 256 * 24)
-    {
-        T v8[24];
-#pragma unroll
-        for (int u = 0; u < 24; u++)
-        {
-            const int e  = e0 + u * 256 + tid;
-            const int ec = (e < (3 + k) * k) ? e : 0;
-            const int c = ec / (3 + k), slot = ec - c * (3 + k);
-            const int row = (slot < 3) ? slot : fxs[(slot - 3) >> 1] + ((slot - 3) & 1);
-            v8[u]         = a.PHT[(size_t)c * a.ldw + row];
-        }
-#pragma unroll
-        for (int u = 0; u < 24; u++)
-        {
-            const int e = e0 + u * 256 + tid;
-            if (e < (3 + k) * k)
-            {
-                const int c = e / (3 + k), slot = e - c * (3 + k);
-                sub[slot * LD + c] = v8[u];
-            }
-        }
-    }
-    __syncthreads();
-    stamp(6);
-    // S = H*PHT + RR (slam.h:244): 5-term sums in ascending column order; identity padding
-#pragma unroll 8
-    for (int e = tid; e < K * K; e += 256)
-    {
-        const int r = e & (K - 1), c = e / K;
-        T         v;
-        if (r < k && c < k)
-        {
-            const int ob = r >> 1, ra = r & 1;
-            const T*  cf = &coef[ob * 10 + ra * 5];
-            T         sm = cf[0] * sub[0 * LD + c];
-            sm += cf[1] * sub[1 * LD + c];
-            sm += cf[2] * sub[2 * LD + c];
-            sm += cf[3] * sub[(3 + 2 * ob) * LD + c];
-            sm += cf[4] * sub[(4 + 2 * ob) * LD + c];
-            const int ri = ra + 2 * (c & 1);
-            const T   rv = (ri == 0) ? r00 : ((ri == 1) ? r10 : ((ri == 2) ? r01 : r11));
-            v            = sm + (((c >> 1) == ob) ? rv : (T)0);
-        }
-        else
-        {
-            v = (r == c) ? (T)1 : (T)0;
-        }
-        S[r + c * LD] = v;
-    }
-    __syncthreads();
-    stamp(7);
-    // makeSymmetric (slam.h:776-779): every thread reads (r, c) and (c, r) of ALL its elements, then all write
-    {
-        constexpr int NE = K * K / 256;
-        T             sv[NE];
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-        {
-            const int e = tid + it * 256;
-            const int r = e & (K - 1), c = e / K;
-            const T   x = S[r + c * LD], y = S[c + r * LD];
-            sv[it]      = (r > c) ? (x + y) * (T)0.5 : ((r < c) ? (y + x) * (T)0.5 : (x + x) * (T)0.5);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int it = 0; it < NE; it++)
-        {
-            const int e = tid + it * 256;
-            const int r = e & (K - 1), c = e / K;
-            S[r + c * LD] = sv[it];
-            if (r < k && c < k)
-            {
-                a.dS[r + c * k] = sv[it];
-            }
-        }
-    }
-    for (int e = tid; e < 3 * K; e += 256) // pose rows of PHT for M, before sub becomes the L store
-    {
-        const int c = e / K, q = e - c * K;
-        t4[(1 + c) * K + q] = (q < k) ? sub[c * LD + q] : (T)0;
-    }
-    __syncthreads();
-    const int lane = tid & 63;
-    const int lj = lane & 31, lh = lane >> 5;
-    f32x16    Tt[NB][NB];
-    if (tid < 64)
-    {
-#pragma unroll
-        for (int I = 0; I < NB; I++)
-        {
-#pragma unroll
-            for (int J = I; J < NB; J++)
-            {
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                {
-                    Tt[I][J][r] = S[(32 * I + (r & 3) + 8 * (r >> 2) + 4 * lh) + (32 * J + lj) * LD];
-                }
-            }
-        }
-    }
-    else
-    {
-        for (int e = tid - 64; e < K * LD; e += 192)
-        {
-            Lm[e] = (T)0;
-        }
-    }
-    __syncthreads(); // #A
-    stamp(1);
-    bool failed = false;
-    if (tid < 64)
-    {
-        static_for<0, NB>([&](auto Jt) {
-            constexpr int J = decltype(Jt)::value;
-            T A4[NB][16]; // per block row I > J: the block's 32 columns, two per entry (the pair shares a register index)
-#pragma unroll
-            for (int I = 0; I < NB; I++)
-            {
-#pragma unroll
-                for (int t = 0; t < 16; t++)
-                {
-                    A4[I][t] = (T)0;
-                }
-            }
-            static_for<0, 32>([&](auto jt) {
-                constexpr int jj = decltype(jt)::value;
-                constexpr int j  = 32 * J + jj;
-                constexpr int rg = (jj & 3) + 4 * (jj >> 3), hf = (jj >> 2) & 1;
-                const T    dj = bcast(Tt[J][J][rg], 32 * hf + jj);
-                failed        = failed || !(dj > (T)0);
-                const T    rs = pivot_rsqrt(dj);
-                const bool on = (lh == hf);
-                T          av[NB];
-#pragma unroll
-                for (int Jc = J; Jc < NB; Jc++)
-                {
-                    const bool keep = on && (Jc > J || lj >= jj);
-                    av[Jc]          = keep ? Tt[J][Jc][rg] * rs : (T)0; // L[32 Jc + lj][j]
-                    if (on)
-                    {
-                        Lm[(32 * Jc + lj) + j * LD] = av[Jc];
-                    }
-                    if (Jc > J)
-                    {
-                        A4[Jc][rg] += av[Jc];
-                    }
-                }
-                if (lane == 0)
-                {
-                    rd[j] = rs;
-                }
-                if (jj < 31)
-                {
-#pragma unroll
-                    for (int Jc = J; Jc < NB; Jc++)
-                    {
-                        Tt[J][Jc] = __builtin_amdgcn_mfma_f32_32x32x2f32(-av[J], av[Jc], Tt[J][Jc], 0, 0, 0);
-                    }
-                }
-            });
-            __builtin_amdgcn_s_waitcnt(0xC07F);
-            if (lane == 0)
-            {
-                __hip_atomic_store(&sflg[2], J + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-#pragma unroll
-            for (int I = J + 1; I < NB; I++)
-            {
-#pragma unroll
-                for (int Jc = I; Jc < NB; Jc++)
-                {
-#pragma unroll
-                    for (int t = 0; t < 16; t++)
-                    {
-                        Tt[I][Jc] = __builtin_amdgcn_mfma_f32_32x32x2f32(-A4[I][t], A4[Jc][t], Tt[I][Jc], 0, 0, 0);
-                    }
-                }
-            }
-        });
-    }
-    if (tid == 0)
-    {
-        sflg[0] = failed ? 1 : 0;
-        stamp(2);
-    }
-    T chk = (T)0;
-    if (tid >= 64 && tid < 128) // ---- wave 1: the inverse, one 32-column block behind
-    {
-        for (int e = lane; e < K * LD; e += 64)
-        {
-            S[e] = (T)0;
-        }
-        const int sq = a.textbook ? LD : 1, sc = a.textbook ? 1 : LD; // X[q][c] -> S[q*sq + c*sc]
-#pragma unroll
-        for (int I = 0; I < NB; I++)
-        {
-#pragma unroll
-            for (int J = 0; J <= I; J++)
-            {
-#pragma unroll
-                for (int r = 0; r < 16; r++)
-                {
-                    Tt[I][J][r] = (I == J && ((r & 3) + 8 * (r >> 2) + 4 * lh) == lj) ? (T)1 : (T)0;
-                }
-            }
-        }
-        static_for<0, NB>([&](auto Qt) {
-            constexpr int Q = decltype(Qt)::value;
-            while (__hip_atomic_load(&sflg[2], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= Q)
-            {
-                __builtin_amdgcn_s_sleep(2);
-            }
-            T X4[NB][16];
-#pragma unroll
-            for (int Jc = 0; Jc < NB; Jc++)
-            {
-#pragma unroll
-                for (int t = 0; t < 16; t++)
-                {
-                    X4[Jc][t] = (T)0;
-                }
-            }
-            T rsv[32], lqv[32];
-#pragma unroll
-            for (int qq = 0; qq < 32; qq++)
-            {
-                rsv[qq] = rd[32 * Q + qq];
-                lqv[qq] = Lm[(32 * Q + lj) + (32 * Q + qq) * LD];
-            }
-            static_for<0, 32>([&](auto qt) {
-                constexpr int qq = decltype(qt)::value;
-                constexpr int q  = 32 * Q + qq;
-                constexpr int rg = (qq & 3) + 4 * (qq >> 3), hf = (qq >> 2) & 1;
-                const bool on = (lh == hf);
-                const T    rs = rsv[qq];
-                const T    lq_ = on ? lqv[qq] : (T)0;
-                T          xv[NB];
-#pragma unroll
-                for (int Jc = 0; Jc <= Q; Jc++)
-                {
-                    xv[Jc] = on ? Tt[Q][Jc][rg] * rs : (T)0; // X[q][32 Jc + lj]
-                    chk    = __builtin_fmaf(xv[Jc], (T)0, chk);
-                    if (on)
-                    {
-                        S[q * sq + (32 * Jc + lj) * sc] = xv[Jc];
-                    }
-                    X4[Jc][rg] += xv[Jc];
-                }
-                if (qq < 31)
-                {
-#pragma unroll
-                    for (int Jc = 0; Jc <= Q; Jc++)
-                    {
-                        Tt[Q][Jc] = __builtin_amdgcn_mfma_f32_32x32x2f32(-lq_, xv[Jc], Tt[Q][Jc], 0, 0, 0);
-                    }
-                }
-            });
-#pragma unroll
-            for (int I = Q + 1; I < NB; I++)
-            {
-#pragma unroll
-                for (int t = 0; t < 16; t++)
-                {
-                    // group t = the two columns whose row register is t: qq = (t&3) + 8 (t>>2) + 4 lh
-                    const T li = Lm[(32 * I + lj) + (32 * Q + (t & 3) + 8 * (t >> 2) + 4 * lh) * LD];
-#pragma unroll
-                    for (int Jc = 0; Jc <= Q; Jc++)
-                    {
-                        Tt[I][Jc] = __builtin_amdgcn_mfma_f32_32x32x2f32(-li, X4[Jc][t], Tt[I][Jc], 0, 0, 0);
-                    }
-                }
-            }
-        });
-        const bool bad = (__ballot(!(chk == chk)) != 0ull);
-        if (lane == 0)
-        {
-            sflg[1] = bad ? 1 : 0;
-        }
-    }
-    __syncthreads(); // #C
-    stamp(3);
-    stamp(8);
-    if (tid == 0 && sflg[0])
-    {
-        sflg[1] = 0;
-    }
-    __syncthreads();
-    const bool zero = (sflg[0] | sflg[1]) != 0;
-    if (zero)
-    {
-        for (int e = tid; e < K * LD; e += 256)
-        {
-            S[e] = (T)0;
-        }
-        __syncthreads();
-    }
-    // outputs: G^T (what the gain kernel reads), t = G^T V, u = G t, M
-#pragma unroll 8
-    for (int e = tid; e < K * K; e += 256)
-    {
-        const int c = e & (K - 1), r = e / K;
-        if (r < k && c < k)
-        {
-            a.dGt[c + r * k] = S[r + c * LD];
-        }
-    }
-    stamp(9);
-    for (int vec = 0; vec < 4; vec++) // (K = 128: two outputs per thread pair: 256 threads = 128 outputs x 2 parts)
-    {
-        const int o = tid >> 1, part = tid & 1;
-        const T*  vin = (vec == 0) ? V : &t4[vec * K];
-        T         s1 = (T)0;
-        if (o < K)
-        {
-#pragma unroll 16
-            for (int r = part; r < K; r += 2)
-            {
-                s1 += S[r + o * LD] * vin[r];
-            }
-        }
-        s1 += __shfl_xor(s1, 1);
-        __syncthreads();
-        if (part == 0 && o < K)
-        {
-            t4[vec * K + o] = (o < k) ? s1 : (T)0;
-            if (vec == 0 && o < k)
-            {
-                a.dt[o] = s1;
-            }
-        }
-        __syncthreads();
-        T s2 = (T)0;
-        if (o < K)
-        {
-#pragma unroll 16
-            for (int c = part; c < K; c += 2)
-            {
-                s2 += S[o + c * LD] * t4[vec * K + c];
-            }
-        }
-        s2 += __shfl_xor(s2, 1);
-        if (part == 0 && o < k)
-        {
-            if (vec == 0)
-            {
-                du[o] = s2;
-            }
-            else if (a.dM != nullptr)
-            {
-                a.dM[(vec - 1) * k + o] = s2;
-            }
-        }
-    }
-    stamp(4);
-    if (tid == 0)
-    {
-        const int code = (sflg[0] ? kFlagLltFailed : 0) | (sflg[1] ? kFlagZeroed : 0);
-        a.flags[1]     = code;
-        if (code)
-        {
-            atomicOr(&a.flags[0], code);
-        }
-    }
+#include "ekf_factor_mfma_big_f32_body.inc" // (shared with ekf_counted_kernels.hpp)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1849,159 +1175,7 @@ __global__ void __launch_bounds__(64) ekf_panel_mfma_f32(const float* __restrict
                                                           const float* __restrict__ Mv = nullptr,
                                                           float* __restrict__ wv_out = nullptr)
 {
-    // (P here is the pose stripe Pv, see p_get: the predicted stripe and pose block are committed there)
-    // Mv != nullptr (gain, XUPD): the factor kernel supplied M = G G^T PHT[0:3,:]^T (3 x kq): the column-tile-0
-    // workgroups also apply the pose-stripe share of slam.h:260, Pv[:, c] -= PHT * M[c, :]^T (= W1 * W1[c, :]^T), and the
-    // pose rows of the W1 panel are written as ZERO (saved to wv_out, 3 x nc, for the debug entry point): the pending-
-    // panel algebra never touches the stripe.
-    // pred != nullptr (gain, XUPD): a predict() was applied on the fly by the gather and factor kernels (PredictArgs);
-    // this kernel commits it: the column-tile-0 workgroups write the predicted stripe and Pvv into P and add the state
-    // correction to the PREDICTED pose.  pred = {g02, g12, pose (3), Pvv (9)} from the factor kernel.
-    // one wave per workgroup, one 32x32 MFMA tile per wave: grid = (n_pad/32 row tiles, ceil(nc/32) column tiles).
-    // Small tiles on purpose: the kernel is a latency chain (load -> MFMA -> store), so it wants many waves.
-    const int  lane = threadIdx.x;
-    const int  lj   = lane & 31;
-    const int  lh   = lane >> 5;
-    const int  row0 = blockIdx.x * 32;
-    const int  c0   = blockIdx.y * 32;
-    const bool cok  = (c0 + lj) < nc;
-    const int  cc   = cok ? (c0 + lj) : (nc - 1); // clamped: loads are unconditional, the VALUE is selected
-    const bool dox  = XUPD && (blockIdx.y == 0);
-    f32x16     acc  = {0};
-    float      xs   = 0.f, xm0 = 0.f, xm1 = 0.f, xm2 = 0.f;
-    const float* pa = A + row0 + lj;
-    // SUB: the old values of the output tile are requested first, so that their latency (the tile was written by
-    // another kernel on other XCDs a moment ago) hides behind the operand loads and the MFMAs
-    float oldv[16];
-    if (SUB)
-    {
-#pragma unroll
-        for (int r = 0; r < 16; r++)
-        {
-            const int col = c0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            oldv[r]       = OUT[(size_t)(col < nc ? col : nc - 1) * ldo + row0 + lj];
-        }
-    }
-    constexpr int NP = 32; // k-pairs per trip: every load of the trip is issued before its first MFMA
-    for (int qb = 0; qb < kq; qb += 2 * NP)
-    {
-        float b[NP], g[NP], uq[NP];
-#pragma unroll
-        for (int t = 0; t < NP; t++)
-        {
-            const int q  = qb + 2 * t + lh;
-            const int qc = (q < kq) ? q : (kq - 1);
-            b[t]         = pa[(size_t)qc * lda];
-            g[t]         = Bt[(size_t)qc * ldb + cc];
-            uq[t]        = XUPD ? u[qc] : 0.f;
-        }
-#pragma unroll
-        for (int t = 0; t < NP; t++)
-        {
-            const int   q  = qb + 2 * t + lh;
-            const bool  ok = q < kq;
-            const float gg = (ok && cok) ? g[t] : 0.f;
-            const float bb = ok ? b[t] : 0.f;
-            acc            = __builtin_amdgcn_mfma_f32_32x32x2f32(gg, bb, acc, 0, 0, 0);
-            xs += bb * uq[t];
-        }
-        if (XUPD && dox && Mv != nullptr) // (workgroup-uniform)
-        {
-#pragma unroll
-            for (int t = 0; t < NP; t++)
-            {
-                const int   q  = qb + 2 * t + lh;
-                const int   qc = (q < kq) ? q : (kq - 1);
-                const float bb = (q < kq) ? b[t] : 0.f;
-                xm0 += bb * Mv[qc];
-                xm1 += bb * Mv[kq + qc];
-                xm2 += bb * Mv[2 * kq + qc];
-            }
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; r++)
-    {
-        const int col = c0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (col < nc)
-        {
-            float* o = OUT + (size_t)col * ldo + row0 + lj;
-            if (!SUB && Mv != nullptr && row0 + lj < 3) // pose rows of the W1 panel: kept aside, stored as zero
-            {
-                wv_out[(size_t)(row0 + lj) * nc + col] = acc[r];
-                *o                                     = 0.f;
-            }
-            else
-            {
-                *o = SUB ? (oldv[r] - acc[r]) : acc[r];
-            }
-        }
-    }
-    if (dox)
-    {
-        xs += __shfl_xor(xs, 32);
-        xm0 += __shfl_xor(xm0, 32);
-        xm1 += __shfl_xor(xm1, 32);
-        xm2 += __shfl_xor(xm2, 32);
-        const int r = row0 + lj;
-        if (lh == 0 && r < n)
-        {
-            X[r] = ((pred != nullptr && r < 3) ? pred[2 + r] : X[r]) + xs;
-            if (pred != nullptr || Mv != nullptr)
-            {
-                // row r of the pose stripe: [predicted (EKF.cpp:439-443)] then [downdated]
-                float a0 = P[(size_t)0 * ldp + r], a1 = P[(size_t)1 * ldp + r], a2 = P[(size_t)2 * ldp + r];
-                if (pred != nullptr)
-                {
-                    if (r >= 3)
-                    {
-                        if (r - 3 < pred_w)
-                        {
-                            float o0, o1, o2;
-                            predict_stripe_col<float>(pred[0], pred[1], a0, a1, a2, &o0, &o1, &o2);
-                            a0 = o0;
-                            a1 = o1;
-                            a2 = o2;
-                        }
-                    }
-                    else // the pose block: predicted Pvv, row r
-                    {
-                        a0 = pred[5 + r];
-                        a1 = pred[5 + r + 3];
-                        a2 = pred[5 + r + 6];
-                    }
-                }
-                if (r >= 3)
-                {
-                    P[(size_t)0 * ldp + r] = a0 - xm0;
-                    P[(size_t)1 * ldp + r] = a1 - xm1;
-                    P[(size_t)2 * ldp + r] = a2 - xm2;
-                }
-                else
-                {
-                    // the 3 x 3 pose block: the increment W1 W1^T is symmetric bit for bit in the reference's product;
-                    // here (r, c) and (c, r) come from different dot products, so the thread of the larger index
-                    // applies ITS increment to both
-                    const float av[3] = {a0, a1, a2};
-                    const float dv[3] = {xm0, xm1, xm2};
-#pragma unroll
-                    for (int c = 0; c < 3; c++)
-                    {
-                        if (c == r)
-                        {
-                            P[(size_t)c * ldp + r] = av[c] - dv[c];
-                        }
-                        else if (c < r)
-                        {
-                            const float bcr = (pred != nullptr) ? pred[5 + c + 3 * r] : P[(size_t)r * ldp + c]; // (c, r)
-                            P[(size_t)c * ldp + r] = av[c] - dv[c];
-                            P[(size_t)r * ldp + c] = bcr - dv[c];
-                        }
-                    }
-                }
-            }
-        }
-    }
+#include "ekf_panel_mfma_f32_body.inc" // (shared with ekf_counted_kernels.hpp)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2021,150 +1195,7 @@ __global__ void __launch_bounds__(64) ekf_panel_mfma_f64(const double* __restric
                                                           double* __restrict__ wv_out = nullptr,
                                                           const double* __restrict__ pred = nullptr, int pred_w = 0)
 {
-    // pred != nullptr (gain, XUPD): commits a predict() that the gather and factor kernels applied on the fly, exactly as
-    // ekf_panel_mfma_f32 does: pred = {g02, g12, pose (3), Pvv (9)} from the gather kernel.
-    const int  lane = threadIdx.x;
-    const int  lj   = lane & 15;
-    const int  lq   = lane >> 4;
-    const int  row0 = blockIdx.x * 16;
-    const int  c0   = blockIdx.y * 16;
-    const bool cok  = (c0 + lj) < nc;
-    const int  cc   = cok ? (c0 + lj) : (nc - 1);
-    const bool dox  = XUPD && (blockIdx.y == 0);
-    f64x4      acc  = {0.0, 0.0, 0.0, 0.0};
-    double     xs = 0.0, xm0 = 0.0, xm1 = 0.0, xm2 = 0.0;
-    const double* pa = A + row0 + lj;
-    double oldv[4];
-    if (SUB)
-    {
-#pragma unroll
-        for (int g = 0; g < 4; g++)
-        {
-            const int col = c0 + lq + 4 * g;
-            oldv[g]       = OUT[(size_t)(col < nc ? col : nc - 1) * ldo + row0 + lj];
-        }
-    }
-    constexpr int NQ = 16; // k-quads per trip: every load of the trip is issued before its first MFMA
-    for (int qb = 0; qb < kq; qb += 4 * NQ)
-    {
-        double b[NQ], g[NQ], uq[NQ], m0[NQ], m1[NQ], m2[NQ];
-#pragma unroll
-        for (int t = 0; t < NQ; t++)
-        {
-            const int q  = qb + 4 * t + lq;
-            const int qc = (q < kq) ? q : (kq - 1);
-            b[t]         = pa[(size_t)qc * lda];
-            g[t]         = Bt[(size_t)qc * ldb + cc];
-            uq[t]        = (XUPD && dox) ? u[qc] : 0.0;
-            if (XUPD && dox && Mv != nullptr)
-            {
-                m0[t] = Mv[qc];
-                m1[t] = Mv[kq + qc];
-                m2[t] = Mv[2 * kq + qc];
-            }
-            else
-            {
-                m0[t] = m1[t] = m2[t] = 0.0;
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NQ; t++)
-        {
-            const int    q  = qb + 4 * t + lq;
-            const bool   ok = q < kq;
-            const double gg = (ok && cok) ? g[t] : 0.0;
-            const double bb = ok ? b[t] : 0.0;
-            acc             = __builtin_amdgcn_mfma_f64_16x16x4f64(gg, bb, acc, 0, 0, 0);
-            xs += bb * uq[t];
-            xm0 += bb * m0[t];
-            xm1 += bb * m1[t];
-            xm2 += bb * m2[t];
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < 4; g++)
-    {
-        const int col = c0 + lq + 4 * g;
-        if (col < nc)
-        {
-            double* o = OUT + (size_t)col * ldo + row0 + lj;
-            if (!SUB && Mv != nullptr && row0 + lj < 3) // pose rows of the W1 panel: kept aside, stored as zero
-            {
-                wv_out[(size_t)(row0 + lj) * nc + col] = acc[g];
-                *o                                     = 0.0;
-            }
-            else
-            {
-                *o = SUB ? (oldv[g] - acc[g]) : acc[g];
-            }
-        }
-    }
-    if (dox)
-    {
-        xs += __shfl_xor(xs, 16);
-        xs += __shfl_xor(xs, 32);
-        xm0 += __shfl_xor(xm0, 16);
-        xm0 += __shfl_xor(xm0, 32);
-        xm1 += __shfl_xor(xm1, 16);
-        xm1 += __shfl_xor(xm1, 32);
-        xm2 += __shfl_xor(xm2, 16);
-        xm2 += __shfl_xor(xm2, 32);
-        const int r = row0 + lj;
-        if (lq == 0 && r < n)
-        {
-            X[r] = ((pred != nullptr && r < 3) ? pred[2 + r] : X[r]) + xs;
-            if (pred != nullptr || Mv != nullptr)
-            {
-                // row r of the pose stripe: [predicted (EKF.cpp:439-443)] then [downdated] (xm* are zero without Mv)
-                double a0 = Pv[(size_t)0 * ldp + r], a1 = Pv[(size_t)1 * ldp + r], a2 = Pv[(size_t)2 * ldp + r];
-                if (pred != nullptr)
-                {
-                    if (r >= 3)
-                    {
-                        if (r - 3 < pred_w)
-                        {
-                            double o0, o1, o2;
-                            predict_stripe_col<double>(pred[0], pred[1], a0, a1, a2, &o0, &o1, &o2);
-                            a0 = o0;
-                            a1 = o1;
-                            a2 = o2;
-                        }
-                    }
-                    else // the pose block: predicted Pvv, row r
-                    {
-                        a0 = pred[5 + r];
-                        a1 = pred[5 + r + 3];
-                        a2 = pred[5 + r + 6];
-                    }
-                }
-                if (r >= 3)
-                {
-                    Pv[(size_t)0 * ldp + r] = a0 - xm0;
-                    Pv[(size_t)1 * ldp + r] = a1 - xm1;
-                    Pv[(size_t)2 * ldp + r] = a2 - xm2;
-                }
-                else // the 3 x 3 pose block: one increment for (r, c) and (c, r) (see ekf_panel_mfma_f32)
-                {
-                    const double av[3] = {a0, a1, a2};
-                    const double dv[3] = {xm0, xm1, xm2};
-#pragma unroll
-                    for (int c = 0; c < 3; c++)
-                    {
-                        if (c == r)
-                        {
-                            Pv[(size_t)c * ldp + r] = av[c] - dv[c];
-                        }
-                        else if (c < r)
-                        {
-                            const double bcr = (pred != nullptr) ? pred[5 + c + 3 * r] : Pv[(size_t)r * ldp + c]; // (c, r)
-                            Pv[(size_t)c * ldp + r] = av[c] - dv[c];
-                            Pv[(size_t)r * ldp + c] = bcr - dv[c];
-                        }
-                    }
-                }
-            }
-        }
-    }
+#include "ekf_panel_mfma_f64_body.inc" // (shared with ekf_counted_kernels.hpp)
 }
 
 // ------------------------------------------------------------------------------------------------

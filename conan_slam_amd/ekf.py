@@ -308,6 +308,46 @@ class EKF:
         check(self._L.cslam_ekf_association_device_ptrs(self._h, *(C.byref(q) for q in p)))
         return tuple(q.value or 0 for q in p)
 
+    def update_counted(self, dZ_ptr: int, m_cap: int, R, d_idf_ptr: int, d_count_ptr: int):
+        """update_device(dZ, c, R, d_idf, batch=True) with c = clamp(*d_count, 0, m_cap) read on the device in stream order
+        (cslam_ekf_update_counted): the host never learns c and never waits.  Raw device pointers; entries c .. m_cap-1 of
+        dZ / d_idf are never read.  m_cap <= 64 (f32) or 32 (f64), asynchronous mode only."""
+        R = self._mat22(R)
+        check(self._L.cslam_ekf_update_counted(self._h, C.c_void_p(dZ_ptr), C.c_int(m_cap), _vp(R), C.c_void_p(d_idf_ptr),
+                                               C.c_void_p(d_count_ptr), C.c_int(1)))
+
+    def associate_deferred_async(self, Z, R, gate1, gate2):
+        """associate_deferred() without the wait (cslam_ekf_associate_deferred_async): Z is consumed before the call returns,
+        the answer is handed out by association_wait(), and association_device_ptrs() may be used at once on the stream."""
+        Z = np.asarray(Z, dtype=self.dtype, order="F").reshape(2, -1, order="F")
+        R = np.asarray(R, dtype=self.dtype, order="F")
+        self._assoc_m = m = Z.shape[1]
+        check(self._L.cslam_ekf_associate_deferred_async(self._h, _vp(Z) if m else None, C.c_int(m), _vp(R),
+                                                         C.c_double(float(gate1)), C.c_double(float(gate2))))
+
+    def association_wait(self, with_counts: bool = False):
+        """The answer of the outstanding associate_deferred_async() call: (idf[m], kind[m]), and with_counts also counts[3]
+        (cslam_ekf_association_wait).  Waits for the association only, not for work enqueued behind it."""
+        m = getattr(self, "_assoc_m", 0)
+        idf = np.zeros(max(m, 1), dtype=np.int32)
+        kind = np.zeros(max(m, 1), dtype=np.int32)
+        counts = np.zeros(3, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        check(self._L.cslam_ekf_association_wait(self._h, idf.ctypes.data_as(ip), kind.ctypes.data_as(ip),
+                                                 counts.ctypes.data_as(ip)))
+        return (idf[:m], kind[:m], counts) if with_counts else (idf[:m], kind[:m])
+
+    def associate_update_counted(self, Z, R, gate1, gate2):
+        """One observation step with no host round trip between association and update: associate_deferred_async(), then
+        update_counted() on the device lists with m_cap = m (the count mf is read on the device), then association_wait().
+        -> (idf[m], kind[m], counts[3])."""
+        Z = np.asarray(Z, dtype=self.dtype, order="F").reshape(2, -1, order="F")
+        self.associate_deferred_async(Z, R, gate1, gate2)
+        if Z.shape[1]:
+            dZF, d_idf, _, d_counts = self.association_device_ptrs()
+            self.update_counted(dZF, Z.shape[1], R, d_idf, d_counts)
+        return self.association_wait(with_counts=True)
+
     # reference-style aliases
     observeHeading = observe_heading
     dataAssociate = data_associate

@@ -50,6 +50,7 @@ extern "C" {
                                    clamped it (no out-of-bounds access), the update used the clamped index           */
 #define CSLAM_FACTOR_HEADING_SKIPPED 32 /* batched engine: a heading step met S = P22 + R <= 0 or non-finite (an
                                           indefinite P) and was skipped for that instance (cslam_ekf_batch_observe_heading) */
+#define CSLAM_FACTOR_COUNT_CLAMPED 64 /* cslam_ekf_update_counted: *d_count was outside 0..m_cap and was clamped */
 
 /* ---- precision ---- */
 #define CSLAM_F32 0 /* the reference's precision (Eigen::MatrixXf everywhere)                          */
@@ -187,6 +188,41 @@ int cslam_ekf_associate_deferred(cslam_ekf_t h, const void* Z, int m, const void
  * it on the handle's chain stream.  Before any such call: CSLAM_ERR_BAD_ARG. */
 int cslam_ekf_association_device_ptrs(cslam_ekf_t h, const void** dZF, const int** d_idf, const void** dZN,
                                       const int** d_counts);
+
+/* cslam_ekf_associate_deferred without the wait (Slam::dataAssociate, EKF.cpp:235-326): the same argument checks, the
+ * same launch of queued work, the same kernels and the same single copy of counts / idf / kind into pinned host memory;
+ * then an event is recorded on the chain stream and the call returns.  Z is consumed before it returns.  The device
+ * lists (cslam_ekf_association_device_ptrs) may be handed to cslam_ekf_update_counted at once: the split the reference
+ * returns (slam.h:482-487) is read there in stream order.  m = 0 launches nothing; its cslam_ekf_association_wait
+ * returns counts 0.  Growing the lists for a larger m synchronises the chain stream, as the synchronous call does. */
+int cslam_ekf_associate_deferred_async(cslam_ekf_t h, const void* Z, int m, const void* R, double gate1, double gate2);
+
+/* Waits for the event of the outstanding cslam_ekf_associate_deferred_async call and hands out idf_out[m], kind_out[m],
+ * counts_out[3] = {mf, mn, dropped} (any of the three may be NULL).  It waits for the association only, not for work
+ * enqueued behind it.  CSLAM_ERR_BAD_ARG when no asynchronous call is outstanding: each call is waited for once, and a
+ * later associate call on the handle, synchronous or asynchronous, discards the outstanding results. */
+int cslam_ekf_association_wait(cslam_ekf_t h, int* idf_out, int* kind_out, int* counts_out /* [3]: mf, mn, dropped */);
+
+/* Slam::update with batch = 1 (slam.h:938-943, batchUpdate EKF.cpp:93-129) for the first c = *d_count observations of
+ * dZ / d_idf, where d_count points to ONE int in device memory that every kernel of the call reads in stream order --
+ * for example d_counts of cslam_ekf_association_device_ptrs, whose first entry is the row count mf of the ZF the
+ * reference splits off (slam.h:482-487).  The result is that of cslam_ekf_update_device(h, dZ, c, R, d_idf, 1); the
+ * call never waits for the device and copies nothing from it, so the host need not know c.
+ *   dZ: 2 x m_cap scalars, column-major; d_idf: m_cap ints; only the first c entries of each are read.  Entries
+ *   c .. m_cap-1 may hold anything (NaN, 0, negative or out-of-range ids): they influence nothing and never raise
+ *   CSLAM_FACTOR_BAD_IDF.  Lifetime of dZ / d_idf / d_count: as for cslam_ekf_update_device.
+ *   A count outside 0..m_cap is clamped into it and CSLAM_FACTOR_COUNT_CLAMPED is raised (cslam_ekf_factor_status).
+ *   c = 0 changes nothing (a held predict has still been applied).
+ * Accepted: 1 <= m_cap <= 64 (f32) or 32 (f64), the ranges of the tuned factor and gain kernels; m_cap = 0 returns
+ * CSLAM_OK and does nothing.  A larger m_cap, m_cap < 0, batch = 0, sync_mode = 1, two-stream mode (CSLAM_PIPELINE=1) or
+ * a NULL dZ / R / d_idf / d_count returns CSLAM_ERR_BAD_ARG and changes nothing.
+ * The host plans for m_cap: 2 m_cap pending columns are booked under the deferral and flush rules of
+ * cslam_ekf_update_device with m = m_cap, of which the columns beyond 2c are exact zeros.  Queued work (a held predict,
+ * the pose queue, a queued look-ahead update as a window of one) is launched first; the counted update itself never
+ * joins a look-ahead window.  cslam_ekf_debug_last_update returns CSLAM_ERR_BAD_ARG after a counted call (its k is
+ * known on the device only). */
+int cslam_ekf_update_counted(cslam_ekf_t h, const void* dZ, int m_cap, const void* R, const int* d_idf, const int* d_count,
+                             int batch);
 
 /* Deferred downdates.  slam.h:260 (P = P - W1*W1^T) is linear in the W1 panels, so the engine may keep
  * P = Ps - Wp*Wp^T with up to max_pending_columns columns of not-yet-applied panels and apply them in ONE

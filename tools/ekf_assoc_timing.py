@@ -7,14 +7,17 @@ observations of mapped landmarks per step.
     (a) predict + associate          + update(batch) with the association's own host lists
     (b) predict + associate_deferred + update_device from association_device_ptrs()
     (c) predict + update_device with known correspondences (no association)
+    (d) predict + associate_deferred_async + update_counted (the count mf read on the device) + association_wait:
+        no host round trip between the association's resolve kernel and the update's gather kernel
 
-(a) and (b) are alternated --rounds times on fresh handles; every run is timed with events on the handle's chain stream
+(a) and (b) -- with --pair bd: (b) and (d) -- are alternated --rounds times on fresh handles; every run is timed with events on the handle's chain stream
 around --steps steps after --warmup steps, and ends in a synchronise.  Prints one JSON line per run and a summary line.
 For the device time of ekf_assoc_pair_kernel run one loop under the profiler,
 `rocprofv3 --kernel-trace --stats -- python tools/ekf_assoc_timing.py --only b --rounds 1`, and set it against
 `pair_bytes`: the 2 nf kp panel scalars and 25 nf entries of P the kernel has to read.
 
     python tools/ekf_assoc_timing.py [--landmarks 5000] [--dtype f32] [--m 32] [--steps 200] [--warmup 20] [--rounds 5]
+                                     [--pair ab|bd] [--only a|b|c|d]
 """
 import argparse
 import json
@@ -84,6 +87,9 @@ def run(loop, N, dtype, m, steps, warmup, seed=1):
             dZF, d_idf, _, _ = e.association_device_ptrs()
             e.update_device(dZF, int(counts[0]), R, d_idf, True)
             associated += int(counts[0]) if t >= warmup else 0
+        elif loop == "d":
+            idf, kind, counts = e.associate_update_counted(Z, R, *GATES)
+            associated += int(counts[0]) if t >= warmup else 0
         else:
             dZ, dI = dev[t]
             e.update_device(dZ.data_ptr(), m, R, dI.data_ptr(), True)
@@ -106,12 +112,13 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--only", choices=["a", "b", "c"], default=None)
+    ap.add_argument("--only", choices=["a", "b", "c", "d"], default=None)
+    ap.add_argument("--pair", choices=["ab", "bd"], default="ab", help="the two loops that are alternated")
     args = ap.parse_args()
     dtype = np.float32 if args.dtype == "f32" else np.float64
-    res = {"a": [], "b": [], "c": []}
+    res = {"a": [], "b": [], "c": [], "d": []}
     for r in range(args.rounds):
-        for loop in ([args.only] if args.only else ["a", "b"] + (["c"] if r in (0, args.rounds - 1) else [])):
+        for loop in ([args.only] if args.only else list(args.pair) + (["c"] if r in (0, args.rounds - 1) else [])):
             out = run(loop, args.landmarks, dtype, args.m, args.steps, args.warmup)
             res[loop].append(out["steps_per_s"])
             print(json.dumps(out), flush=True)
@@ -125,6 +132,10 @@ def main():
         a, b = res["a"], res["b"]
         summary["every_b_faster_than_every_a"] = bool(min(b) > max(a))
         summary["median_gap_over_range_of_a"] = round((np.median(b) - np.median(a)) / max(max(a) - min(a), 1e-9), 2)
+    if res["b"] and res["d"]:
+        b, d = res["b"], res["d"]
+        summary["every_d_faster_than_every_b"] = bool(min(d) > max(b))
+        summary["median_gap_over_range_of_b"] = round((np.median(d) - np.median(b)) / max(max(b) - min(b), 1e-9), 2)
     if res["b"] and res["c"]:
         summary["b_over_c"] = round(float(np.median(res["b"]) / np.median(res["c"])), 3)
     print(json.dumps(summary), flush=True)
