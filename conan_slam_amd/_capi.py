@@ -172,6 +172,16 @@ _PROTOTYPES.update({
 EKF_COUNTED_SYMBOLS = ("cslam_ekf_update_counted", "cslam_ekf_associate_deferred_async", "cslam_ekf_association_wait")
 
 
+# Slam::augment with the new features read from device memory, one launch per EKF_AUGMENT_CHUNK features (test/main.cpp:
+# 188-189, slam.h:190-191, EKF.cpp:9-91), and the count of augment kernel launches of a handle.
+EKF_AUGMENT_CHUNK = 64  # kAugChunk of csrc/ekf_augment_kernels.hpp
+_PROTOTYPES.update({
+    "cslam_ekf_augment_device": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "cslam_ekf_augment_launches": [C.c_void_p, C.POINTER(C.c_longlong)],
+})
+EKF_AUGMENT_DEVICE_SYMBOLS = ("cslam_ekf_augment_device", "cslam_ekf_augment_launches")
+
+
 # The Monte-Carlo driver over single handles: one host thread and one stream pair per handle (ekf.run_many).  The handle
 # and pointer tables and the controls travel as plain addresses.
 _PROTOTYPES.update({

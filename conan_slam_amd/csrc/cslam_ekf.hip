@@ -30,6 +30,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_kernels_fast.hpp"
 #include "ekf_assoc_deferred_kernels.hpp"
+#include "ekf_augment_kernels.hpp"
 #include "ekf_counted_kernels.hpp"
 #include "ekf_landmark_kernels.hpp"
 #include "ekf_lookahead.hpp"
@@ -151,6 +152,7 @@ struct EkfBase
     long long   la_windows = 0;     // look-ahead windows launched (cslam_ekf_lookahead_windows)
     long long   stage_launches = 0; // ekf_stage_obs_kernel launches (cslam_ekf_stage_launches)
     long long   rows_launches = 0;  // ekf_la_rows_kernel launches (cslam_ekf_rows_launches)
+    long long   augment_launches = 0; // ekf_augment_kernel + ekf_augment_many_kernel launches (cslam_ekf_augment_launches)
 
     virtual int init()                                                                        = 0;
     virtual int set_state(const void* X, int n, const void* P, int ldp)                        = 0;
@@ -168,6 +170,7 @@ struct EkfBase
     virtual int predict(double v, double swa, const void* Q, double wb, double dt)             = 0;
     virtual int update(const void* Z, int m, const void* R, const int* idf, int batch, bool on_device) = 0;
     virtual int augment(const void* Z, int q, const void* R)                                   = 0;
+    virtual int augment_device(const void* dZ, int q, const void* R)                           = 0;
     virtual int observe_heading(double phi, int use)                                           = 0;
     virtual int associate(const void* Z, int m, const void* R, double g1, double g2, int* idf_out, int* kind) = 0;
     virtual int update_counted(const void* dZ, int m_cap, const void* R, const int* d_idf, const int* d_count,
@@ -2747,7 +2750,44 @@ struct Ekf : EkfBase
             hipLaunchKernelGGL(ekf_augment_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, dX.get(), dP.get(),
                                dPv.get(), ldp, n, Z[2 * i], Z[2 * i + 1], R[0], R[1], R[2], R[3], opt.lower);
             CSLAM_HIP_TRY(hipGetLastError());
+            augment_launches++;
             n += 2;
+        }
+        return CSLAM_OK;
+    }
+
+    // The same with Z in device memory, read in stream order: kAugChunk features per launch (ekf_augment_kernels.hpp).
+    // A later chunk finds the rows of the earlier ones in the stripe, as a later call would.
+    int augment_device(const void* dZv, int q, const void* Rv) override
+    {
+        if (q < 0 || !Rv || (q > 0 && !dZv))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "augment_device: bad arguments (q=%d)", q);
+        }
+        if (n + 2 * q > ncap)
+        {
+            return fail(CSLAM_ERR_CAPACITY, "augment_device: %d features would exceed max_landmarks=%d", (n - 3) / 2 + q,
+                        nmax);
+        }
+        int rc = use_device();
+        if (rc)
+        {
+            return rc;
+        }
+        if (q > 0 && (rc = wait_pgemm())) // (as augment)
+        {
+            return rc;
+        }
+        const T* dZ = static_cast<const T*>(dZv);
+        const T* R  = static_cast<const T*>(Rv);
+        for (int i = 0; i < q; i += kAugChunk)
+        {
+            const int qc = std::min(q - i, kAugChunk);
+            hipLaunchKernelGGL(ekf_augment_many_kernel<T>, dim3((n + 3 * qc + 255) / 256), dim3(256), 0, stream, dX.get(),
+                               dP.get(), dPv.get(), ldp, n, dZ + 2 * i, qc, R[0], R[1], R[2], R[3], opt.lower);
+            CSLAM_HIP_TRY(hipGetLastError());
+            augment_launches++;
+            n += 2 * qc;
         }
         return CSLAM_OK;
     }
@@ -3497,6 +3537,36 @@ int cslam_ekf_augment(cslam_ekf_t h, const void* Z, int q, const void* R)
         return rc;
     }
     return B(h)->augment(Z, q, R);
+}
+
+int cslam_ekf_augment_device(cslam_ekf_t h, const void* dZ, int q, const void* R)
+{
+    CSLAM_NEED(h);
+    if (q < 0 || !R || (q > 0 && !dZ)) // (before queued work is launched: on an error nothing changes)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "augment_device: bad arguments (q=%d)", q);
+    }
+    if (B(h)->n + 2 * q > B(h)->ncap)
+    {
+        return fail(CSLAM_ERR_CAPACITY, "augment_device: %d features would exceed max_landmarks=%d", (B(h)->n - 3) / 2 + q,
+                    B(h)->nmax);
+    }
+    if (int rc = B(h)->resolve_predict()) // (as cslam_ekf_augment, also for q = 0, which launches no augment kernel)
+    {
+        return rc;
+    }
+    return B(h)->augment_device(dZ, q, R);
+}
+
+int cslam_ekf_augment_launches(cslam_ekf_t h, long long* launches)
+{
+    CSLAM_NEED(h);
+    if (!launches)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "augment_launches: null");
+    }
+    *launches = B(h)->augment_launches;
+    return CSLAM_OK;
 }
 
 int cslam_ekf_associate(cslam_ekf_t h, const void* Z, int m, const void* R, double gate1, double gate2, int* idf_out,

@@ -348,6 +348,31 @@ class EKF:
             self.update_counted(dZF, Z.shape[1], R, d_idf, d_counts)
         return self.association_wait(with_counts=True)
 
+    def augment_device(self, dZ_ptr: int, q: int, R):
+        """augment() with Z (2 x q scalars, column-major, the handle's dtype) already in HBM (a raw device pointer): one
+        launch per 64 features instead of one per feature, the same bits (cslam_ekf_augment_device).  Entries beyond 2q
+        are never read; q stays a host value."""
+        R = self._mat22(R)
+        check(self._L.cslam_ekf_augment_device(self._h, C.c_void_p(dZ_ptr) if dZ_ptr else None, C.c_int(int(q)), _vp(R)))
+
+    def augment_launches(self) -> int:
+        """augment kernel launches of this handle, from augment() and augment_device() (cslam_ekf_augment_launches)"""
+        w = C.c_longlong(0)
+        check(self._L.cslam_ekf_augment_launches(self._h, C.byref(w)))
+        return w.value
+
+    def associate_update_augment(self, Z, R, gate1, gate2):
+        """One whole observation step of the reference's loop (test/main.cpp:180-189) from the device lists:
+        associate_deferred_async(), update_counted() on ZF / idf, association_wait() -- which waits for the association
+        only, the update runs behind it -- and then augment_device() on the ZN the association left in HBM, with the count
+        the wait returned.  Under REF_EXACT quirks nothing is augmented: the reference returns an empty ZN there
+        (EKF.cpp:307, see data_associate_deferred).  -> (idf[m], kind[m], counts[3])."""
+        idf, kind, counts = self.associate_update_counted(Z, R, gate1, gate2)
+        if counts[1] > 0 and self.quirks != Q_REF_EXACT:
+            dZN = self.association_device_ptrs()[2]
+            self.augment_device(dZN, int(counts[1]), R)
+        return idf, kind, counts
+
     # reference-style aliases
     observeHeading = observe_heading
     dataAssociate = data_associate

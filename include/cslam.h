@@ -146,6 +146,25 @@ int cslam_ekf_update_device(cslam_ekf_t h, const void* dZ, int m, const void* R,
  * Z: 2 x q scalars (host). Fails with CSLAM_ERR_CAPACITY beyond max_landmarks. */
 int cslam_ekf_augment(cslam_ekf_t h, const void* Z, int q, const void* R);
 
+/* Slam::augment (test/main.cpp:188-189, slam.h:190-191, EKF.cpp:9-26 / addOneNewFeature EKF.cpp:28-91) with the new
+ * features read from device memory: the result -- X, P and n, bit for bit -- is that of cslam_ekf_augment(h, Z, q, R)
+ * with Z the first 2q scalars of dZ.  dZ: 2 x q scalars (r, b) in the handle's dtype, column-major, in HBM; entries
+ * beyond 2q are never read.  R is a host pointer (4 scalars).  The q features are added by ONE kernel launch per 64
+ * features (a call with q <= 64 is exactly one launch), where cslam_ekf_augment launches once per feature.
+ * Queued work (a held predict, the pose queue, a queued look-ahead update) is launched first, as by cslam_ekf_augment;
+ * pending covariance columns stay pending, their rows for the new features are zero.
+ * q = 0 returns CSLAM_OK and launches no augment kernel.  q < 0, a NULL R, or a NULL dZ with q > 0 returns
+ * CSLAM_ERR_BAD_ARG; more than max_landmarks features in all returns CSLAM_ERR_CAPACITY; on either error nothing changes.
+ * Lifetime of dZ: as for cslam_ekf_update_device -- it is read by work this call enqueues on the chain stream, and
+ * nothing is held past the call.  The dZN of cslam_ekf_association_device_ptrs and of cslam_sim_device_ptrs may be passed
+ * directly, with the count the host learnt from cslam_ekf_association_wait / cslam_sim_associate_table.
+ * Works in every mode in which cslam_ekf_augment works. */
+int cslam_ekf_augment_device(cslam_ekf_t h, const void* dZ, int q, const void* R);
+
+/* Augment kernel launches of this handle so far, from cslam_ekf_augment (one per feature) and cslam_ekf_augment_device
+ * (one per 64 features): a host-side counter, like cslam_ekf_stage_launches. */
+int cslam_ekf_augment_launches(cslam_ekf_t h, long long* launches);
+
 /* Replaces Slam::observeHeading(X, P, phi, useHeading)  -- slam.h:788, EKF.cpp:328-352 with
  * josephUpdate slam.h:700-725.  With H = e_2^T the Joseph form equals P - p p^T / S (p = P[:,2], S = P22 + R) for a
  * symmetric P: the pose stripe is updated at once, the map block receives the rank-1 downdate as one more pending

@@ -12,6 +12,8 @@
 //   HipEKF::predict          slam.h:841-847   EKF.cpp:406-455        -> cslam_ekf_predict
 //   HipEKF::update           slam.h:938-943   EKF.cpp:481-496        -> cslam_ekf_update   (batchUpdate / singleUpdate too)
 //   HipEKF::augment          slam.h:190-191   EKF.cpp:9-26           -> cslam_ekf_augment  (addOneNewFeature too)
+//   HipEKF::augmentDevice / augmentAssociated   (the same Slam::augment, test/main.cpp:188-189, with the new features read
+//                            from device memory, one launch for all of them)  -> cslam_ekf_augment_device
 //   HipEKF::observeHeading   slam.h:788       EKF.cpp:328-352        -> cslam_ekf_observe_heading
 //   HipEKF::dataAssociate    slam.h:482-487   EKF.cpp:235-326        -> cslam_ekf_associate, or, after
 //                            setDeferredAssociation(true),              -> cslam_ekf_associate_deferred (nothing flushed)
@@ -127,6 +129,31 @@ class HipEKF : public EKF
     }
     using EKF::addOneNewFeature; // (the particle overload stays the reference's empty stub, EKF.h:22-24)
 
+    /// augment with Z (2 x q floats, column-major) already in device memory: all q features in one launch
+    /// (cslam_ekf_augment_device).  Plain forwarding: the engine holds the state of the last hot-path call, and the
+    /// caller's X grows at the next one (or at syncP).
+    void augmentDevice(const void* dZ, int q, const Eigen::MatrixXf& R)
+    {
+        report(cslam_ekf_augment_device(h_, dZ, q, R.data()), "HipEKF::augmentDevice");
+    }
+    /// after a dataAssociate under setDeferredAssociation(true): augment with the new-feature list ZN that call left on
+    /// the device, taking the count it returned (the ZN the reference's dataAssociate loses at EKF.cpp:307).  Each
+    /// association is consumed once; without one this does nothing.
+    void augmentAssociated(const Eigen::MatrixXf& R)
+    {
+        const void* dZN = nullptr;
+        const int   q   = associatedNew_;
+        associatedNew_  = 0;
+        if (q <= 0)
+        {
+            return;
+        }
+        report(cslam_ekf_association_device_ptrs(h_, nullptr, nullptr, &dZN, nullptr), "HipEKF::augmentAssociated");
+        augmentDevice(dZN, q, R);
+    }
+    /// new features the last deferred dataAssociate found and augmentAssociated has not consumed yet
+    int associatedNew() const { return associatedNew_; }
+
     void observeHeading(Eigen::VectorXf& X, Eigen::MatrixXf& P, const float& phi, bool useHeading = false) override
     {
         push(X, P);
@@ -141,10 +168,13 @@ class HipEKF : public EKF
         push(X, P);
         const int        m = static_cast<int>(Z.cols());
         std::vector<int> idf(static_cast<size_t>(m > 0 ? m : 1)), kind(static_cast<size_t>(m > 0 ? m : 1));
+        associatedNew_ = 0;
         if (deferredAssociation_)
         {
-            report(cslam_ekf_associate_deferred(h_, Z.data(), m, R.data(), gate1, gate2, idf.data(), kind.data(), nullptr),
+            int counts[3] = {0, 0, 0};
+            report(cslam_ekf_associate_deferred(h_, Z.data(), m, R.data(), gate1, gate2, idf.data(), kind.data(), counts),
                    "HipEKF::dataAssociate");
+            associatedNew_ = counts[1]; // (left on the device as ZN: augmentAssociated)
         }
         else
         {
@@ -245,6 +275,7 @@ class HipEKF : public EKF
     cslam_ekf_t h_        = nullptr;
     bool        uploaded_ = false;
     bool        deferredAssociation_ = false;
+    int         associatedNew_ = 0;
 
     static void report(int rc, const char* who)
     {
