@@ -116,6 +116,20 @@ PF_DRAW_SYMBOLS = ("cslam_pf_seed_draws", "cslam_pf_get_draws", "cslam_pf_sample
                    "cslam_pf_resample_sharded_drawn", "cslam_pf_observation_step_drawn", "cslam_pf_stage_copies")
 PF_DRAW_OBS_MAX = 32  # kPfDrawObsMax of csrc/pf_draw_kernels.hpp: observations that travel as kernel arguments
 
+# The scan that observes only new features (test/main.cpp:314-328): sample every pose from its own Gaussian
+# (slam.h:753-764, 413-436), zero Pv, add the features at the sampled pose (PF.cpp:9-60), optionally behind the predict
+# (PF.cpp:419-471).
+_PROTOTYPES.update({
+    "cslam_pf_sample_pose": [C.c_void_p, C.c_void_p],
+    "cslam_pf_sample_pose_drawn": [C.c_void_p, C.c_longlong],
+    "cslam_pf_new_feature_step": [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                  C.c_int, C.c_void_p, C.c_void_p],
+    "cslam_pf_new_feature_step_drawn": [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_longlong],
+})
+PF_NEW_FEATURE_SYMBOLS = ("cslam_pf_sample_pose", "cslam_pf_sample_pose_drawn", "cslam_pf_new_feature_step",
+                          "cslam_pf_new_feature_step_drawn")
+
 
 # The particle filter's score and trajectory log kept on the device (test/main.cpp:330, slam.h:493-511, 513-539): the
 # totals use the SCORE_* indices above; a series record is 4 floats, a track record 5 doubles.

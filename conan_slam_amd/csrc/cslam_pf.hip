@@ -21,6 +21,7 @@
 #include "pf_draw_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
+#include "pf_new_feature_kernels.hpp"
 #include "pf_score_kernels.hpp"
 #include "pf_staging.hpp"
 
@@ -94,6 +95,13 @@ struct PfBase
     virtual int observation_step_drawn(double v, double swa, const void* Q, double wb, double dt, const void* Z, int m,
                                        const int* idf, const void* R, long long step, double n_eff, int status)     = 0;
     virtual int get_stage_copies(long long* copies)                                                                 = 0;
+    // the scan that observes only new features (pf_new_feature_kernels.hpp); Q == nullptr: no predict
+    virtual int sample_pose(const void* normals)                                                                    = 0;
+    virtual int sample_pose_drawn(long long step)                                                                   = 0;
+    virtual int new_feature_step(double v, double swa, const void* Q, double wb, double dt, const void* Z, int q,
+                                 const void* R, const void* normals)                                                = 0;
+    virtual int new_feature_step_drawn(double v, double swa, const void* Q, double wb, double dt, const void* Z, int q,
+                                       const void* R, long long step)                                               = 0;
 };
 
 // Pf<T> sequences the runtime calls of every entry point; what it sequences them over lives in parts with one job each
@@ -1284,7 +1292,10 @@ struct Pf : PfBase
         if (m > 0)
         {
             std::memcpy(o.z, Z, (size_t)2 * m * sizeof(T));
-            std::memcpy(o.idf, idf, (size_t)m * sizeof(int));
+            if (idf) // (none: the new-feature scan has no correspondences; the idf slots get zeros)
+            {
+                std::memcpy(o.idf, idf, (size_t)m * sizeof(int));
+            }
         }
         const int nn = normals ? np : 0;
         const int lanes = std::max(std::max(nn, n_sel), std::max(2 * m, 1));
@@ -1406,6 +1417,89 @@ struct Pf : PfBase
         }
         *copies = ring.copies();
         return CSLAM_OK;
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // The scan that observes only new features (test/main.cpp:314-328, pf_new_feature_kernels.hpp): sample every pose
+    // from its own Gaussian, zero Pv, add the features at the sampled pose.  The normals sit where the proposal's sit in
+    // the staging area; Z travels as add_features' does.  Poses and nf change, slots do not: the association memo is
+    // left as cslam_pf_add_features and cslam_pf_predict leave it.
+    // ------------------------------------------------------------------------------------------------
+    int check_new_features(const void* Z, int q, const void* Rv, bool has_normals, const char* who)
+    {
+        switch (pf_new_feature_check(q, Z != nullptr, Rv != nullptr, has_normals, nf, nfcap))
+        {
+        case PfNewFeatureRefusal::none:
+            return CSLAM_OK;
+        case PfNewFeatureRefusal::capacity:
+            return fail(CSLAM_ERR_CAPACITY, "%s: %d features would exceed max_features=%d", who, nf + q, nfcap);
+        case PfNewFeatureRefusal::bad_arg:
+            break;
+        }
+        return fail(CSLAM_ERR_BAD_ARG, "%s: bad arguments (q=%d)", who, q);
+    }
+    int launch_sample_pose()
+    {
+        hipLaunchKernelGGL(pf_sample_pose_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), obs.dNormals());
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    // [predict +] sample + q new features behind Z | normals in the staging area; counts the features
+    int launch_new_feature_step(double v, double swa, const void* Qv, double wb, double dt, int q, const void* Rv)
+    {
+        const T*     Q = static_cast<const T*>(Qv);
+        const T*     R = static_cast<const T*>(Rv);
+        const T      zero[4] = {(T)0, (T)0, (T)0, (T)0};
+        PfPredict<T> pr = no_predict();
+        if (Q)
+        {
+            pr = PfPredict<T>{1, (T)v, (T)swa, Q[0], Q[1], Q[2], Q[3], (T)wb, (T)dt};
+        }
+        if (!R) // (q == 0: nothing reads it)
+        {
+            R = zero;
+        }
+        hipLaunchKernelGGL(pf_new_feature_step_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), obs.z(), q,
+                           R[0], R[1], R[2], R[3], obs.dNormals(), pr);
+        CSLAM_HIP_TRY(hipGetLastError());
+        nf += q;
+        return CSLAM_OK;
+    }
+
+    int sample_pose(const void* normals) override
+    {
+        CSLAM_TRY(check_new_features(nullptr, 0, nullptr, normals != nullptr, "pf_sample_pose"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage(nullptr, 0, nullptr, normals));
+        return launch_sample_pose();
+    }
+
+    int sample_pose_drawn(long long step) override
+    {
+        CSLAM_TRY(need_draws("pf_sample_pose_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage_drawn(nullptr, 0, nullptr, step));
+        return launch_sample_pose();
+    }
+
+    int new_feature_step(double v, double swa, const void* Qv, double wb, double dt, const void* Z, int q, const void* Rv,
+                         const void* normals) override
+    {
+        CSLAM_TRY(check_new_features(Z, q, Rv, normals != nullptr, "pf_new_feature_step"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage(Z, q, nullptr, normals));
+        return launch_new_feature_step(v, swa, Qv, wb, dt, q, Rv);
+    }
+
+    // launches only up to kPfDrawObsMax new observations: the producer writes Z and the normals of `step`
+    int new_feature_step_drawn(double v, double swa, const void* Qv, double wb, double dt, const void* Z, int q,
+                               const void* Rv, long long step) override
+    {
+        CSLAM_TRY(check_new_features(Z, q, Rv, true, "pf_new_feature_step_drawn"));
+        CSLAM_TRY(need_draws("pf_new_feature_step_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage_drawn(Z, q, nullptr, step));
+        return launch_new_feature_step(v, swa, Qv, wb, dt, q, Rv);
     }
 };
 
@@ -1940,6 +2034,34 @@ int cslam_pf_stage_copies(cslam_pf_t h, long long* copies)
 {
     CSLAM_NEED(h);
     return B(h)->get_stage_copies(copies);
+}
+
+/* test/main.cpp:321-324: X <- X + chol(P) z (slam.h:753-764, 413-436), P <- 0 */
+int cslam_pf_sample_pose(cslam_pf_t h, const void* normals)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_pose(normals);
+}
+
+int cslam_pf_sample_pose_drawn(cslam_pf_t h, long long step)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_pose_drawn(step);
+}
+
+/* test/main.cpp:314-328 behind PF.cpp:419-471: predict, sample the pose, zero Pv, PF.cpp:9-60 at the sampled pose */
+int cslam_pf_new_feature_step(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z, int q,
+                              const void* R, const void* normals)
+{
+    CSLAM_NEED(h);
+    return B(h)->new_feature_step(v, swa, Q, wb, dt, Z, q, R, normals);
+}
+
+int cslam_pf_new_feature_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z,
+                                    int q, const void* R, long long step)
+{
+    CSLAM_NEED(h);
+    return B(h)->new_feature_step_drawn(v, swa, Q, wb, dt, Z, q, R, step);
 }
 
 int cslam_pf_best_particle_sharded(cslam_pf_t h, cslam_comm_t comm, int pick, long long* global_index, void* w, void* Xv,

@@ -149,6 +149,29 @@ inline bool pf_has_duplicate(const int* idf, int m)
     return false;
 }
 
+// why a call of the new-feature scan (cslam_pf_sample_pose, cslam_pf_new_feature_step and their _drawn forms) is refused
+enum class PfNewFeatureRefusal
+{
+    none,
+    bad_arg, // q < 0, no normals, or q > 0 without Z or R
+    capacity // nf + q > max_features
+};
+
+// The arguments of the new-feature scan: q new observations (Z 2 x q, R 2 x 2) on a store of nf features with room for
+// nfcap.  With q = 0 neither Z nor R is read.  A refused call changes nothing.
+inline PfNewFeatureRefusal pf_new_feature_check(int q, bool has_Z, bool has_R, bool has_normals, int nf, int nfcap)
+{
+    if (q < 0 || !has_normals || (q > 0 && (!has_Z || !has_R)))
+    {
+        return PfNewFeatureRefusal::bad_arg;
+    }
+    if (q > nfcap - nf)
+    {
+        return PfNewFeatureRefusal::capacity;
+    }
+    return PfNewFeatureRefusal::none;
+}
+
 // The record counts of a sharded exchange: hc[r] records go to rank r, hc[world + r] come from it; both buffers hold
 // them grouped by rank.  Where the records for / from `rank` start:
 inline void pf_exchange_offsets(const int* hc, int world, int rank, size_t* soff, size_t* roff)

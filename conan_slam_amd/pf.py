@@ -467,6 +467,55 @@ class ParticleShard:
                                                       C.c_longlong(int(step)), C.c_double(float(n_effective)),
                                                       C.c_int(1 if resample_status else 0)))
 
+    # ---- the scan that observes only new features (test/main.cpp:314-328)
+    def _normals(self, normals):
+        return np.ascontiguousarray(np.asarray(normals, dtype=self.dtype).reshape(3, self.n_local))
+
+    def sample_pose(self, normals):
+        """X <- X + chol(P) z, P <- 0 for every owned particle (test/main.cpp:321-324, slam.h:753-764, 413-436); the
+        weights stay.  normals: 3 x n_local standard-normal draws (input)."""
+        check(self._L.cslam_pf_sample_pose(self._h, _vp(self._normals(normals))))
+
+    def sample_pose_drawn(self, step: int):
+        """sample_pose with the normals of `step` drawn on the device (streams 0..2); any shard of a seeded set."""
+        check(self._L.cslam_pf_sample_pose_drawn(self._h, C.c_longlong(int(step))))
+
+    def _new_feature_args(self, v, swa, Q, wb, dt, Z, R):
+        Zc, q = self._z(Z)
+        Qc = None if Q is None else self._m22(Q)
+        Rc = None if R is None else self._m22(R)
+        keep = (Zc, Qc, Rc)  # (alive until the call has consumed them)
+        return keep, (C.c_double(float(v)), C.c_double(float(swa)), _vp(Qc) if Qc is not None else None,
+                      C.c_double(float(wb)), C.c_double(float(dt)), _vp(Zc), C.c_int(q),
+                      _vp(Rc) if Rc is not None else None)
+
+    def new_feature_step(self, v, swa, Q, wb, dt, Z, R, normals):
+        """The whole all-new scan in one launch (test/main.cpp:314-328): predict (PF.cpp:419-471; Q=None: none), sample
+        the pose, zero Pv, add the features Z (2 x q) at the sampled pose (PF.cpp:9-60)."""
+        keep, args = self._new_feature_args(v, swa, Q, wb, dt, Z, R)
+        check(self._L.cslam_pf_new_feature_step(self._h, *args, _vp(self._normals(normals))))
+
+    def new_feature_step_drawn(self, v, swa, Q, wb, dt, Z, R, step: int):
+        """new_feature_step with the normals of `step` drawn on the device: launches only when q <= 32."""
+        keep, args = self._new_feature_args(v, swa, Q, wb, dt, Z, R)
+        check(self._L.cslam_pf_new_feature_step_drawn(self._h, *args, C.c_longlong(int(step))))
+
+    def scan_step_drawn(self, v, swa, Q, wb, dt, ZF, idf, ZN, R, step: int, n_effective: float, resample_status: bool):
+        """One scan of the reference's loop (test/main.cpp:279-328) on a shard that holds the whole set, every random
+        input of `step` drawn on the device.  ZF / idf: the observations of known features, ZN: those of new ones.
+        Known features seen: observation_step_drawn, then add_features(ZN) at the proposal's pose.  Only new ones:
+        new_feature_step_drawn (the pose is sampled, Pv zeroed, the features added there).  Neither: predict."""
+        mf = 0 if ZF is None else self._z(ZF)[1]
+        mn = 0 if ZN is None else self._z(ZN)[1]
+        if mf > 0:
+            self.observation_step_drawn(v, swa, Q, wb, dt, ZF, idf, R, step, n_effective, resample_status)
+            if mn > 0:
+                self.add_features(ZN, R)
+        elif mn > 0:
+            self.new_feature_step_drawn(v, swa, Q, wb, dt, ZN, R, step)
+        else:
+            self.predict(v, swa, Q, wb, dt)
+
     def stage_copies(self) -> int:
         """Host-to-device copy commands this shard has enqueued for per-step inputs (cslam_pf_stage_copies)."""
         n = C.c_longlong(0)

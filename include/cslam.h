@@ -671,6 +671,40 @@ int cslam_pf_observation_step_drawn(cslam_pf_t h, double v, double swa, const vo
                                     int m, const int* idf, const void* R, long long step, double n_effective,
                                     int resample_status);
 int cslam_pf_stage_copies(cslam_pf_t h, long long* copies);
+
+/* ---- the scan that observes ONLY new features (test/main.cpp:314-328; from X = 0, P = 0 the first scan of every run).
+ * The reference then draws every particle's pose from its own Gaussian, X <- X + chol(P) z
+ * (multivariateNormalGaussianDistribution, slam.h:753-764, with choleskyDecomposition, slam.h:413-436: the Jacobi
+ * factor V sqrt(lambda) where the LLT fails, a zero factor where that is not finite -- such a particle keeps its pose),
+ * sets P <- 0 and initialises the new features at the SAMPLED pose (PF::addOneNewFeature, PF.cpp:9-60).  The weights
+ * are not touched.
+ *
+ * cslam_pf_sample_pose        replaces test/main.cpp:321-324 for every owned particle (slam.h:753-764, slam.h:413-436).
+ *                             normals: 3 * n_particles scalars (host), component-major as cslam_pf_sample_proposal
+ *                             takes them.
+ * cslam_pf_new_feature_step   replaces the whole branch test/main.cpp:314-328 in ONE launch: PF::predict
+ *                             (PF.cpp:419-471) when Q is not NULL, the pose sample (slam.h:753-764, slam.h:413-436),
+ *                             P <- 0, and PF::addOneNewFeature (PF.cpp:9-60) of the q observations Z (2 x q) at the
+ *                             sampled pose.  Q = NULL: no predict (v, swa, wb, dt are ignored); the poses and Pv then
+ *                             come out bit for bit as cslam_pf_sample_pose leaves them, and the features as
+ *                             cslam_pf_add_features computes them behind it (to rounding: another kernel).
+ *                             q = 0 does exactly what [cslam_pf_predict +] cslam_pf_sample_pose does.
+ * The _drawn forms take the normals of `step` from the device-side draws (streams e = 0..2, see above; a scan takes
+ * either the proposal or this branch, so the two never both draw at one step): they need cslam_pf_seed_draws, work on
+ * ANY shard (first_global arbitrary: there is no collective in this branch), enqueue no copy command up to 32 new
+ * observations, and cslam_pf_get_draws(step) returns exactly the normals they consume.
+ * All four are asynchronous on the handle's stream and consume their host arrays before they return.
+ * q < 0, NULL normals, or q > 0 with a NULL Z or R: CSLAM_ERR_BAD_ARG; an unseeded handle in a _drawn form:
+ * CSLAM_ERR_BAD_ARG; nf + q > max_features: CSLAM_ERR_CAPACITY.  A refused call changes nothing: not the store, not the
+ * feature count, not the staging area, not the association tables.  On success the feature count grows by q.
+ * The tables of cslam_pf_associate are treated as cslam_pf_predict and cslam_pf_add_features treat them: poses and the
+ * feature count change, particles keep their slots, so the tables stay valid for their consumers. */
+int cslam_pf_sample_pose(cslam_pf_t h, const void* normals /* 3*np, component-major */);
+int cslam_pf_sample_pose_drawn(cslam_pf_t h, long long step);
+int cslam_pf_new_feature_step(cslam_pf_t h, double v, double swa, const void* Q /* NULL: no predict */, double wb, double dt,
+                              const void* Z, int q, const void* R, const void* normals);
+int cslam_pf_new_feature_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z,
+                                    int q, const void* R, long long step);
 /* download one particle (host buffers; any may be NULL): w (1), Xv (3), Pv (9), XF (2*nf), PF (4*nf) */
 int cslam_pf_get_particle(cslam_pf_t h, int index, void* w, void* Xv, void* Pv, void* XF, void* PF);
 /* upload one particle with nf features (nf must equal the current feature count, or set it when the

@@ -388,18 +388,10 @@ class HipPF : public PF
     {
         // the engine wants the draws component-major (normals[e * numParticles + p], one coalesced load per component);
         // an Eigen 3 x numParticles matrix is particle-major
-        if (normals.rows() != 3 || normals.cols() != np_)
+        std::vector<float> nrm;
+        if (!componentMajor(normals, nrm, "sampleProposal"))
         {
-            std::cout << "HipPF::sampleProposal: normals must be 3 x " << np_ << "\t" << "sampleProposal" << std::endl;
             return;
-        }
-        std::vector<float> nrm(static_cast<size_t>(3) * static_cast<size_t>(np_));
-        for (int p = 0; p < np_; p++)
-        {
-            for (int e = 0; e < 3; e++)
-            {
-                nrm[static_cast<size_t>(e) * static_cast<size_t>(np_) + static_cast<size_t>(p)] = normals(e, p);
-            }
         }
         report(cslam_pf_sample_proposal(h_, Z.data(), static_cast<int>(Z.cols()), idf.data(), R.data(), nrm.data()),
                "HipPF::sampleProposal"); // PF.cpp:502-544
@@ -418,6 +410,79 @@ class HipPF : public PF
     void addNewFeaturesAll(const Eigen::MatrixXf& Z, const Eigen::MatrixXf& R)
     {
         report(cslam_pf_add_features(h_, Z.data(), static_cast<int>(Z.cols()), R.data()), "HipPF::addOneNewFeature");
+    }
+    // ---- the scan that observes only new features (test/main.cpp:314-328): the pose of every particle is drawn from its
+    //      own Gaussian (slam.h:753-764 with slam.h:413-436), P <- 0, and the features are added at the sampled pose
+    /// test/main.cpp:321-324 for every owned particle; normals: 3 x numParticles, as sampleProposalAll takes them
+    void sampleNewFeaturePoseAll(const Eigen::MatrixXf& normals)
+    {
+        std::vector<float> nrm;
+        if (componentMajor(normals, nrm, "sampleNewFeaturePose"))
+        {
+            report(cslam_pf_sample_pose(h_, nrm.data()), "HipPF::sampleNewFeaturePose");
+        }
+    }
+    /// the same with the normals of the step set with setStep() drawn on the device: needs seedDraws()
+    void sampleNewFeaturePoseAll() { report(cslam_pf_sample_pose_drawn(h_, step_), "HipPF::sampleNewFeaturePose"); }
+    /// test/main.cpp:314-328 in one launch: sample the pose, zero P, addOneNewFeature (PF.cpp:9-60) at the sampled pose
+    void addNewFeaturesSampledAll(const Eigen::MatrixXf& Z, const Eigen::MatrixXf& R, const Eigen::MatrixXf& normals)
+    {
+        std::vector<float> nrm;
+        if (componentMajor(normals, nrm, "addNewFeaturesSampled"))
+        {
+            report(cslam_pf_new_feature_step(h_, 0.0, 0.0, nullptr, 0.0, 0.0, Z.data(), static_cast<int>(Z.cols()), R.data(),
+                                             nrm.data()),
+                   "HipPF::addNewFeaturesSampled");
+        }
+    }
+    /// the same with the normals of the step set with setStep() drawn on the device: needs seedDraws()
+    void addNewFeaturesSampledAll(const Eigen::MatrixXf& Z, const Eigen::MatrixXf& R)
+    {
+        report(cslam_pf_new_feature_step_drawn(h_, 0.0, 0.0, nullptr, 0.0, 0.0, Z.data(), static_cast<int>(Z.cols()), R.data(),
+                                               step_),
+               "HipPF::addNewFeaturesSampled");
+    }
+    /// One scan of the reference's loop -- predict (test/main.cpp:279-286) and the branches of test/main.cpp:303-328 --
+    /// with every random input of the step set with setStep() drawn on the device (needs seedDraws()).  ZF / idf: the
+    /// observations of known features, ZN: those of new ones, as dataAssociateTable splits them (test/main.cpp:300).
+    /// Known features seen: predict + sampleProposal + featureUpdate + resampleParticles, then addOneNewFeature of ZN.
+    /// Only new ones: predict, the pose sample, P <- 0 and addOneNewFeature in one launch.  Neither: predict.
+    void scanStepAll(const float& v, const float& swa, const Eigen::MatrixXf& Q, const float& wb, const float& dt,
+                     const Eigen::MatrixXf& ZF, const Eigen::VectorXi& idf, const Eigen::MatrixXf& ZN,
+                     const Eigen::MatrixXf& R, int numEffective, bool resampleStatus = false)
+    {
+        const int mf = static_cast<int>(ZF.cols()), mn = static_cast<int>(ZN.cols());
+        if (mf > 0 && comm_ == nullptr)
+        {
+            report(cslam_pf_observation_step_drawn(h_, v, swa, Q.data(), wb, dt, ZF.data(), mf, idf.data(), R.data(), step_,
+                                                   numEffective, resampleStatus ? 1 : 0),
+                   "HipPF::scanStep");
+        }
+        else if (mf > 0) // a sharded set: the same calls one by one, the resample over the communicator
+        {
+            double neff      = 0.0;
+            int    resampled = 0;
+            predictAll(v, swa, Q, wb, dt);
+            sampleProposalAll(ZF, idf, R);
+            featureUpdateAll(ZF, idf, R);
+            report(cslam_pf_resample_sharded_drawn(h_, comm_, step_, numEffective, resampleStatus ? 1 : 0, &neff, &resampled),
+                   "HipPF::scanStep");
+            lastNeff_      = static_cast<float>(neff);
+            lastResampled_ = resampled != 0;
+        }
+        if (mf > 0 && mn > 0)
+        {
+            addNewFeaturesAll(ZN, R);
+        }
+        else if (mf == 0 && mn > 0)
+        {
+            report(cslam_pf_new_feature_step_drawn(h_, v, swa, Q.data(), wb, dt, ZN.data(), mn, R.data(), step_),
+                   "HipPF::scanStep");
+        }
+        else if (mf == 0)
+        {
+            predictAll(v, swa, Q, wb, dt);
+        }
     }
 
     /// the strata positions of PF.cpp:557 (stratifiedRandom): supplied by the caller so that runs are reproducible
@@ -621,6 +686,24 @@ class HipPF : public PF
         {
             std::cout << cslam_last_error() << "\t" << who << std::endl; // cf. PF.cpp:215-218
         }
+    }
+    // an Eigen 3 x numParticles matrix of draws (particle-major) as the engine takes them: nrm[e * numParticles + p]
+    bool componentMajor(const Eigen::MatrixXf& normals, std::vector<float>& nrm, const char* who) const
+    {
+        if (normals.rows() != 3 || normals.cols() != np_)
+        {
+            std::cout << "HipPF::" << who << ": normals must be 3 x " << np_ << "\t" << who << std::endl;
+            return false;
+        }
+        nrm.resize(static_cast<size_t>(3) * static_cast<size_t>(np_));
+        for (int p = 0; p < np_; p++)
+        {
+            for (int e = 0; e < 3; e++)
+            {
+                nrm[static_cast<size_t>(e) * static_cast<size_t>(np_) + static_cast<size_t>(p)] = normals(e, p);
+            }
+        }
+        return true;
     }
     void applySeed()
     {
