@@ -586,9 +586,13 @@ struct Pf : PfBase
         {
             CSLAM_TRY(launch_draw(step, nullptr, sh.plan.selG.get(), N, 0, nullptr, nullptr));
         }
-        // 1. global weight sums
-        CSLAM_TRY(launch_weight_sums());
-        CSLAM_TRY(c->all_reduce_sum_f64(dSums.get(), sh.plan.sumsG.get(), 2, stream));
+        // 1. global weight sums, formed by every rank from the gathered weights with the reduction of the one-shard plan
+        // kernel: an all-reduce of per-rank sums would add the same f64 terms in an order that depends on the partition,
+        // and the normalised weights of a set would then depend, in their last bits, on how many ranks hold it
+        T* wall = sh.plan.wall.get();
+        CSLAM_TRY(c->all_gather(dW.get(), wall, (size_t)L, dt, sizeof(T), stream));
+        hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, wall, N, sh.plan.sumsG.get());
+        CSLAM_HIP_TRY(hipGetLastError());
         double* hs = sh.h_sums(); // (pinned; the counts use it later)
         CSLAM_HIP_TRY(hipMemcpyAsync(hs, sh.plan.sumsG.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
@@ -611,9 +615,10 @@ struct Pf : PfBase
         {
             return CSLAM_OK;
         }
-        // 3. every rank plans the same keep[] from the gathered weights and the shared strata
-        CSLAM_TRY(c->all_gather(dW.get(), sh.plan.wall.get(), (size_t)L, dt, sizeof(T), stream));
-        hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, sh.plan.wall.get(), N, sh.plan.selG.get(),
+        // 3. every rank plans the same keep[] from the gathered weights, normalised as its own were, and the shared strata
+        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((N + 255) / 256), dim3(256), 0, stream, wall, N, (T)(1.0 / ws), 0);
+        CSLAM_HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, wall, N, sh.plan.selG.get(),
                            sh.plan.keepG.get(), sh.plan.cumG.get());
         CSLAM_HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(pf_exchange_plan_kernel<0>, dim3(1), dim3(256), 0, stream, sh.plan.keepG.get(), N, L, rank, world,

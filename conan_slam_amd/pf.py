@@ -128,7 +128,7 @@ class TorchComm:
 
 class RcclComm:
     """The engine's own RCCL communicator (cslam_comm_create, include/cslam.h): the sharded resample then runs entirely
-    behind the C ABI (cslam_pf_resample_sharded) -- all-reduce, all-gather, the keep[] plan on the device and one grouped
+    behind the C ABI (cslam_pf_resample_sharded) -- all-gather, the sums and the keep[] plan on the device and one grouped
     send/recv -- with no tensor library in the data path.  The 128-byte unique id is created on rank 0 and handed to
     the other ranks through torch.distributed (any backend; gloo will do), which is used for nothing else."""
 

@@ -597,9 +597,11 @@ int cslam_pf_resample_stats(cslam_pf_t h, double* calls, double* resamples, doub
  * PF::resampleParticles (slam.h:871-872, PF.cpp:473-500) with stratifiedResample (PF.cpp:546-574) where every rank
  * holds n_particles of the world * n_particles particles (block partition: global slot g lives on rank g / n_particles).
  * The collectives run over RCCL (xGMI inside a node) on the handle's stream:
- *     1. all-reduce(sum) of [sum w, sum w^2]                       -> normalisation and Neff, identical on every rank
- *     2. only when it resamples: all-gather of the normalised weights; every rank derives the identical keep[] on its
- *        own device from the shared strata positions
+ *     1. all-gather of the weights; every rank forms [sum w, sum w^2] over the whole set with the reduction of the
+ *        one-shard call -> normalisation and Neff, identical on every rank AND bit for bit those of
+ *        cslam_pf_resample_local on the whole set, whatever the number of ranks
+ *     2. only when it resamples: every rank derives the identical keep[] on its own device from the gathered weights
+ *        and the shared strata positions
  *     3. one grouped send/recv of the packed particle records whose source rank differs from the destination rank
  * `select`: the world * n_particles strata positions of PF.cpp:557 (host pointer), identical on every rank.
  * neff / resampled may be NULL.  The librccl of the process is bound at run time (dlopen): there is no link-time
