@@ -130,6 +130,28 @@ _PROTOTYPES.update({
 PF_NEW_FEATURE_SYMBOLS = ("cslam_pf_sample_pose", "cslam_pf_sample_pose_drawn", "cslam_pf_new_feature_step",
                           "cslam_pf_new_feature_step_drawn")
 
+# The vote on new features kept on the device (the split of test/main.cpp:279-328 decided from the summary of
+# EKF.cpp:131-144, 235-326 per particle), the consumers that read its mask where it lies (PF.cpp:502-544, 222-277), the
+# add of the voted observations (PF.cpp:9-60) and the whole unknown-correspondence scan in one call.
+_PROTOTYPES.update({
+    "cslam_pf_associate_vote": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double],
+    "cslam_pf_associate_vote_sharded": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                        C.c_double],
+    "cslam_pf_vote_wait": [C.c_void_p, C.POINTER(C.c_int), C.c_void_p],
+    "cslam_pf_get_vote": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)],
+    "cslam_pf_sample_proposal_voted": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double],
+    "cslam_pf_sample_proposal_voted_drawn": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_longlong],
+    "cslam_pf_feature_update_voted": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "cslam_pf_add_features_voted": [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)],
+    "cslam_pf_assoc_scan_step_drawn": [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_longlong,
+                                       C.c_double, C.c_int, C.POINTER(C.c_int)],
+})
+PF_VOTE_SYMBOLS = ("cslam_pf_associate_vote", "cslam_pf_associate_vote_sharded", "cslam_pf_vote_wait", "cslam_pf_get_vote",
+                   "cslam_pf_sample_proposal_voted", "cslam_pf_sample_proposal_voted_drawn",
+                   "cslam_pf_feature_update_voted", "cslam_pf_add_features_voted", "cslam_pf_assoc_scan_step_drawn")
+PF_VOTE_LANES = 256  # kPfVoteLanes of csrc/pf_vote_kernels.hpp: observations per tile of the compaction
+
 
 # The particle filter's score and trajectory log kept on the device (test/main.cpp:330, slam.h:493-511, 513-539): the
 # totals use the SCORE_* indices above; a series record is 4 floats, a track record 5 doubles.

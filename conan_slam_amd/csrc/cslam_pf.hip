@@ -24,6 +24,7 @@
 #include "pf_new_feature_kernels.hpp"
 #include "pf_score_kernels.hpp"
 #include "pf_staging.hpp"
+#include "pf_vote_kernels.hpp"
 
 using namespace cslam;
 
@@ -102,6 +103,19 @@ struct PfBase
                                  const void* R, const void* normals)                                                = 0;
     virtual int new_feature_step_drawn(double v, double swa, const void* Q, double wb, double dt, const void* Z, int q,
                                        const void* R, long long step)                                               = 0;
+    // the vote on new features kept on the device (pf_vote_kernels.hpp) and the calls that consume it; c == nullptr: this
+    // handle alone
+    virtual int associate_vote(Comm* c, const void* Z, int m, const void* R, double gate1, double gate2,
+                               double new_fraction)                                                                 = 0;
+    virtual int vote_wait(int* q, int* use)                                                                         = 0;
+    virtual int get_vote(int* use, int* new_idx, void* ZN, int* q)                                                  = 0;
+    virtual int sample_proposal_voted(const void* Z, int m, const void* R, const void* normals, double miss_likelihood) = 0;
+    virtual int sample_proposal_voted_drawn(const void* Z, int m, const void* R, double miss_likelihood, long long step) = 0;
+    virtual int feature_update_voted(const void* Z, int m, const void* R)                                           = 0;
+    virtual int add_features_voted(const void* R, int* q_out)                                                       = 0;
+    virtual int assoc_scan_step_drawn(double v, double swa, const void* Q, double wb, double dt, const void* Z, int m,
+                                      const void* R, double gate1, double gate2, double new_fraction,
+                                      double miss_likelihood, long long step, double n_eff, int status, int* q_out) = 0;
 };
 
 // Pf<T> sequences the runtime calls of every entry point; what it sequences them over lives in parts with one job each
@@ -120,6 +134,7 @@ struct Pf : PfBase
     PfEstimateBufs<T>  est;
     PfScoreBufs        sc;
     PfAssocTables<T>   assoc;
+    PfVote<T>          vote;
     PfDraws<T>         draws;
 
     ~Pf() override
@@ -188,11 +203,11 @@ struct Pf : PfBase
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
-    // (the use[] mask travels in the staging area's idf slot)
-    int launch_proposal_assoc(int m, const T* R, double miss_likelihood)
+    // use: the mask on the device -- the staging area's idf slot (a caller's mask travels there) or the vote's
+    int launch_proposal_assoc(int m, const T* R, double miss_likelihood, const int* use)
     {
         hipLaunchKernelGGL(pf_sample_proposal_assoc_kernel<T>, dim3((np * kPfSubLanes + 63) / 64), dim3(64), 0, stream,
-                           store(), obs.z(), assoc.tab.idf.get(), obs.dIdf(), m, R[0], R[1], R[2], R[3], obs.dNormals(),
+                           store(), obs.z(), assoc.tab.idf.get(), use, m, R[0], R[1], R[2], R[3], obs.dNormals(),
                            (T)miss_likelihood, fused_update_gain());
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
@@ -204,10 +219,10 @@ struct Pf : PfBase
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
-    int launch_feature_update_assoc(int m, const T* R)
+    int launch_feature_update_assoc(int m, const T* R, const int* use)
     {
         hipLaunchKernelGGL(pf_feature_update_assoc_kernel<T>, dim3((np + 63) / 64, m), dim3(64), 0, stream, store(),
-                           obs.z(), assoc.tab.idf.get(), obs.dIdf(), m, R[0], R[1], R[2], R[3], update_gain());
+                           obs.z(), assoc.tab.idf.get(), use, m, R[0], R[1], R[2], R[3], update_gain());
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
@@ -1168,6 +1183,7 @@ struct Pf : PfBase
             CSLAM_HIP_TRY(hipGetLastError());
         }
         assoc.memo.associated(Z, m, nf);
+        vote.memo.forget(); // a vote belongs to the associate it was taken on
         return CSLAM_OK;
     }
 
@@ -1232,7 +1248,7 @@ struct Pf : PfBase
         CSLAM_TRY(use_device());
         CSLAM_TRY(check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc"));
         CSLAM_TRY(stage(Z, m, use, normals));
-        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood);
+        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood, obs.dIdf());
     }
 
     int feature_update_assoc(const void* Z, int m, const void* Rv, const int* use) override
@@ -1248,7 +1264,7 @@ struct Pf : PfBase
             return CSLAM_OK;
         }
         CSLAM_TRY(stage(Z, m, use));
-        return launch_feature_update_assoc(m, static_cast<const T*>(Rv));
+        return launch_feature_update_assoc(m, static_cast<const T*>(Rv), obs.dIdf());
     }
 
     // ------------------------------------------------------------------------------------------------
@@ -1377,7 +1393,7 @@ struct Pf : PfBase
         CSLAM_TRY(use_device());
         CSLAM_TRY(check_assoc_inputs(Z, m, use, "pf_sample_proposal_assoc_drawn"));
         CSLAM_TRY(stage_drawn(Z, m, use, step));
-        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood);
+        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood, obs.dIdf());
     }
 
     int resample_local_drawn(long long step, double n_eff, int status, double* neff, int* did) override
@@ -1505,6 +1521,255 @@ struct Pf : PfBase
         CSLAM_TRY(use_device());
         CSLAM_TRY(stage_drawn(Z, q, nullptr, step));
         return launch_new_feature_step(v, swa, Qv, wb, dt, q, Rv);
+    }
+
+    // ------------------------------------------------------------------------------------------------
+    // The vote on new features, kept on the device (pf_vote_kernels.hpp): which observations of the last associate become
+    // features of every particle.  The vote kernel runs behind the association's summary kernel and leaves use[], the
+    // compacted new observations and their count in HBM; one device-to-host copy of [q, m, use[m]] and an event follow.
+    // The _voted consumers launch the kernels of the _assoc consumers with the vote's use[] in the mask's place;
+    // add_features_voted waits for the event alone (the host owns nf, and q sizes the grid) and launches
+    // pf_add_features_kernel on the vote's ZN.  What the buffers describe: vote.memo (PfVoteMemo).
+    // ------------------------------------------------------------------------------------------------
+    int associate_vote(Comm* c, const void* Z, int m, const void* Rv, double gate1, double gate2,
+                       double new_fraction) override
+    {
+        const char* who = c ? "pf_associate_vote_sharded" : "pf_associate_vote";
+        if (!std::isfinite(new_fraction))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: new_fraction must be finite (got %g)", who, new_fraction);
+        }
+        if (m < 0 || m > 65535 || !Rv || (m > 0 && !Z) || !std::isfinite(gate1) || !std::isfinite(gate2))
+        {
+            return associate(Z, m, Rv, gate1, gate2); // (refuses with its own text, changes nothing)
+        }
+        CSLAM_TRY(use_device());
+        // everything that can fail comes before the collective: a rank never leaves its peers waiting inside one
+        CSLAM_TRY(est_comm_ok(c, who));
+        CSLAM_TRY(vote.ensure(m, c != nullptr, stream));
+        CSLAM_TRY(associate(Z, m, Rv, gate1, gate2));
+        if (m == 0) // nothing to vote on: q = 0, known at once, nothing launched
+        {
+            vote.memo.voted(0);
+            vote.memo.arrived(0);
+            return CSLAM_OK;
+        }
+        const double* summary = assoc.tab.summary.get();
+        if (c)
+        {
+            // the sum over the ranks of the shards' summaries, identical on every rank (the loopback adds in rank order)
+            CSLAM_TRY(c->all_reduce_sum_f64(summary, vote.summary_all.get(), 4 * m, stream));
+            summary = vote.summary_all.get();
+        }
+        hipLaunchKernelGGL(pf_assoc_vote_kernel<T>, dim3(1), dim3(kPfVoteLanes), 0, stream, summary, obs.z(), m,
+                           new_fraction, vote.use(), vote.b.new_idx.get(), vote.b.ZN.get(), vote.count());
+        CSLAM_HIP_TRY(hipGetLastError());
+        CSLAM_HIP_TRY(hipMemcpyAsync(vote.b.host.get(), vote.count(), PfVote<T>::copy_ints(m) * sizeof(int),
+                                     hipMemcpyDeviceToHost, stream));
+        CSLAM_HIP_TRY(hipEventRecord(vote.ev.get(), stream));
+        vote.memo.voted(m);
+        return CSLAM_OK;
+    }
+
+    // the texts of PfVoteMemo's refusals
+    int vote_refused(PfVoteRefusal r, const char* who)
+    {
+        switch (r)
+        {
+        case PfVoteRefusal::none:
+            return CSLAM_OK;
+        case PfVoteRefusal::already_added:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: the features of this vote have been added already", who);
+        case PfVoteRefusal::no_vote:
+            break;
+        }
+        return fail(CSLAM_ERR_BAD_ARG, "%s: no vote: cslam_pf_associate_vote has not been called since the last cslam_pf_associate",
+                    who);
+    }
+
+    // q of the live vote on the host: waits for the vote's event, and for nothing queued behind it
+    int vote_arrive(const char* who)
+    {
+        if (!vote.memo.waited())
+        {
+            CSLAM_HIP_TRY(hipEventSynchronize(vote.ev.get()));
+            const int q = vote.h_count()[0], m = vote.h_count()[1];
+            if (m != vote.memo.m() || q < 0 || q > m)
+            {
+                return fail(CSLAM_ERR_HIP, "%s: the vote came back as q=%d of m=%d, expected m=%d", who, q, m, vote.memo.m());
+            }
+            vote.memo.arrived(q);
+        }
+        return CSLAM_OK;
+    }
+
+    int vote_wait(int* q, int* use) override
+    {
+        CSLAM_TRY(vote_refused(vote.memo.check_read(), "pf_vote_wait"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(vote_arrive("pf_vote_wait"));
+        if (q)
+        {
+            *q = vote.memo.q();
+        }
+        if (use && vote.memo.m() > 0)
+        {
+            std::memcpy(use, vote.h_use(), (size_t)vote.memo.m() * sizeof(int));
+        }
+        return CSLAM_OK;
+    }
+
+    int get_vote(int* use, int* new_idx, void* ZN, int* q) override
+    {
+        CSLAM_TRY(vote_refused(vote.memo.check_read(), "pf_get_vote"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(vote_arrive("pf_get_vote"));
+        const int m = vote.memo.m(), nq = vote.memo.q();
+        if (use && m > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(use, vote.use(), (size_t)m * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (new_idx && nq > 0) // (entries from q on were never written)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(new_idx, vote.b.new_idx.get(), (size_t)nq * sizeof(int), hipMemcpyDeviceToHost, stream));
+        }
+        if (ZN && nq > 0)
+        {
+            CSLAM_HIP_TRY(hipMemcpyAsync(ZN, vote.b.ZN.get(), (size_t)2 * nq * sizeof(T), hipMemcpyDeviceToHost, stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        if (q)
+        {
+            *q = nq;
+        }
+        return CSLAM_OK;
+    }
+
+    // a _voted consumer reads use[] next to the association table: a live vote, and the scan and slots of its associate
+    int check_voted_inputs(const void* Z, int m, const char* who)
+    {
+        CSLAM_TRY(vote_refused(vote.memo.check_read(), who));
+        switch (assoc.memo.check_scan(Z, m, nf))
+        {
+        case PfAssocRefusal::never_associated:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: cslam_pf_associate has not been called", who);
+        case PfAssocRefusal::moved:
+            return fail(CSLAM_ERR_BAD_ARG,
+                        "%s: particles were resampled, unpacked or set (moved) since cslam_pf_associate_vote (its table is per slot)",
+                        who);
+        case PfAssocRefusal::other_scan:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: Z / m (%d) are not those of the last cslam_pf_associate_vote (m=%d)", who, m,
+                        assoc.memo.m());
+        case PfAssocRefusal::map_shrank:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: the map shrank (%d features) since cslam_pf_associate_vote (%d)", who, nf,
+                        assoc.memo.nf());
+        default:
+            break;
+        }
+        return CSLAM_OK;
+    }
+
+    int sample_proposal_voted(const void* Z, int m, const void* Rv, const void* normals, double miss_likelihood) override
+    {
+        if (m < 0 || !Rv || !normals || (m > 0 && !Z) || !std::isfinite(miss_likelihood))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_voted: bad arguments");
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_voted_inputs(Z, m, "pf_sample_proposal_voted"));
+        CSLAM_TRY(stage(Z, m, nullptr, normals));
+        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood, vote.use());
+    }
+
+    int sample_proposal_voted_drawn(const void* Z, int m, const void* Rv, double miss_likelihood, long long step) override
+    {
+        if (m < 0 || !Rv || (m > 0 && !Z) || !std::isfinite(miss_likelihood))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_sample_proposal_voted_drawn: bad arguments");
+        }
+        CSLAM_TRY(need_draws("pf_sample_proposal_voted_drawn"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_voted_inputs(Z, m, "pf_sample_proposal_voted_drawn"));
+        CSLAM_TRY(stage_drawn(Z, m, nullptr, step));
+        return launch_proposal_assoc(m, static_cast<const T*>(Rv), miss_likelihood, vote.use());
+    }
+
+    int feature_update_voted(const void* Z, int m, const void* Rv) override
+    {
+        if (m < 0 || !Rv || (m > 0 && !Z))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_feature_update_voted: bad arguments");
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(check_voted_inputs(Z, m, "pf_feature_update_voted"));
+        if (m == 0)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_TRY(stage(Z, m, nullptr));
+        return launch_feature_update_assoc(m, static_cast<const T*>(Rv), vote.use());
+    }
+
+    // PF.cpp:9-60 of the voted observations, read where the vote kernel left them.  Allowed after a resample: ZN is per
+    // observation.  A refusal leaves the store, the count and the vote as they were.
+    int add_features_voted(const void* Rv, int* q_out) override
+    {
+        if (!Rv)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_add_features_voted: R is null");
+        }
+        CSLAM_TRY(vote_refused(vote.memo.check_add(), "pf_add_features_voted"));
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(vote_arrive("pf_add_features_voted"));
+        const int q = vote.memo.q();
+        if (q_out)
+        {
+            *q_out = q;
+        }
+        if (nf + q > nfcap)
+        {
+            return fail(CSLAM_ERR_CAPACITY, "pf_add_features_voted: %d features would exceed max_features=%d", nf + q, nfcap);
+        }
+        if (q > 0)
+        {
+            const T* R = static_cast<const T*>(Rv);
+            hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, q), dim3(64), 0, stream, store(),
+                               vote.b.ZN.get(), q, R[0], R[1], R[2], R[3]);
+            CSLAM_HIP_TRY(hipGetLastError());
+            nf += q;
+        }
+        vote.memo.features_added();
+        return CSLAM_OK;
+    }
+
+    // One scan of the unknown-correspondence loop for a handle that holds the whole set: predict, associate + vote, the
+    // proposal on the vote's mask, the resample with nothing returned -- all queued -- and only then the wait for the
+    // vote's event and the voted features.  No dispatch to the sampled-pose branch of an all-new scan: q is not known
+    // when the proposal is queued.
+    int assoc_scan_step_drawn(double v, double swa, const void* Qv, double wb, double dt, const void* Z, int m, const void* Rv,
+                              double gate1, double gate2, double new_fraction, double miss_likelihood, long long step,
+                              double n_eff, int status, int* q_out) override
+    {
+        if (!Qv || !Rv || m < 0 || m > 65535 || (m > 0 && !Z) || !std::isfinite(gate1) || !std::isfinite(gate2) ||
+            !std::isfinite(new_fraction) || !std::isfinite(miss_likelihood))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_assoc_scan_step_drawn: bad arguments (m=%d)", m);
+        }
+        CSLAM_TRY(need_whole_set("pf_assoc_scan_step_drawn"));
+        CSLAM_TRY(use_device());
+        if (q_out)
+        {
+            *q_out = 0;
+        }
+        if (m == 0)
+        {
+            return launch_predict(v, swa, static_cast<const T*>(Qv), wb, dt);
+        }
+        CSLAM_TRY(launch_predict(v, swa, static_cast<const T*>(Qv), wb, dt));
+        CSLAM_TRY(associate_vote(nullptr, Z, m, Rv, gate1, gate2, new_fraction));
+        CSLAM_TRY(sample_proposal_voted_drawn(Z, m, Rv, miss_likelihood, step));
+        CSLAM_TRY(resample_local_drawn(step, n_eff, status, nullptr, nullptr));
+        return add_features_voted(Rv, q_out);
     }
 };
 
@@ -2089,6 +2354,76 @@ int cslam_pf_estimate_sharded(cslam_pf_t h, cslam_comm_t comm, double* w_sum, do
         return fail(CSLAM_ERR_BAD_ARG, "pf_estimate_sharded: null communicator");
     }
     return B(h)->estimate(reinterpret_cast<Comm*>(comm), w_sum, neff, Xv, Pv, XF, PF);
+}
+
+/* EKF.cpp:131-144, 235-326 on every particle's own state, then the split of test/main.cpp:279-328 voted on the device */
+int cslam_pf_associate_vote(cslam_pf_t h, const void* Z, int m, const void* R, double gate1, double gate2, double new_fraction)
+{
+    CSLAM_NEED(h);
+    return B(h)->associate_vote(nullptr, Z, m, R, gate1, gate2, new_fraction);
+}
+
+int cslam_pf_associate_vote_sharded(cslam_pf_t h, cslam_comm_t comm, const void* Z, int m, const void* R, double gate1,
+                                    double gate2, double new_fraction)
+{
+    CSLAM_NEED(h);
+    if (!comm)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pf_associate_vote_sharded: null communicator");
+    }
+    return B(h)->associate_vote(reinterpret_cast<Comm*>(comm), Z, m, R, gate1, gate2, new_fraction);
+}
+
+int cslam_pf_vote_wait(cslam_pf_t h, int* q, int* use)
+{
+    CSLAM_NEED(h);
+    return B(h)->vote_wait(q, use);
+}
+
+int cslam_pf_get_vote(cslam_pf_t h, int* use, int* new_idx, void* ZN, int* q)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_vote(use, new_idx, ZN, q);
+}
+
+/* PF.cpp:502-544 + 222-277 with every particle's own correspondences (EKF.cpp:131-144, 235-326), the mask from the vote */
+int cslam_pf_sample_proposal_voted(cslam_pf_t h, const void* Z, int m, const void* R, const void* normals,
+                                   double miss_likelihood)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_proposal_voted(Z, m, R, normals, miss_likelihood);
+}
+
+int cslam_pf_sample_proposal_voted_drawn(cslam_pf_t h, const void* Z, int m, const void* R, double miss_likelihood,
+                                         long long step)
+{
+    CSLAM_NEED(h);
+    return B(h)->sample_proposal_voted_drawn(Z, m, R, miss_likelihood, step);
+}
+
+/* PF.cpp:222-277 alone, the mask from the vote */
+int cslam_pf_feature_update_voted(cslam_pf_t h, const void* Z, int m, const void* R)
+{
+    CSLAM_NEED(h);
+    return B(h)->feature_update_voted(Z, m, R);
+}
+
+/* PF.cpp:9-60 of the voted observations */
+int cslam_pf_add_features_voted(cslam_pf_t h, const void* R, int* q_out)
+{
+    CSLAM_NEED(h);
+    return B(h)->add_features_voted(R, q_out);
+}
+
+/* test/main.cpp:279-328 with unknown correspondences in one call */
+int cslam_pf_assoc_scan_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z,
+                                   int m, const void* R, double gate1, double gate2, double new_fraction,
+                                   double miss_likelihood, long long step, double n_effective, int resample_status,
+                                   int* q_out)
+{
+    CSLAM_NEED(h);
+    return B(h)->assoc_scan_step_drawn(v, swa, Q, wb, dt, Z, m, R, gate1, gate2, new_fraction, miss_likelihood, step,
+                                       n_effective, resample_status, q_out);
 }
 
 } // extern "C"

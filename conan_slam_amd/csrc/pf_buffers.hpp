@@ -282,6 +282,70 @@ struct PfAssocTables
     int    mcap_     = 0; // observations the (m x np) tables and the summary hold
 };
 
+// The vote on new features (pf_vote_kernels.hpp) and what it describes (PfVoteMemo).  count and use share one block,
+// [q, m, use[mcap]], so that ONE device-to-host copy brings the count and the mask to the pinned mirror; new_idx and ZN
+// hold the compacted new observations; summary_all is the sum over the ranks of the shards' summaries and is allocated
+// for the sharded vote only.  The event is recorded behind that copy: waiting for it waits for the vote, not for what
+// has been queued since.
+template <typename T>
+struct PfVote
+{
+    struct Bufs
+    {
+        DevBuf<int>    count;   // [2 + mcap]: q, m, use[mcap]
+        DevBuf<int>    new_idx; // [mcap]
+        DevBuf<T>      ZN;      // [2 * mcap]
+        PinnedBuf<int> host;    // [2 + mcap], the mirror of count
+    };
+    Bufs           b;
+    DevBuf<double> summary_all; // [4 * mcap], sharded form
+    Event          ev;
+    PfVoteMemo     memo;
+
+    int* count() const { return b.count.get(); }
+    int* use() const { return b.count.get() + 2; }
+    const int* h_count() const { return b.host.get(); }
+    const int* h_use() const { return b.host.get() + 2; }
+    static size_t copy_ints(int m) { return (size_t)2 + (size_t)m; }
+
+    int ensure(int m, bool sharded, hipStream_t stream)
+    {
+        if (!ev)
+        {
+            CSLAM_TRY(ev.create(hipEventDisableTiming));
+        }
+        if (m > mcap_ || !b.count)
+        {
+            const int newm = std::max(m, std::max(64, 2 * mcap_));
+            Bufs      n;
+            CSLAM_TRY(n.count.alloc((size_t)2 + newm));
+            CSLAM_TRY(n.new_idx.alloc((size_t)newm));
+            CSLAM_TRY(n.ZN.alloc((size_t)2 * newm));
+            CSLAM_TRY(n.host.alloc((size_t)2 + newm));
+            DevBuf<double> s;
+            if (sharded || summary_all)
+            {
+                CSLAM_TRY(s.alloc((size_t)4 * newm));
+            }
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream)); // nothing queued still uses the old set
+            b           = std::move(n);
+            summary_all = std::move(s);
+            mcap_       = newm;
+            memo.forget(); // the old vote is gone
+        }
+        if (sharded && !summary_all)
+        {
+            DevBuf<double> s;
+            CSLAM_TRY(s.alloc((size_t)4 * mcap_));
+            summary_all = std::move(s);
+        }
+        return CSLAM_OK;
+    }
+
+  private:
+    int mcap_ = 0; // observations the set holds
+};
+
 // The seed of the device-side draws and the strata table of the resample (pf_draw_kernels.hpp).
 template <typename T>
 struct PfDraws

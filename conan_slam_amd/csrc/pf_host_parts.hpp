@@ -1,6 +1,7 @@
 // pf_host_parts.hpp -- the arithmetic and bookkeeping of the particle handle that needs no GPU: the layout of the device
-// staging area, the memo of what it holds, the validity of the association tables, and the small host loops of the
-// fused step, the sharded exchange and the strata table, and the book of the device-side score.  No HIP include:
+// staging area, the memo of what it holds, the validity of the association tables and of the vote on new features, and
+// the small host loops of the fused step, the sharded exchange and the strata table, and the book of the device-side
+// score.  No HIP include:
 // tests/host/pf_host_parts_check.cpp and pf_score_book_check.cpp build it with plain g++ (and under the address and
 // undefined-behaviour sanitizers).
 #pragma once
@@ -99,6 +100,24 @@ class PfAssocMemo
     // the consumers take the observations of the last associate: anything else would pair a table with the wrong scan
     PfAssocRefusal check(const void* Z, int m, int nf, const int* use, int* index) const
     {
+        const PfAssocRefusal scan = check_scan(Z, m, nf);
+        if (scan != PfAssocRefusal::none)
+        {
+            return scan;
+        }
+        for (int i = 0; i < m; i++)
+        {
+            if (use[i] != 0 && use[i] != 1)
+            {
+                *index = i;
+                return PfAssocRefusal::bad_use;
+            }
+        }
+        return PfAssocRefusal::none;
+    }
+    // the same without a host mask (the _voted consumers read theirs from the device)
+    PfAssocRefusal check_scan(const void* Z, int m, int nf) const
+    {
         if (assoc_m < 0)
         {
             return PfAssocRefusal::never_associated;
@@ -115,14 +134,6 @@ class PfAssocMemo
         {
             return PfAssocRefusal::map_shrank;
         }
-        for (int i = 0; i < m; i++)
-        {
-            if (use[i] != 0 && use[i] != 1)
-            {
-                *index = i;
-                return PfAssocRefusal::bad_use;
-            }
-        }
         return PfAssocRefusal::none;
     }
 
@@ -131,6 +142,64 @@ class PfAssocMemo
     int               assoc_nf    = 0;
     bool              assoc_moved = false;
     std::vector<char> assoc_Z; // the 2 * assoc_m observation scalars
+};
+
+// why a call that needs the vote on new features (cslam_pf_associate_vote) may not have it now
+enum class PfVoteRefusal
+{
+    none,
+    no_vote,      // no cslam_pf_associate_vote yet, or a later cslam_pf_associate dropped it
+    already_added // cslam_pf_add_features_voted has added this vote's features
+};
+
+// What the vote buffers describe.  A vote belongs to the LAST associate: a later plain associate drops it, a later
+// associate_vote replaces it.  Its features are added at most once.  The _voted consumers read use[] next to the
+// association table, so they need what PfAssocMemo::check_scan needs as well (same Z and m, particles not moved, map not
+// shrunk); adding the voted features needs none of that: ZN is per observation, not per particle slot.  q becomes known
+// to the host when somebody has waited for the vote's event.
+class PfVoteMemo
+{
+  public:
+    bool live() const { return live_; }
+    int  m() const { return m_; }
+    bool waited() const { return waited_; } // (of a live vote)
+    int  q() const { return q_; }           // (of a live vote somebody has waited for)
+    bool added() const { return added_; }
+
+    void forget() { live_ = false; } // a later associate, or the buffers are gone
+    void voted(int m)                // the vote of m observations has been queued behind its associate
+    {
+        live_   = true;
+        m_      = m;
+        waited_ = false;
+        q_      = 0;
+        added_  = false;
+    }
+    void arrived(int q) // somebody waited for the event: q is on the host
+    {
+        waited_ = true;
+        q_      = q;
+    }
+    void features_added() { added_ = true; }
+
+    // the consumers (together with PfAssocMemo::check_scan), cslam_pf_vote_wait and cslam_pf_get_vote
+    PfVoteRefusal check_read() const { return live_ ? PfVoteRefusal::none : PfVoteRefusal::no_vote; }
+    // cslam_pf_add_features_voted (a refusal -- this one or a capacity overflow -- leaves the vote as it was)
+    PfVoteRefusal check_add() const
+    {
+        if (!live_)
+        {
+            return PfVoteRefusal::no_vote;
+        }
+        return added_ ? PfVoteRefusal::already_added : PfVoteRefusal::none;
+    }
+
+  private:
+    bool live_   = false;
+    bool waited_ = false;
+    bool added_  = false;
+    int  m_      = 0;
+    int  q_      = 0;
 };
 
 // does an observation list name a feature twice?

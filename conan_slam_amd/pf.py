@@ -318,6 +318,86 @@ class ParticleShard:
         check(self._L.cslam_pf_feature_update_assoc(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)),
                                                     _vp(use) if m else None))
 
+    # ---- the vote on new features kept on the device: data_associate's policy without the host in the scan
+    def associate_vote(self, Z, R, gate1, gate2, new_fraction=0.5, comm=None):
+        """associate(Z, ...), then new_feature_votes on the device (cslam_pf_associate_vote): use[], the new observations
+        compacted in order and their count stay in HBM for the _voted calls.  comm: the vote reads the sum over the ranks
+        of the shards' summaries (cslam_pf_associate_vote_sharded).  Asynchronous; see vote_wait() and vote()."""
+        Zc, m = self._z(Z)
+        if np.isfinite(float(new_fraction)):  # (a non-finite fraction is refused before anything changes)
+            self._assoc_m = None
+        args = (_vp(Zc), C.c_int(m), _vp(self._m22(R)), C.c_double(float(gate1)), C.c_double(float(gate2)),
+                C.c_double(float(new_fraction)))
+        if comm is None:
+            check(self._L.cslam_pf_associate_vote(self._h, *args))
+        else:
+            check(self._L.cslam_pf_associate_vote_sharded(self._h, comm._h, *args))
+        self._assoc_m = m
+        self._voted(m)
+
+    def _voted(self, m):
+        # a refused call leaves the live vote (and its m) as it was; buffers are sized for the largest m ever voted on
+        self._vote_m, self._vote_cap = m, max(m, getattr(self, "_vote_cap", 1))
+
+    def vote_wait(self):
+        """-> (q, use) of the live vote, waiting for the vote alone and not for what has been queued behind it."""
+        m = getattr(self, "_vote_m", 0)
+        q, use = C.c_int(0), np.zeros(getattr(self, "_vote_cap", 1), np.int32)
+        check(self._L.cslam_pf_vote_wait(self._h, C.byref(q), _vp(use)))
+        return q.value, use[:m]
+
+    def vote(self):
+        """-> (use [m], new_idx [q], ZN [2 x q], q) of the live vote, read from the device (synchronises)."""
+        m, cap = getattr(self, "_vote_m", 0), getattr(self, "_vote_cap", 1)
+        use, idx = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        ZN, q = np.zeros((2, cap), self.dtype, order="F"), C.c_int(0)
+        check(self._L.cslam_pf_get_vote(self._h, _vp(use), _vp(idx), _vp(ZN), C.byref(q)))
+        return use[:m], idx[:q.value], np.asfortranarray(ZN[:, :q.value]), q.value
+
+    def sample_proposal_voted(self, Z, R, normals, miss_likelihood=1.0):
+        """sample_proposal_assoc with the mask of the live vote, read on the device."""
+        Zc, m = self._z(Z)
+        check(self._L.cslam_pf_sample_proposal_voted(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)),
+                                                     _vp(self._normals(normals)), C.c_double(float(miss_likelihood))))
+
+    def sample_proposal_voted_drawn(self, Z, R, step: int, miss_likelihood=1.0):
+        """sample_proposal_assoc_drawn with the mask of the live vote, read on the device."""
+        Zc, m = self._z(Z)
+        check(self._L.cslam_pf_sample_proposal_voted_drawn(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R)),
+                                                           C.c_double(float(miss_likelihood)), C.c_longlong(int(step))))
+
+    def feature_update_voted(self, Z, R):
+        """feature_update_assoc with the mask of the live vote, read on the device."""
+        Zc, m = self._z(Z)
+        check(self._L.cslam_pf_feature_update_voted(self._h, _vp(Zc), C.c_int(m), _vp(self._m22(R))))
+
+    def add_features_voted(self, R) -> int:
+        """add_features of the voted observations, read from the device (cslam_pf_add_features_voted) -> q."""
+        q = C.c_int(0)
+        check(self._L.cslam_pf_add_features_voted(self._h, _vp(self._m22(R)), C.byref(q)))
+        return q.value
+
+    def assoc_scan_step_drawn(self, v, swa, Q, wb, dt, Z, R, gate1, gate2, step: int, n_effective: float,
+                              resample_status: bool, new_fraction=0.5, miss_likelihood=1.0) -> int:
+        """One scan with unknown correspondences on a shard that holds the whole set, in one C call
+        (cslam_pf_assoc_scan_step_drawn): predict, associate_vote, sample_proposal_voted_drawn, resample_local_drawn with
+        nothing returned, add_features_voted -> q.  No observations: the predict alone."""
+        Zc, m = self._z(Z)
+        q = C.c_int(0)
+        if m:
+            self._assoc_m = None
+            self._vote_cap = max(m, getattr(self, "_vote_cap", 1))
+        rc = self._L.cslam_pf_assoc_scan_step_drawn(
+            self._h, C.c_double(float(v)), C.c_double(float(swa)), _vp(self._m22(Q)), C.c_double(float(wb)),
+            C.c_double(float(dt)), _vp(Zc), C.c_int(m), _vp(self._m22(R)), C.c_double(float(gate1)),
+            C.c_double(float(gate2)), C.c_double(float(new_fraction)), C.c_double(float(miss_likelihood)),
+            C.c_longlong(int(step)), C.c_double(float(n_effective)), C.c_int(1 if resample_status else 0), C.byref(q))
+        if m and rc in (_capi.OK, _capi.ERR_CAPACITY):  # (on a capacity overflow the scan ran and its vote is live)
+            self._assoc_m = m
+            self._voted(m)
+        check(rc)
+        return q.value
+
     # ---- pieces of the resample step
     def weight_sums(self) -> Tuple[float, float]:
         s = (C.c_double * 2)()

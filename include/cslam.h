@@ -707,6 +707,71 @@ int cslam_pf_new_feature_step(cslam_pf_t h, double v, double swa, const void* Q 
                               const void* Z, int q, const void* R, const void* normals);
 int cslam_pf_new_feature_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z,
                                     int q, const void* R, long long step);
+
+/* ---- the vote on new features, on the device: the scan with unknown correspondences without a host decision ----
+ * cslam_pf_associate gives every particle its own correspondences (EKF.cpp:131-144, 235-326); WHICH observations become
+ * new features is one decision for the whole set, because the feature index space is shared (the split that
+ * test/main.cpp:279-328 takes from its table).  Observation j is NEW when, with summary[j] = (s0, s1, s2, .) of the last
+ * associate and total = (s0 + s1) + s2 in double, in this order:  total > 0, s1 > 0 and s1 >= new_fraction * total.
+ *
+ * cslam_pf_associate_vote          cslam_pf_associate (EKF.cpp:131-144, 235-326), then the vote on this handle's summary:
+ *                                  in HBM use[j] = new ? 0 : 1, the new observations compacted in observation order
+ *                                  (new_idx[k] = j, ZN column k = Z column j) and their count q; one device-to-host copy
+ *                                  of [q, m, use[m]] into a pinned block and an event behind it.  Asynchronous.  A
+ *                                  non-finite new_fraction: CSLAM_ERR_BAD_ARG, nothing changes.  m = 0 launches nothing
+ *                                  and is a vote with q = 0.
+ * cslam_pf_associate_vote_sharded  the same (EKF.cpp:131-144, 235-326 on every rank's shard) with the vote read from the
+ *                                  SUM over the ranks of the shards' summaries (one all-reduce of 4 m doubles; the
+ *                                  loopback communicator adds in rank order): every rank ends with identical use, ZN and
+ *                                  q.  cslam_pf_get_association still returns the shard's own summary.  Everything that
+ *                                  can fail locally comes before the collective, as in cslam_pf_resample_sharded.
+ * A vote belongs to the last associate: a later cslam_pf_associate drops it, a later cslam_pf_associate_vote replaces it.
+ * cslam_pf_vote_wait               waits for the vote's event only -- not for work queued behind it -- and returns q and
+ *                                  (use != NULL) the m flags from the pinned block.  May be called more than once per
+ *                                  vote.  No live vote: CSLAM_ERR_BAD_ARG.
+ * cslam_pf_get_vote                for tests and reporting; synchronises.  use m ints, new_idx q ints, ZN 2 * q scalars of
+ *                                  the handle's dtype (room for m / m / 2 * m serves any vote), any output may be NULL.
+ *                                  Entries from q on are not written.
+ * cslam_pf_sample_proposal_voted, _voted_drawn (PF.cpp:502-544 + 222-277), cslam_pf_feature_update_voted (PF.cpp:222-277)
+ *                                  cslam_pf_sample_proposal_assoc, _assoc_drawn and cslam_pf_feature_update_assoc with the
+ *                                  mask read from the vote's use[] on the device: the same kernels, no mask staged.  They
+ *                                  need a live vote and what the _assoc calls need: Z and m of that associate, particles
+ *                                  in the slots they had then (a resample since: CSLAM_ERR_BAD_ARG, "moved"), a map that
+ *                                  has not shrunk.
+ * cslam_pf_add_features_voted      PF::addOneNewFeature (PF.cpp:9-60) of the q voted observations, read from the vote's
+ *                                  ZN: waits for the vote's event if nobody has, then one launch, and the feature count
+ *                                  grows by q (*q_out = q, may be NULL).  Allowed after a resample (ZN is per observation,
+ *                                  not per slot).  q = 0 launches nothing.  A vote is added at most once: a second call
+ *                                  is CSLAM_ERR_BAD_ARG.  nf + q > max_features: CSLAM_ERR_CAPACITY with *q_out = q,
+ *                                  nothing changes and the vote stays as it was.
+ * cslam_pf_assoc_scan_step_drawn   one scan of test/main.cpp:279-328 with unknown correspondences in ONE call, for a
+ *                                  handle that holds the whole set (the preconditions of cslam_pf_resample_local_drawn):
+ *                                  cslam_pf_predict (PF.cpp:419-471), cslam_pf_associate_vote,
+ *                                  cslam_pf_sample_proposal_voted_drawn(step), cslam_pf_resample_local_drawn(step) with
+ *                                  nothing returned (PF.cpp:473-500), and only then the wait for the vote and
+ *                                  cslam_pf_add_features_voted: the host blocks on the vote's event alone, with the
+ *                                  proposal and the resample already queued.  m = 0 is the predict alone (*q_out = 0, a
+ *                                  live vote is left as it is).  On CSLAM_ERR_CAPACITY the predict, the proposal and the
+ *                                  resample HAVE been applied and no feature was added -- the state the separate calls
+ *                                  leave; the vote can still be added after room has been made.  A scan in which every
+ *                                  observation is new takes this path too (the poses are not sampled as
+ *                                  cslam_pf_new_feature_step samples them: q is not known when the proposal is queued). */
+int cslam_pf_associate_vote(cslam_pf_t h, const void* Z, int m, const void* R, double gate1, double gate2,
+                            double new_fraction);
+int cslam_pf_associate_vote_sharded(cslam_pf_t h, cslam_comm_t comm, const void* Z, int m, const void* R, double gate1,
+                                    double gate2, double new_fraction);
+int cslam_pf_vote_wait(cslam_pf_t h, int* q, int* use /* m or NULL */);
+int cslam_pf_get_vote(cslam_pf_t h, int* use, int* new_idx, void* ZN, int* q);
+int cslam_pf_sample_proposal_voted(cslam_pf_t h, const void* Z, int m, const void* R, const void* normals,
+                                   double miss_likelihood);
+int cslam_pf_sample_proposal_voted_drawn(cslam_pf_t h, const void* Z, int m, const void* R, double miss_likelihood,
+                                         long long step);
+int cslam_pf_feature_update_voted(cslam_pf_t h, const void* Z, int m, const void* R);
+int cslam_pf_add_features_voted(cslam_pf_t h, const void* R, int* q_out);
+int cslam_pf_assoc_scan_step_drawn(cslam_pf_t h, double v, double swa, const void* Q, double wb, double dt, const void* Z,
+                                   int m, const void* R, double gate1, double gate2, double new_fraction,
+                                   double miss_likelihood, long long step, double n_effective, int resample_status,
+                                   int* q_out);
 /* download one particle (host buffers; any may be NULL): w (1), Xv (3), Pv (9), XF (2*nf), PF (4*nf) */
 int cslam_pf_get_particle(cslam_pf_t h, int index, void* w, void* Xv, void* Pv, void* XF, void* PF);
 /* upload one particle with nf features (nf must equal the current feature count, or set it when the

@@ -28,6 +28,10 @@
 //   HipPF::extractMap        (the mixture's feature means)           -> cslam_pf_estimate
 //   HipPF::scoreReset / scoreTruth / score / scores   (the estimate test/main.cpp:330 prints, scored and logged on the
 //                            device; slam.h:493-511, 513-539)        -> cslam_pf_score_reset / _set_truth / _score / _get_scores
+//   HipPF::associateVoteAll / sampleProposalVotedAll / addVotedFeaturesAll / scanStepUnknownAll   (the loop of
+//                            test/main.cpp:279-328 without its table: EKF.cpp:131-144, 235-326 per particle, the vote on
+//                            new features kept on the device)         -> cslam_pf_associate_vote / _sample_proposal_voted_drawn
+//                                                                       / _add_features_voted / _assoc_scan_step_drawn
 //
 // Ownership: the reference passes X and P by reference into every call; here the handle owns them in HBM.  X is
 // refreshed after every call (the driver reads it every iteration, test/main.cpp:136); P is refreshed on demand
@@ -483,6 +487,56 @@ class HipPF : public PF
         {
             predictAll(v, swa, Q, wb, dt);
         }
+    }
+
+    // ---- unknown correspondences with the vote on new features kept on the device: no host decision inside the scan
+    /// Every particle's own gated nearest-neighbour association (EKF.cpp:131-144, 235-326), then the vote on which
+    /// observations become features of every particle (the split test/main.cpp:300 takes from its table), left on the
+    /// device.  newFraction: the share of the weight mass that must call an observation new.  With a communicator the
+    /// vote reads the summaries of all ranks.  Asynchronous.
+    void associateVoteAll(const Eigen::MatrixXf& Z, const Eigen::MatrixXf& R, float gate1, float gate2,
+                          float newFraction = 0.5f)
+    {
+        const int m = static_cast<int>(Z.cols());
+        if (comm_ != nullptr)
+        {
+            report(cslam_pf_associate_vote_sharded(h_, comm_, Z.data(), m, R.data(), gate1, gate2, newFraction),
+                   "HipPF::associateVote");
+        }
+        else
+        {
+            report(cslam_pf_associate_vote(h_, Z.data(), m, R.data(), gate1, gate2, newFraction), "HipPF::associateVote");
+        }
+    }
+    /// sampleProposal + featureUpdate (PF.cpp:502-544, 222-277) with every particle's own correspondences and the mask of
+    /// the vote, read on the device; the normals of the step set with setStep() are drawn there too (needs seedDraws()).
+    /// Z: the observations of associateVoteAll.  A particle without a match pays missLikelihood.
+    void sampleProposalVotedAll(const Eigen::MatrixXf& Z, const Eigen::MatrixXf& R, float missLikelihood = 1.0f)
+    {
+        report(cslam_pf_sample_proposal_voted_drawn(h_, Z.data(), static_cast<int>(Z.cols()), R.data(), missLikelihood, step_),
+               "HipPF::sampleProposalVoted");
+    }
+    /// addOneNewFeature (PF.cpp:9-60) of the voted observations, read on the device; returns how many there were
+    int addVotedFeaturesAll(const Eigen::MatrixXf& R)
+    {
+        int q = 0;
+        report(cslam_pf_add_features_voted(h_, R.data(), &q), "HipPF::addVotedFeatures");
+        return q;
+    }
+    /// One scan of the reference's loop (test/main.cpp:279-328) WITHOUT its table, for a set held by one handle: predict,
+    /// associateVoteAll, sampleProposalVotedAll, resampleParticles with the strata of the step set with setStep() and
+    /// addVotedFeaturesAll, in one call that waits for the vote alone.  Returns the number of features added.  No
+    /// observations: predict.
+    int scanStepUnknownAll(const float& v, const float& swa, const Eigen::MatrixXf& Q, const float& wb, const float& dt,
+                           const Eigen::MatrixXf& Z, const Eigen::MatrixXf& R, float gate1, float gate2, int numEffective,
+                           bool resampleStatus = false, float newFraction = 0.5f, float missLikelihood = 1.0f)
+    {
+        int q = 0;
+        report(cslam_pf_assoc_scan_step_drawn(h_, v, swa, Q.data(), wb, dt, Z.data(), static_cast<int>(Z.cols()), R.data(),
+                                              gate1, gate2, newFraction, missLikelihood, step_, numEffective,
+                                              resampleStatus ? 1 : 0, &q),
+               "HipPF::scanStepUnknown");
+        return q;
     }
 
     /// the strata positions of PF.cpp:557 (stratifiedRandom): supplied by the caller so that runs are reproducible
