@@ -152,6 +152,23 @@ PF_VOTE_SYMBOLS = ("cslam_pf_associate_vote", "cslam_pf_associate_vote_sharded",
                    "cslam_pf_feature_update_voted", "cslam_pf_add_features_voted", "cslam_pf_assoc_scan_step_drawn")
 PF_VOTE_LANES = 256  # kPfVoteLanes of csrc/pf_vote_kernels.hpp: observations per tile of the compaction
 
+# A run of control steps in one launch per PF_CONTROL_MAX (test/main.cpp:279-286: PF.cpp:419-471 then PF.cpp:382-417 per
+# step), the count of those launches, and the whole iteration block of test/main.cpp:249-334 in one call, with known and
+# with unknown correspondences.
+_CONTROL_ARGS = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_int]
+_PROTOTYPES.update({
+    "cslam_pf_control_run": [C.c_void_p] + _CONTROL_ARGS,
+    "cslam_pf_control_launches": [C.c_void_p, C.POINTER(C.c_longlong)],
+    "cslam_pf_cycle_drawn": [C.c_void_p] + _CONTROL_ARGS + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                            C.c_void_p, C.c_longlong, C.c_double, C.c_int],
+    "cslam_pf_assoc_cycle_drawn": [C.c_void_p] + _CONTROL_ARGS + [C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_double,
+                                                                  C.c_double, C.c_double, C.c_longlong, C.c_double,
+                                                                  C.c_int, C.POINTER(C.c_int)],
+})
+PF_CONTROL_SYMBOLS = ("cslam_pf_control_run", "cslam_pf_control_launches", "cslam_pf_cycle_drawn",
+                      "cslam_pf_assoc_cycle_drawn")
+PF_CONTROL_MAX = 16  # kPfControlMax of csrc/pf_control_kernels.hpp: control steps of one launch
+
 
 # The particle filter's score and trajectory log kept on the device (test/main.cpp:330, slam.h:493-511, 513-539): the
 # totals use the SCORE_* indices above; a series record is 4 floats, a track record 5 doubles.

@@ -18,6 +18,7 @@
 #include "pf_assoc_kernels.hpp"
 #include "pf_buffers.hpp"
 #include "pf_comm.hpp"
+#include "pf_control_kernels.hpp"
 #include "pf_draw_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
 #include "pf_kernels.hpp"
@@ -42,6 +43,7 @@ struct PfBase
     int         nf     = 0;
     Stream      stream_own;       // (in the base: destroyed after the buffers and events of Pf<T>)
     hipStream_t stream = nullptr; // = stream_own.get()
+    long long   control_launches = 0; // pf_control_run_kernel launches (cslam_pf_control_launches)
 
     virtual int init()                                                                       = 0;
     virtual int set_uniform_weight(double w0)                                                 = 0;
@@ -116,6 +118,16 @@ struct PfBase
     virtual int assoc_scan_step_drawn(double v, double swa, const void* Q, double wb, double dt, const void* Z, int m,
                                       const void* R, double gate1, double gate2, double new_fraction,
                                       double miss_likelihood, long long step, double n_eff, int status, int* q_out) = 0;
+    // a run of control steps in one launch per kPfControlMax (pf_control_kernels.hpp) and the whole-cycle calls behind it
+    virtual int control_run(int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                            const double* phi, int use)                                                             = 0;
+    virtual int cycle_drawn(int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                            const double* phi, int use, const void* ZF, int mf, const int* idf, const void* ZN, int mn,
+                            const void* R, long long step, double n_eff, int status)                                = 0;
+    virtual int assoc_cycle_drawn(int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                                  const double* phi, int use, const void* Z, int m, const void* R, double gate1,
+                                  double gate2, double new_fraction, double miss_likelihood, long long step, double n_eff,
+                                  int status, int* q_out)                                                           = 0;
 };
 
 // Pf<T> sequences the runtime calls of every entry point; what it sequences them over lives in parts with one job each
@@ -1771,6 +1783,204 @@ struct Pf : PfBase
         CSLAM_TRY(resample_local_drawn(step, n_eff, status, nullptr, nullptr));
         return add_features_voted(Rv, q_out);
     }
+
+    // ------------------------------------------------------------------------------------------------
+    // The control run (test/main.cpp:279-286, pf_control_kernels.hpp): k x (PF::predict, PF::observeHeading) for every
+    // owned particle in one launch per kPfControlMax steps, and the whole-cycle calls that put it in front of a scan.
+    // Poses change, slots and the feature count do not: the staging memo, the association memo and the vote are left as
+    // cslam_pf_predict leaves them -- untouched.
+    // ------------------------------------------------------------------------------------------------
+    int check_control(int k, const double* v, const double* swa, const void* Qv, const double* phi, int use, const char* who)
+    {
+        switch (pf_control_check(k, v != nullptr, swa != nullptr, Qv != nullptr, phi != nullptr, use != 0))
+        {
+        case PfControlRefusal::none:
+            return CSLAM_OK;
+        case PfControlRefusal::bad_k:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: k=%d control steps", who, k);
+        case PfControlRefusal::null_control:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: v, swa or Q is null (k=%d)", who, k);
+        case PfControlRefusal::null_phi:
+            break;
+        }
+        return fail(CSLAM_ERR_BAD_ARG, "%s: the heading is observed and phi is null (k=%d)", who, k);
+    }
+    // the launches of a checked run; every value is cast to T as cslam_pf_predict and cslam_pf_observe_heading cast it
+    int launch_control_run(int k, const double* v, const double* swa, const void* Qv, double wb, double dt, const double* phi,
+                           int use)
+    {
+        static_assert(kPfControlMax == kPfControlChunk, "the chunk split is that of the kernel");
+        const T* Q     = static_cast<const T*>(Qv);
+        const T  sigma = (T)(((double)0.01f * kPi) / 180.0); // PF.cpp:391
+        int      first = 0, count = 0;
+        for (int c = 0; pf_control_chunk(k, c, &first, &count); c++)
+        {
+            PfControls<T> ctl;
+            std::memset(&ctl, 0, sizeof(ctl));
+            for (int j = 0; j < count; j++)
+            {
+                ctl.v[j]   = (T)v[first + j];
+                ctl.swa[j] = (T)swa[first + j];
+                ctl.phi[j] = use ? (T)phi[first + j] : (T)0;
+            }
+            hipLaunchKernelGGL(pf_control_run_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), count, ctl,
+                               Q[0], Q[1], Q[2], Q[3], (T)wb, (T)dt, use ? 1 : 0, sigma * sigma);
+            CSLAM_HIP_TRY(hipGetLastError());
+            control_launches++;
+        }
+        return CSLAM_OK;
+    }
+
+    int control_run(int k, const double* v, const double* swa, const void* Qv, double wb, double dt, const double* phi,
+                    int use) override
+    {
+        CSLAM_TRY(check_control(k, v, swa, Qv, phi, use, "pf_control_run"));
+        if (k == 0)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_TRY(use_device());
+        return launch_control_run(k, v, swa, Qv, wb, dt, phi, use);
+    }
+
+    // One iteration block of the reference's loop with known correspondences for a handle that holds the whole seeded
+    // set: the control run, then the scan of test/main.cpp:294-328 WITHOUT a predict of its own, on the kernels of the
+    // separate calls.  Everything that can refuse does so before the control run is launched.  Z of the known and of the
+    // new features travel together as the producer kernel's arguments while they fit (mf + mn <= kPfDrawObsMax): the new
+    // ones lie behind the known ones in the staging area until pf_add_features_kernel reads them, behind the resample.
+    int cycle_drawn(int k, const double* v, const double* swa, const void* Qv, double wb, double dt, const double* phi,
+                    int use, const void* ZF, int mf, const int* idf, const void* ZN, int mn, const void* Rv, long long step,
+                    double n_eff, int status) override
+    {
+        const char* who = "pf_cycle_drawn";
+        CSLAM_TRY(check_control(k, v, swa, Qv, phi, use, who));
+        if (mf < 0 || mn < 0 || (mf > 0 && (!ZF || !idf)) || (mn > 0 && !ZN) || ((mf > 0 || mn > 0) && !Rv))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: bad arguments (mf=%d, mn=%d)", who, mf, mn);
+        }
+        if (mf > 0)
+        {
+            CSLAM_TRY(need_whole_set(who));
+            CSLAM_TRY(check_idf(idf, mf, who));
+            if (mn > nfcap - nf)
+            {
+                return fail(CSLAM_ERR_CAPACITY, "%s: %d features would exceed max_features=%d", who, nf + mn, nfcap);
+            }
+        }
+        else if (mn > 0)
+        {
+            CSLAM_TRY(check_new_features(ZN, mn, Rv, true, who));
+            CSLAM_TRY(need_draws(who));
+        }
+        CSLAM_TRY(use_device());
+        const bool together = mf > 0 && mn > 0 && mf + mn <= kPfDrawObsMax;
+        if (mf > 0 || mn > 0)
+        {
+            CSLAM_TRY(ensure_m(together ? mf + mn : std::max(mf, mn)));
+        }
+        if (mf > 0)
+        {
+            CSLAM_TRY(rs.ensure(np, stream));
+        }
+        CSLAM_TRY(launch_control_run(k, v, swa, Qv, wb, dt, phi, use));
+        if (mf == 0)
+        {
+            if (mn == 0)
+            {
+                return CSLAM_OK;
+            }
+            CSLAM_TRY(stage_drawn(ZN, mn, nullptr, step));
+            return launch_new_feature_step(0.0, 0.0, nullptr, 0.0, 0.0, mn, Rv);
+        }
+        const T* R = static_cast<const T*>(Rv);
+        obs.forget();
+        if (together)
+        {
+            T   zz[2 * kPfDrawObsMax];
+            int ii[kPfDrawObsMax];
+            std::memset(ii, 0, sizeof(ii));
+            std::memcpy(zz, ZF, (size_t)2 * mf * sizeof(T));
+            std::memcpy(zz + 2 * mf, ZN, (size_t)2 * mn * sizeof(T));
+            std::memcpy(ii, idf, (size_t)mf * sizeof(int));
+            CSLAM_TRY(launch_draw(step, obs.dNormals(), obs.dSelect(), np, mf + mn, zz, ii));
+        }
+        else
+        {
+            const bool by_copy = mf > kPfDrawObsMax;
+            if (by_copy)
+            {
+                CSLAM_TRY(stage(ZF, mf, idf));
+            }
+            CSLAM_TRY(launch_draw(step, obs.dNormals(), obs.dSelect(), np, by_copy ? 0 : mf, ZF, idf));
+        }
+        // the feature update rides in the proposal unless the list names a feature twice (launch_observation_step)
+        const int fu = pf_has_duplicate(idf, mf) ? 0 : fused_update_gain();
+        CSLAM_TRY(launch_proposal(mf, R, no_predict(), fu));
+        if (fu == 0)
+        {
+            CSLAM_TRY(launch_feature_update(mf, R));
+        }
+        CSLAM_TRY(launch_resample(obs.dSelect(), n_eff, status));
+        if (mn > 0)
+        {
+            const T* zn = obs.z() + 2 * mf;
+            if (!together)
+            {
+                if (mn > kPfDrawObsMax)
+                {
+                    CSLAM_TRY(stage(ZN, mn, nullptr));
+                }
+                else // (a producer launch that only carries Z: no draw is taken)
+                {
+                    CSLAM_TRY(launch_draw(step, nullptr, nullptr, 0, mn, ZN, nullptr));
+                }
+                zn = obs.z();
+            }
+            hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, mn), dim3(64), 0, stream, store(), zn, mn,
+                               R[0], R[1], R[2], R[3]);
+            CSLAM_HIP_TRY(hipGetLastError());
+            nf += mn;
+        }
+        obs.forget(); // (the area holds this cycle's mix, not the Z || idf of one call)
+        return CSLAM_OK;
+    }
+
+    // The control run followed by the body of assoc_scan_step_drawn behind its predict: associate + vote, the proposal on
+    // the vote's mask, the resample with nothing returned, and only then the wait for the vote and its features.
+    int assoc_cycle_drawn(int k, const double* v, const double* swa, const void* Qv, double wb, double dt, const double* phi,
+                          int use, const void* Z, int m, const void* Rv, double gate1, double gate2, double new_fraction,
+                          double miss_likelihood, long long step, double n_eff, int status, int* q_out) override
+    {
+        const char* who = "pf_assoc_cycle_drawn";
+        CSLAM_TRY(check_control(k, v, swa, Qv, phi, use, who));
+        if (m < 0 || m > 65535 || (m > 0 && (!Z || !Rv)) || !std::isfinite(gate1) || !std::isfinite(gate2) ||
+            !std::isfinite(new_fraction) || !std::isfinite(miss_likelihood))
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "%s: bad arguments (m=%d)", who, m);
+        }
+        CSLAM_TRY(need_whole_set(who));
+        CSLAM_TRY(use_device());
+        if (m > 0) // what can fail for want of memory, before anything is launched
+        {
+            CSLAM_TRY(ensure_m(m));
+            CSLAM_TRY(vote.ensure(m, false, stream));
+            CSLAM_TRY(assoc.ensure(m, (nf + kPfAssocFeatChunk - 1) / kPfAssocFeatChunk, np, stream));
+            CSLAM_TRY(rs.ensure(np, stream));
+        }
+        if (q_out)
+        {
+            *q_out = 0;
+        }
+        CSLAM_TRY(launch_control_run(k, v, swa, Qv, wb, dt, phi, use));
+        if (m == 0)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_TRY(associate_vote(nullptr, Z, m, Rv, gate1, gate2, new_fraction));
+        CSLAM_TRY(sample_proposal_voted_drawn(Z, m, Rv, miss_likelihood, step));
+        CSLAM_TRY(resample_local_drawn(step, n_eff, status, nullptr, nullptr));
+        return add_features_voted(Rv, q_out);
+    }
 };
 
 inline PfBase* B(cslam_pf_t h)
@@ -2424,6 +2634,46 @@ int cslam_pf_assoc_scan_step_drawn(cslam_pf_t h, double v, double swa, const voi
     CSLAM_NEED(h);
     return B(h)->assoc_scan_step_drawn(v, swa, Q, wb, dt, Z, m, R, gate1, gate2, new_fraction, miss_likelihood, step,
                                        n_effective, resample_status, q_out);
+}
+
+/* k iterations of test/main.cpp:279-286 (PF.cpp:419-471, 382-417) in one launch per 16 steps */
+int cslam_pf_control_run(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                         const double* phi, int use_heading)
+{
+    CSLAM_NEED(h);
+    return B(h)->control_run(k, v, swa, Q, wb, dt, phi, use_heading);
+}
+
+int cslam_pf_control_launches(cslam_pf_t h, long long* launches)
+{
+    CSLAM_NEED(h);
+    if (!launches)
+    {
+        return fail(CSLAM_ERR_BAD_ARG, "pf_control_launches: null");
+    }
+    *launches = B(h)->control_launches;
+    return CSLAM_OK;
+}
+
+/* test/main.cpp:249-334: the control steps of one iteration block and its scan with known correspondences, in one call */
+int cslam_pf_cycle_drawn(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                         const double* phi, int use_heading, const void* ZF, int mf, const int* idf, const void* ZN, int mn,
+                         const void* R, long long step, double n_effective, int resample_status)
+{
+    CSLAM_NEED(h);
+    return B(h)->cycle_drawn(k, v, swa, Q, wb, dt, phi, use_heading, ZF, mf, idf, ZN, mn, R, step, n_effective,
+                             resample_status);
+}
+
+/* the same with unknown correspondences */
+int cslam_pf_assoc_cycle_drawn(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                               const double* phi, int use_heading, const void* Z, int m, const void* R, double gate1,
+                               double gate2, double new_fraction, double miss_likelihood, long long step,
+                               double n_effective, int resample_status, int* q)
+{
+    CSLAM_NEED(h);
+    return B(h)->assoc_cycle_drawn(k, v, swa, Q, wb, dt, phi, use_heading, Z, m, R, gate1, gate2, new_fraction,
+                                   miss_likelihood, step, n_effective, resample_status, q);
 }
 
 } // extern "C"

@@ -1,9 +1,9 @@
 // pf_host_parts.hpp -- the arithmetic and bookkeeping of the particle handle that needs no GPU: the layout of the device
 // staging area, the memo of what it holds, the validity of the association tables and of the vote on new features, and
-// the small host loops of the fused step, the sharded exchange and the strata table, and the book of the device-side
-// score.  No HIP include:
-// tests/host/pf_host_parts_check.cpp and pf_score_book_check.cpp build it with plain g++ (and under the address and
-// undefined-behaviour sanitizers).
+// the small host loops of the fused step, the sharded exchange and the strata table, the chunk split and the refusal
+// rule of the control run, and the book of the device-side score.  No HIP include:
+// tests/host/pf_host_parts_check.cpp, pf_control_check.cpp and pf_score_book_check.cpp build it with plain g++ (and under
+// the address and undefined-behaviour sanitizers).
 #pragma once
 
 #include <algorithm>
@@ -239,6 +239,52 @@ inline PfNewFeatureRefusal pf_new_feature_check(int q, bool has_Z, bool has_R, b
         return PfNewFeatureRefusal::capacity;
     }
     return PfNewFeatureRefusal::none;
+}
+
+// A run of k control steps (test/main.cpp:279-286) goes out kPfControlChunk steps per launch, the chunks back to back.
+constexpr int kPfControlChunk = 16; // = kPfControlMax of pf_control_kernels.hpp
+
+// launches of a run of k steps (k <= 0: none)
+inline int pf_control_chunks(int k) { return k > 0 ? (k - 1) / kPfControlChunk + 1 : 0; }
+// chunk c of a run of k steps covers steps *first .. *first + *count - 1; false when the run has no chunk c
+inline bool pf_control_chunk(int k, int c, int* first, int* count)
+{
+    if (c < 0 || c >= pf_control_chunks(k))
+    {
+        *first = *count = 0;
+        return false;
+    }
+    *first = c * kPfControlChunk;
+    *count = std::min(kPfControlChunk, k - *first);
+    return true;
+}
+
+// why a control run (cslam_pf_control_run, and the run in front of cslam_pf_cycle_drawn / _assoc_cycle_drawn) is refused
+enum class PfControlRefusal
+{
+    none,
+    bad_k,       // k < 0
+    null_control, // k > 0 without v, swa or Q
+    null_phi     // k > 0 and the heading observed, without phi
+};
+
+// The arguments of a control run of k steps.  With k = 0 nothing is read, so nothing needs to be there; phi is read only
+// when the heading is observed.  A refused run changes nothing.
+inline PfControlRefusal pf_control_check(int k, bool has_v, bool has_swa, bool has_Q, bool has_phi, bool use_heading)
+{
+    if (k < 0)
+    {
+        return PfControlRefusal::bad_k;
+    }
+    if (k > 0 && (!has_v || !has_swa || !has_Q))
+    {
+        return PfControlRefusal::null_control;
+    }
+    if (k > 0 && use_heading && !has_phi)
+    {
+        return PfControlRefusal::null_phi;
+    }
+    return PfControlRefusal::none;
 }
 
 // The record counts of a sharded exchange: hc[r] records go to rank r, hc[world + r] come from it; both buffers hold

@@ -398,6 +398,80 @@ class ParticleShard:
         check(rc)
         return q.value
 
+    # ---- a run of control steps in one launch, and the whole iteration block in one call (test/main.cpp:249-334)
+    def _controls(self, v, swa, Q, wb, dt, phi, use_heading):
+        """-> (arrays kept alive, the C arguments k, v, swa, Q, wb, dt, phi, use_heading).  v and swa: scalars or
+        sequences of equal length (a scalar is broadcast to the other's length); a scalar phi is broadcast."""
+        va, sa = np.atleast_1d(np.asarray(v, np.float64)), np.atleast_1d(np.asarray(swa, np.float64))
+        k = max(va.shape[0], sa.shape[0]) if va.size and sa.size else 0
+        if np.ndim(v) == 0:
+            va = np.full(k, float(v))
+        if np.ndim(swa) == 0:
+            sa = np.full(k, float(swa))
+        assert va.shape == sa.shape == (k,), "v and swa: scalars or sequences of equal length"
+        va, sa = np.ascontiguousarray(va), np.ascontiguousarray(sa)
+        pa = None
+        if phi is not None:
+            pa = np.full(k, float(phi)) if np.ndim(phi) == 0 else np.ascontiguousarray(phi, dtype=np.float64)
+            assert pa.shape == (k,), "phi: a scalar or one value per control step"
+        Qc = None if Q is None else self._m22(Q)
+        keep = (va, sa, pa, Qc)
+        return keep, (C.c_int(k), _vp(va), _vp(sa), _vp(Qc) if Qc is not None else None, C.c_double(float(wb)),
+                      C.c_double(float(dt)), _vp(pa) if pa is not None else None, C.c_int(1 if use_heading else 0))
+
+    def control_run(self, v, swa, Q, wb, dt, phi=None, use_heading=False):
+        """k x (predict(v[j], swa[j], Q, wb, dt); observe_heading(phi[j], use_heading)) for every owned particle -- k
+        iterations of test/main.cpp:279-286 -- bit for bit, in one launch per 16 steps (cslam_pf_control_run)."""
+        keep, args = self._controls(v, swa, Q, wb, dt, phi, use_heading)
+        check(self._L.cslam_pf_control_run(self._h, *args))
+
+    def control_launches(self) -> int:
+        """Control-run kernel launches of this shard so far (cslam_pf_control_launches)."""
+        n = C.c_longlong(0)
+        check(self._L.cslam_pf_control_launches(self._h, C.byref(n)))
+        return n.value
+
+    def cycle_drawn(self, v, swa, Q, wb, dt, ZF, idf, ZN, R, step: int, n_effective: float, resample_status: bool,
+                    phi=None, use_heading=False):
+        """One iteration block of the reference's loop on a shard that holds the whole seeded set, in one C call
+        (cslam_pf_cycle_drawn): control_run over all of v / swa / phi, then the scan without a predict of its own.  Known
+        features seen (ZF, idf): sample_proposal_drawn, feature_update, resample_local_drawn with nothing returned, then
+        add_features(ZN).  Only new ones: new_feature_step_drawn(Q=None).  Neither: the control run alone."""
+        keep, args = self._controls(v, swa, Q, wb, dt, phi, use_heading)
+        ZFc, mf = self._z(ZF if ZF is not None else [])
+        ZNc, mn = self._z(ZN if ZN is not None else [])
+        idf = np.ascontiguousarray(idf if mf else [], dtype=np.int32)
+        Rc = None if R is None else self._m22(R)
+        check(self._L.cslam_pf_cycle_drawn(self._h, *args, _vp(ZFc), C.c_int(mf), _vp(idf) if mf else None, _vp(ZNc),
+                                           C.c_int(mn), _vp(Rc) if Rc is not None else None, C.c_longlong(int(step)),
+                                           C.c_double(float(n_effective)), C.c_int(1 if resample_status else 0)))
+
+    def assoc_cycle_drawn(self, v, swa, Q, wb, dt, Z, R, gate1, gate2, step: int, n_effective: float,
+                          resample_status: bool, phi=None, use_heading=False, new_fraction=0.5,
+                          miss_likelihood=1.0) -> int:
+        """The same with unknown correspondences (cslam_pf_assoc_cycle_drawn): control_run, then associate_vote,
+        sample_proposal_voted_drawn, resample_local_drawn with nothing returned, add_features_voted -> q.  No
+        observations: the control run alone."""
+        keep, args = self._controls(v, swa, Q, wb, dt, phi, use_heading)
+        Zc, m = self._z(Z)
+        q = C.c_int(0)
+        had_assoc, had_cap = getattr(self, "_assoc_m", None), getattr(self, "_vote_cap", 1)
+        if m:
+            self._assoc_m = None
+            self._vote_cap = max(m, had_cap)
+        Rc = None if R is None else self._m22(R)
+        rc = self._L.cslam_pf_assoc_cycle_drawn(
+            self._h, *args, _vp(Zc), C.c_int(m), _vp(Rc) if Rc is not None else None, C.c_double(float(gate1)),
+            C.c_double(float(gate2)), C.c_double(float(new_fraction)), C.c_double(float(miss_likelihood)),
+            C.c_longlong(int(step)), C.c_double(float(n_effective)), C.c_int(1 if resample_status else 0), C.byref(q))
+        if m and rc in (_capi.OK, _capi.ERR_CAPACITY):  # (on a capacity overflow the scan ran and its vote is live)
+            self._assoc_m = m
+            self._voted(m)
+        elif m:  # (refused before anything was launched: the tables are those of before)
+            self._assoc_m = had_assoc
+        check(rc)
+        return q.value
+
     # ---- pieces of the resample step
     def weight_sums(self) -> Tuple[float, float]:
         s = (C.c_double * 2)()

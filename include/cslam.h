@@ -772,6 +772,55 @@ int cslam_pf_assoc_scan_step_drawn(cslam_pf_t h, double v, double swa, const voi
                                    int m, const void* R, double gate1, double gate2, double new_fraction,
                                    double miss_likelihood, long long step, double n_effective, int resample_status,
                                    int* q_out);
+
+/* ---- a run of control steps in one launch, and whole-cycle calls ----
+ * Between two scans the reference's particle loop (test/main.cpp:249-334) runs about six control steps
+ * (mDtObserve = 5.058 mDtControls, slam.h:69-77), each of them PF::predict then PF::observeHeading for every particle
+ * (test/main.cpp:279-286); mSwitchHeadingKnown is true by default (slam.h:99).
+ *
+ * cslam_pf_control_run       replaces k iterations of test/main.cpp:279-286 for every owned particle: bit for bit the
+ *                            result of k x (cslam_pf_predict(v[j], swa[j], Q, wb, dt) -- PF.cpp:419-471;
+ *                            cslam_pf_observe_heading(phi[j], use_heading) -- PF.cpp:382-417, slam.h:700-725), with ONE
+ *                            launch per 16 steps (the chunks of a longer run are queued back to back) and the pose state
+ *                            loaded and stored once per launch.  v, swa, phi: k host doubles each, cast to the handle's
+ *                            dtype as the single calls cast theirs; phi may be NULL when use_heading = 0.  Works on any
+ *                            shard, needs no draws, is asynchronous as cslam_pf_predict is, and leaves the staging area,
+ *                            the association tables and the vote exactly as cslam_pf_predict leaves them.  k = 0 returns
+ *                            CSLAM_OK and launches nothing.  k < 0, a NULL v, swa or Q with k > 0, or a NULL phi with
+ *                            k > 0 and use_heading != 0: CSLAM_ERR_BAD_ARG, nothing changes.
+ * cslam_pf_control_launches  introspection: control-run kernel launches of this handle so far (a host-side counter), so
+ *                            that a test can hold "one launch per 16 steps".
+ * cslam_pf_cycle_drawn       one whole iteration block of test/main.cpp:249-334 with known correspondences, for a handle
+ *                            that holds the whole seeded set (the preconditions of cslam_pf_resample_local_drawn): the
+ *                            control run of ALL k steps (test/main.cpp:279-286), then the scan of test/main.cpp:294-328
+ *                            without a predict of its own.  mf > 0: bit for bit cslam_pf_sample_proposal_drawn(ZF, mf,
+ *                            idf, R, step) (PF.cpp:502-544), cslam_pf_feature_update(ZF, mf, idf, R) (PF.cpp:222-277),
+ *                            cslam_pf_resample_local_drawn(step) with nothing returned (PF.cpp:473-500), then
+ *                            cslam_pf_add_features(ZN, mn, R) (PF.cpp:9-60).  mf = 0 and mn > 0:
+ *                            cslam_pf_new_feature_step_drawn(ZN, mn, R, step) with Q = NULL (test/main.cpp:314-328; any
+ *                            shard of a seeded set will do).  mf = mn = 0: the control run alone.  With mf <= 32 and
+ *                            mn <= 32 the call enqueues no copy command (cslam_pf_stage_copies does not move).
+ *                            Everything that can refuse is checked BEFORE the control run is launched -- what
+ *                            cslam_pf_control_run refuses, an unseeded handle or a shard of a larger set, idf outside
+ *                            1..nf, NULL arrays: CSLAM_ERR_BAD_ARG; nf + mn > max_features: CSLAM_ERR_CAPACITY -- and a
+ *                            refused cycle changes nothing.
+ * cslam_pf_assoc_cycle_drawn the same with unknown correspondences: the control run (test/main.cpp:279-286), then the body
+ *                            of cslam_pf_assoc_scan_step_drawn behind its predict -- cslam_pf_associate_vote
+ *                            (EKF.cpp:131-144, 235-326), cslam_pf_sample_proposal_voted_drawn(step) (PF.cpp:502-544 +
+ *                            222-277), cslam_pf_resample_local_drawn(step) (PF.cpp:473-500), cslam_pf_add_features_voted
+ *                            (PF.cpp:9-60) -- with its return values, its *q, and its rule that a capacity overflow
+ *                            leaves the run, the proposal and the resample applied and the vote live.  m = 0 is the
+ *                            control run alone (*q = 0). */
+int cslam_pf_control_run(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                         const double* phi /* k or NULL */, int use_heading);
+int cslam_pf_control_launches(cslam_pf_t h, long long* launches);
+int cslam_pf_cycle_drawn(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                         const double* phi, int use_heading, const void* ZF, int mf, const int* idf, const void* ZN, int mn,
+                         const void* R, long long step, double n_effective, int resample_status);
+int cslam_pf_assoc_cycle_drawn(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                               const double* phi, int use_heading, const void* Z, int m, const void* R, double gate1,
+                               double gate2, double new_fraction, double miss_likelihood, long long step,
+                               double n_effective, int resample_status, int* q);
 /* download one particle (host buffers; any may be NULL): w (1), Xv (3), Pv (9), XF (2*nf), PF (4*nf) */
 int cslam_pf_get_particle(cslam_pf_t h, int index, void* w, void* Xv, void* Pv, void* XF, void* PF);
 /* upload one particle with nf features (nf must equal the current feature count, or set it when the

@@ -32,6 +32,9 @@
 //                            test/main.cpp:279-328 without its table: EKF.cpp:131-144, 235-326 per particle, the vote on
 //                            new features kept on the device)         -> cslam_pf_associate_vote / _sample_proposal_voted_drawn
 //                                                                       / _add_features_voted / _assoc_scan_step_drawn
+//   HipPF::controlRunAll / cycleAll / cycleUnknownAll   (the control steps between two scans, test/main.cpp:279-286, in one
+//                            launch per 16, and the whole iteration block of test/main.cpp:249-334 in one call)
+//                                                                    -> cslam_pf_control_run / _cycle_drawn / _assoc_cycle_drawn
 //
 // Ownership: the reference passes X and P by reference into every call; here the handle owns them in HBM.  X is
 // refreshed after every call (the driver reads it every iteration, test/main.cpp:136); P is refreshed on demand
@@ -539,6 +542,87 @@ class HipPF : public PF
         return q;
     }
 
+    // ---- a run of control steps in one launch, and the whole iteration block of test/main.cpp:249-334 in one call
+    /// k = v.rows() iterations of test/main.cpp:279-286 for every owned particle -- predict(v[j], swa[j], Q, wb, dt)
+    /// (PF.cpp:419-471) then observeHeading(phi[j], useHeading) (PF.cpp:382-417) -- bit for bit, in one launch per 16
+    /// steps.  phi may be empty when useHeading is false.
+    void controlRunAll(const Eigen::VectorXf& v, const Eigen::VectorXf& swa, const Eigen::MatrixXf& Q, const float& wb,
+                       const float& dt, const Eigen::VectorXf& phi, bool useHeading = false)
+    {
+        std::vector<double> c;
+        if (controls(v, swa, phi, useHeading, c, "controlRun"))
+        {
+            const int k = static_cast<int>(v.rows());
+            report(cslam_pf_control_run(h_, k, c.data(), c.data() + k, Q.data(), wb, dt, useHeading ? c.data() + 2 * k : nullptr,
+                                        useHeading ? 1 : 0),
+                   "HipPF::controlRun");
+        }
+    }
+    /// One iteration block of the reference's loop with mSwitchHeadingKnown as the caller has it: ALL the control steps
+    /// since the last scan (the last one included), then the scan without a predict of its own, every random input of the
+    /// step set with setStep() drawn on the device (needs seedDraws()).  ZF / idf / ZN as scanStepAll takes them.
+    void cycleAll(const Eigen::VectorXf& v, const Eigen::VectorXf& swa, const Eigen::MatrixXf& Q, const float& wb,
+                  const float& dt, const Eigen::VectorXf& phi, bool useHeading, const Eigen::MatrixXf& ZF,
+                  const Eigen::VectorXi& idf, const Eigen::MatrixXf& ZN, const Eigen::MatrixXf& R, int numEffective,
+                  bool resampleStatus = false)
+    {
+        const int mf = static_cast<int>(ZF.cols()), mn = static_cast<int>(ZN.cols());
+        if (comm_ == nullptr)
+        {
+            std::vector<double> c;
+            if (controls(v, swa, phi, useHeading, c, "cycle"))
+            {
+                const int k = static_cast<int>(v.rows());
+                report(cslam_pf_cycle_drawn(h_, k, c.data(), c.data() + k, Q.data(), wb, dt,
+                                            useHeading ? c.data() + 2 * k : nullptr, useHeading ? 1 : 0, ZF.data(), mf,
+                                            idf.data(), ZN.data(), mn, R.data(), step_, numEffective, resampleStatus ? 1 : 0),
+                       "HipPF::cycle");
+            }
+            return;
+        }
+        // a sharded set: the run, then the same calls one by one, the resample over the communicator (as scanStepAll)
+        controlRunAll(v, swa, Q, wb, dt, phi, useHeading);
+        if (mf > 0)
+        {
+            double neff      = 0.0;
+            int    resampled = 0;
+            sampleProposalAll(ZF, idf, R);
+            featureUpdateAll(ZF, idf, R);
+            report(cslam_pf_resample_sharded_drawn(h_, comm_, step_, numEffective, resampleStatus ? 1 : 0, &neff, &resampled),
+                   "HipPF::cycle");
+            lastNeff_      = static_cast<float>(neff);
+            lastResampled_ = resampled != 0;
+            if (mn > 0)
+            {
+                addNewFeaturesAll(ZN, R);
+            }
+        }
+        else if (mn > 0)
+        {
+            addNewFeaturesSampledAll(ZN, R);
+        }
+    }
+    /// The same WITHOUT the table of test/main.cpp:300, for a set held by one handle: the control steps, then the body of
+    /// scanStepUnknownAll behind its predict.  Returns the number of features added.  No observations: the run alone.
+    int cycleUnknownAll(const Eigen::VectorXf& v, const Eigen::VectorXf& swa, const Eigen::MatrixXf& Q, const float& wb,
+                        const float& dt, const Eigen::VectorXf& phi, bool useHeading, const Eigen::MatrixXf& Z,
+                        const Eigen::MatrixXf& R, float gate1, float gate2, int numEffective, bool resampleStatus = false,
+                        float newFraction = 0.5f, float missLikelihood = 1.0f)
+    {
+        int                 q = 0;
+        std::vector<double> c;
+        if (controls(v, swa, phi, useHeading, c, "cycleUnknown"))
+        {
+            const int k = static_cast<int>(v.rows());
+            report(cslam_pf_assoc_cycle_drawn(h_, k, c.data(), c.data() + k, Q.data(), wb, dt,
+                                              useHeading ? c.data() + 2 * k : nullptr, useHeading ? 1 : 0, Z.data(),
+                                              static_cast<int>(Z.cols()), R.data(), gate1, gate2, newFraction, missLikelihood,
+                                              step_, numEffective, resampleStatus ? 1 : 0, &q),
+                   "HipPF::cycleUnknown");
+        }
+        return q;
+    }
+
     /// the strata positions of PF.cpp:557 (stratifiedRandom): supplied by the caller so that runs are reproducible
     /// (the reference seeds from the clock, slam.h:587-594); when a communicator is set, `select` has one entry per
     /// particle of the WHOLE set (numParticles x ranks) and must be identical on every rank
@@ -756,6 +840,27 @@ class HipPF : public PF
             {
                 nrm[static_cast<size_t>(e) * static_cast<size_t>(np_) + static_cast<size_t>(p)] = normals(e, p);
             }
+        }
+        return true;
+    }
+    // the per-step controls of a run as the engine takes them: c = v[k] | swa[k] | phi[k] in double (a float widens
+    // exactly, so the engine's cast to its own dtype gives the caller's float back)
+    static bool controls(const Eigen::VectorXf& v, const Eigen::VectorXf& swa, const Eigen::VectorXf& phi, bool useHeading,
+                         std::vector<double>& c, const char* who)
+    {
+        const int k = static_cast<int>(v.rows());
+        if (static_cast<int>(swa.rows()) != k || (useHeading && static_cast<int>(phi.rows()) != k))
+        {
+            std::cout << "HipPF::" << who << ": v, swa and (with the heading known) phi need one value per step\t" << who
+                      << std::endl;
+            return false;
+        }
+        c.assign(static_cast<size_t>(3 * k) + 1, 0.0); // (+ 1: data() of an empty run is still an address)
+        for (int j = 0; j < k; j++)
+        {
+            c[static_cast<size_t>(j)]         = v(j);
+            c[static_cast<size_t>(k + j)]     = swa(j);
+            c[static_cast<size_t>(2 * k + j)] = useHeading ? phi(j) : 0.0f;
         }
         return true;
     }
