@@ -38,6 +38,7 @@ struct PfBase
     int         dtype  = CSLAM_F32;
     int         device = 0;
     int         quirks = CSLAM_Q_REF_EXACT;
+    int         report_degenerate = 0; // cslam_pf_set_degenerate_policy
     int         np     = 0;
     int         nfcap  = 0;
     int         nf     = 0;
@@ -54,6 +55,8 @@ struct PfBase
     virtual int add_features(const void* Z, int q, const void* R)                             = 0;
     virtual int weight_sums(double* sums)                                                     = 0;
     virtual int scale_weights(double scale)                                                   = 0;
+    virtual int set_degenerate_policy(int report)                                             = 0;
+    virtual int divide_weights(double ws)                                                     = 0;
     virtual int weights_ptr(void** p)                                                         = 0;
     virtual int get_weights(void* w)                                                          = 0;
     virtual int set_weights(const void* w)                                                    = 0;
@@ -252,6 +255,25 @@ struct Pf : PfBase
         CSLAM_HIP_TRY(hipGetLastError());
         return CSLAM_OK;
     }
+    // wv[0..n) /= ws
+    int launch_divide_weights(T* wv, int n, double ws)
+    {
+        hipLaunchKernelGGL(pf_divide_weights_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, wv, n, ws);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
+    // wv[0..n) normalised by the weight sum ws as the plan kernel does it (PF.cpp:482-487): by the scale (T)(1 / ws)
+    // where that is a normal number of T, else by division (pf_kernels.hpp, at pf_scale_is_normal)
+    int launch_normalize(T* wv, int n, double ws)
+    {
+        if (!pf_use_scale<T>(ws, report_degenerate))
+        {
+            return launch_divide_weights(wv, n, ws);
+        }
+        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, stream, wv, n, (T)(1.0 / ws), 0);
+        CSLAM_HIP_TRY(hipGetLastError());
+        return CSLAM_OK;
+    }
     int launch_pack(const int* d_idx, int count, T* d_rec)
     {
         hipLaunchKernelGGL(pf_pack_kernel<T>, dim3(count), dim3(256), 0, stream, store(), d_idx, count, d_rec);
@@ -407,6 +429,22 @@ struct Pf : PfBase
     {
         CSLAM_TRY(use_device());
         return launch_scale_weights(scale, 0);
+    }
+
+    int set_degenerate_policy(int report) override
+    {
+        if (report != 0 && report != 1)
+        {
+            return fail(CSLAM_ERR_BAD_ARG, "pf_set_degenerate_policy: %d is neither CSLAM_PF_REPAIR nor CSLAM_PF_REPORT", report);
+        }
+        report_degenerate = report;
+        return CSLAM_OK;
+    }
+
+    int divide_weights(double ws) override
+    {
+        CSLAM_TRY(use_device());
+        return launch_divide_weights(dW.get(), np, ws);
     }
 
     int weights_ptr(void** p) override
@@ -624,10 +662,23 @@ struct Pf : PfBase
         CSLAM_HIP_TRY(hipMemcpyAsync(hs, sh.plan.sumsG.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
         CSLAM_HIP_TRY(hipStreamSynchronize(stream));
         const double ws = hs[0], ws2 = hs[1];
-        // 2. w /= ws (PF.cpp:482-487), Neff = 1 / sum (w/ws)^2 (PF.cpp:549-554), the decision (PF.cpp:490)
-        CSLAM_TRY(launch_scale_weights(1.0 / ws, 0));
-        const double ne = (ws2 > 0.0) ? (ws * ws) / ws2 : 0.0;
-        const bool   go = (ne < n_eff) && status;
+        // 2. w /= ws (PF.cpp:482-487), Neff = 1 / sum (w/ws)^2 (PF.cpp:549-554), the decision (PF.cpp:490); as the plan
+        // kernel does at the ends of the range: Neff from the sums of the normalised weights where the raw squares have
+        // left the range of double (f64 only)
+        CSLAM_TRY(launch_normalize(dW.get(), np, ws));
+        double ne = pf_neff_raw(ws, ws2, report_degenerate);
+        bool   wall_normalised = false;
+        if (sizeof(T) == 8 && pf_sum_usable(ws) && !pf_neff_from_raw_sums(ws, ws2))
+        {
+            CSLAM_TRY(launch_normalize(wall, N, ws));
+            wall_normalised = true;
+            hipLaunchKernelGGL(pf_weight_sums_kernel<T>, dim3(1), dim3(256), 0, stream, wall, N, sh.plan.sumsG.get());
+            CSLAM_HIP_TRY(hipGetLastError());
+            CSLAM_HIP_TRY(hipMemcpyAsync(hs, sh.plan.sumsG.get(), 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+            ne = (hs[0] * hs[0]) / hs[1];
+        }
+        const bool go = (ne < n_eff) && status;
         if (neff)
         {
             *neff = ne;
@@ -643,8 +694,10 @@ struct Pf : PfBase
             return CSLAM_OK;
         }
         // 3. every rank plans the same keep[] from the gathered weights, normalised as its own were, and the shared strata
-        hipLaunchKernelGGL(pf_scale_weights_kernel<T>, dim3((N + 255) / 256), dim3(256), 0, stream, wall, N, (T)(1.0 / ws), 0);
-        CSLAM_HIP_TRY(hipGetLastError());
+        if (!wall_normalised)
+        {
+            CSLAM_TRY(launch_normalize(wall, N, ws));
+        }
         hipLaunchKernelGGL(pf_keep_kernel<T>, dim3(1), dim3(256), 0, stream, wall, N, sh.plan.selG.get(),
                            sh.plan.keepG.get(), sh.plan.cumG.get());
         CSLAM_HIP_TRY(hipGetLastError());
@@ -737,7 +790,7 @@ struct Pf : PfBase
     {
         assoc.memo.moved(); // (whether it resamples is decided on the device)
         hipLaunchKernelGGL(pf_resample_plan_kernel<T>, dim3(1), dim3(256), 0, stream, dW.get(), np, d_select, n_eff,
-                           status, rs.cum.get(), rs.keep.get(), rs.info.get(), rs.enable.get());
+                           status, rs.cum.get(), rs.keep.get(), rs.info.get(), rs.enable.get(), report_degenerate);
         CSLAM_HIP_TRY(hipGetLastError());
         const dim3 ggrid(13 + 6 * nf, (np + 255) / 256);
         const T    w_new = (T)(1.0 / (double)np);
@@ -2130,6 +2183,18 @@ int cslam_pf_scale_weights(cslam_pf_t h, double scale)
 {
     CSLAM_NEED(h);
     return B(h)->scale_weights(scale);
+}
+
+int cslam_pf_set_degenerate_policy(cslam_pf_t h, int policy)
+{
+    CSLAM_NEED(h);
+    return B(h)->set_degenerate_policy(policy);
+}
+
+int cslam_pf_divide_weights(cslam_pf_t h, double ws)
+{
+    CSLAM_NEED(h);
+    return B(h)->divide_weights(ws);
 }
 
 int cslam_pf_weights_device_ptr(cslam_pf_t h, void** dptr)

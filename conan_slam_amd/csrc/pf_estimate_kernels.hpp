@@ -30,11 +30,11 @@ namespace cslam
 {
 
 constexpr int kEstChunk      = 1024; // particles per workgroup (4 per thread)
-constexpr int kEstP1         = 10;   // doubles per pass-1 partial
+constexpr int kEstP1         = 12;   // doubles per pass-1 partial: 6 sums, 2 x (best weight, index), 2 scaled sums of squares (f64)
 constexpr int kEstP2Pose     = 12;   // doubles per pass-2 pose partial: S1 (3), S2 (9, column-major)
 constexpr int kEstP2Feat     = 6;    // doubles per (chunk, feature): S1 (2), S2 (4, column-major)
 constexpr int kEstFeatPerWg  = 4;    // one wave per feature
-constexpr int kEstSumHdr     = 24;   // doubles of a rank summary before its features: W, W2, Ssin, Scos, r(3), S1(3), S2(9)
+constexpr int kEstSumHdr     = 24;   // doubles of a rank summary before its features: W, W2, Ssin, Scos, r(3), S1(3), S2(9), W2 up, W2 down
 constexpr int kEstSumFeat    = 6;    // per feature: mean (2), centred second moment (4)
 constexpr int kEstOutHdr     = 8;    // doubles in front of the T record of an output block: w_sum, neff, index, found
 constexpr int kEstPickMax    = 0;
@@ -118,6 +118,41 @@ __device__ inline void est_pose_mean(const EstTotals& t, double x0, double y0, d
     m[2] = atan2(t.Ss, t.Sc);
 }
 
+// Neff = W^2 / sum w^2.  f64 weights beyond 2^-511 .. 2^512 take their squares out of the range of double although W and
+// every moment are fine, so an f64 set also carries the sums of the squares of 2^512 w and of 2^-512 w (fixed scales:
+// partials and rank summaries add as they are).  Whenever W^2 and sum w^2 are normal numbers Neff is formed from them as
+// ever -- and since a power of two scales every term, every partial sum and W^2 exactly, the other two forms would give
+// the same bits there.  f32 weights never leave that range (their squares span 2^-298 .. 2^256).
+constexpr double kEstUp = 0x1p+512, kEstDown = 0x1p-512;
+
+__device__ inline double est_neff(double W, double W2, double W2u, double W2d, bool wide)
+{
+    if (!wide || (W2 >= 2.2250738585072014e-308 && W2 <= 1.7976931348623157e+308 && W * W <= 1.7976931348623157e+308))
+    {
+        return (W * W) / W2;
+    }
+    if (W2 < 2.2250738585072014e-308)
+    {
+        const double Wu = W * kEstUp;
+        return (Wu * Wu) / W2u;
+    }
+    const double Wd = W * kEstDown;
+    return (Wd * Wd) / W2d;
+}
+
+// the scaled sums of squares of the pass-1 partials added in chunk order
+__device__ inline void est_wide_squares(const double* __restrict__ part1, int nchunks, double* up, double* down)
+{
+    double u = 0.0, d = 0.0;
+    for (int c = 0; c < nchunks; c++)
+    {
+        u += part1[(size_t)c * kEstP1 + 10];
+        d += part1[(size_t)c * kEstP1 + 11];
+    }
+    *up   = u;
+    *down = d;
+}
+
 __device__ inline bool est_degenerate(double W)
 {
     return !(W > 0.0) || !isfinite(W);
@@ -134,6 +169,7 @@ __global__ void __launch_bounds__(256) pf_est_pass1_kernel(PfStore<T> s, double*
     const int    base = blockIdx.x * kEstChunk, end = min(base + kEstChunk, np);
     const double x0 = (double)s.xv[0], y0 = (double)s.xv[np];
     double       acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double       sq[2]  = {0.0, 0.0}; // (f64) sums of the squares of 2^512 w and 2^-512 w: est_neff
     double       bw[2]  = {0.0, 0.0};
     int          bi[2]  = {-1, -1};
     for (int p = base + (int)threadIdx.x; p < end; p += 256)
@@ -146,6 +182,12 @@ __global__ void __launch_bounds__(256) pf_est_pass1_kernel(PfStore<T> s, double*
         acc[3] += w * (y - y0);
         acc[4] += w * sin(phi);
         acc[5] += w * cos(phi);
+        if (sizeof(T) == 8)
+        {
+            const double wu = w * kEstUp, wd = w * kEstDown;
+            sq[0] += wu * wu;
+            sq[1] += wd * wd;
+        }
         if (w == w)
         {
 #pragma unroll
@@ -161,6 +203,15 @@ __global__ void __launch_bounds__(256) pf_est_pass1_kernel(PfStore<T> s, double*
     }
     double* out = part1 + (size_t)blockIdx.x * kEstP1;
     est_block_sum<6>(acc, s_red, out);
+    if (sizeof(T) == 8)
+    {
+        __shared__ double s_sq[4 * 2];
+        est_block_sum<2>(sq, s_sq, out + 10);
+    }
+    else if (threadIdx.x < 2)
+    {
+        out[10 + threadIdx.x] = 0.0;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 2; k++)
@@ -292,7 +343,7 @@ __device__ inline void est_write_pose(const double* __restrict__ h, bool bad, do
 {
     const double nan = __builtin_nan("");
     out_hdr[0]       = h[0];
-    out_hdr[1]       = bad ? nan : (h[0] * h[0]) / h[1];
+    out_hdr[1]       = bad ? nan : est_neff(h[0], h[1], h[19], h[20], sizeof(T) == 8);
 #pragma unroll
     for (int i = 0; i < 3; i++)
     {
@@ -353,7 +404,8 @@ __global__ void __launch_bounds__(256) pf_est_finish_kernel(PfStore<T> s, const 
             {
                 h[7 + k] = s_pose[k];
             }
-            for (int k = 19; k < kEstSumHdr; k++)
+            est_wide_squares(part1, nchunks, &h[19], &h[20]);
+            for (int k = 21; k < kEstSumHdr; k++)
             {
                 h[k] = 0.0;
             }
@@ -464,6 +516,8 @@ __global__ void __launch_bounds__(256) pf_est_combine_kernel(const double* __res
             }
             h[0] = Wab;
             h[1] += b[1];
+            h[19] += b[19];
+            h[20] += b[20];
             h[2] = Ss;
             h[3] = Sc;
         }

@@ -999,6 +999,89 @@ __global__ void __launch_bounds__(256) pf_scale_weights_kernel(T* __restrict__ w
     }
 }
 
+// ---- the normalisation w / ws (PF.cpp:482-487) over the whole range of the weight sum.
+// A healthy sum normalises as ever by w * (T)(1 / ws).  That scale overflows T for ws <= 2^-128 (f32; 2^-1024 for f64:
+// inf * w, and inf * 0 = NaN) and is a subnormal of T, short of bits, for ws > 2^126 (2^1022), so whenever it is not a
+// NORMAL number of T the weights are divided instead: (T)((double)w / ws), one rounding (for f32 the quotient rounded to
+// double first is innocuous: 53 >= 2 * 24 + 2).
+// A sum that is NOT a positive finite double (0 after total underflow, a NaN or +inf weight): with the handle's degenerate
+// policy on REPORT the weights are divided as well, which leaves the IEEE quotients w / ws (NaN, or 0 under an infinite
+// sum), Neff is NaN and nothing resamples -- the reference's arithmetic (PF.cpp:482-490: NaN < n is false).  With the policy
+// on REPAIR (the default for now) the former arithmetic runs bit for bit: the scale (T)(1 / ws),
+// Neff = 0, every slot resampled onto particle 0.
+// The same functions decide on the device (plan kernel) and on the host (sharded call); pf.py restates the rule.
+template <typename T>
+struct PfRange;
+template <>
+struct PfRange<float>
+{
+    static constexpr float tiny = 1.17549435e-38f, huge = 3.40282347e+38f; // smallest normal, largest finite
+};
+template <>
+struct PfRange<double>
+{
+    static constexpr double tiny = 2.2250738585072014e-308, huge = 1.7976931348623157e+308;
+};
+
+__host__ __device__ inline bool pf_sum_usable(double ws)
+{
+    return ws > 0.0 && ws <= PfRange<double>::huge; // (false for NaN)
+}
+
+template <typename T>
+__host__ __device__ inline bool pf_scale_is_normal(double ws)
+{
+    if (!pf_sum_usable(ws)) // (first: no out-of-range double is ever converted to T)
+    {
+        return false;
+    }
+    const double scale = 1.0 / ws;
+    return scale >= (double)PfRange<T>::tiny && scale <= (double)PfRange<T>::huge;
+}
+
+// multiply by (T)(1 / ws) -- or divide (positive finite sums whose scale is no normal number of T; a degenerate sum that
+// is to be reported)
+template <typename T>
+__host__ __device__ inline bool pf_use_scale(double ws, int report)
+{
+    return pf_scale_is_normal<T>(ws) || (!pf_sum_usable(ws) && !report);
+}
+
+// Neff of a resample call from the raw sums: NaN for a degenerate sum that is to be reported
+__host__ __device__ inline double pf_neff_raw(double ws, double ws2, int report)
+{
+    if (report && !pf_sum_usable(ws))
+    {
+        return __builtin_nan("");
+    }
+    return (ws2 > 0.0) ? (ws * ws) / ws2 : 0.0;
+}
+
+template <typename T>
+__host__ __device__ inline T pf_divide_weight(T w, double ws)
+{
+    return (T)((double)w / ws);
+}
+
+// Neff = ws^2 / sum w^2 from the raw sums (PF.cpp:549-554) is what every healthy run computes.  In f64 the squares leave
+// the range of double long before the weights do (ws < 2^-511 or > 2^512); Neff then comes from the sums of the
+// NORMALISED weights, formed by the same reduction.  f32 weights never get there (their squares span 2^-298 .. 2^256).
+__host__ __device__ inline bool pf_neff_from_raw_sums(double ws, double ws2)
+{
+    return ws2 >= PfRange<double>::tiny && ws2 <= PfRange<double>::huge && ws * ws <= PfRange<double>::huge;
+}
+
+// w = w / ws where pf_use_scale says no (else the caller launches pf_scale_weights_kernel with (T)(1 / ws))
+template <typename T>
+__global__ void __launch_bounds__(256) pf_divide_weights_kernel(T* __restrict__ w, int np, double ws)
+{
+    int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < np)
+    {
+        w[i] = pf_divide_weight<T>(w[i], ws);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // PF::resampleParticles (PF.cpp:473-500) with stratifiedResample (PF.cpp:546-574) for ONE shard holding the whole
 // particle set, entirely on the device: weight sums (same reduction as pf_weight_sums_kernel), normalisation,
@@ -1092,15 +1175,12 @@ __device__ __forceinline__ int pf_first_above(const __attribute__((address_space
     return (lo < np) ? lo : 0;
 }
 
+// s1[0] = sum w, s2[0] = sum w^2 in double: the reduction of pf_weight_sums_kernel (same order, same bits).  Called by
+// every thread of the one workgroup of 256.
 template <typename T>
-__global__ void __launch_bounds__(256) pf_resample_plan_kernel(T* __restrict__ w, int np, const T* __restrict__ select,
-                                                                double n_effective, int resample_status,
-                                                                T* __restrict__ cum, int* __restrict__ keep,
-                                                                double* __restrict__ info, int* __restrict__ enable)
+__device__ __forceinline__ void pf_plan_sums(const T* w, int np, double* s1, double* s2)
 {
-    __shared__ double s1[256], s2[256];
-    __shared__ int    s_do;
-    double            a = 0.0, b = 0.0;
+    double a = 0.0, b = 0.0;
     for (int i = threadIdx.x; i < np; i += 256)
     {
         double x = (double)w[i];
@@ -1119,14 +1199,44 @@ __global__ void __launch_bounds__(256) pf_resample_plan_kernel(T* __restrict__ w
         }
         __syncthreads();
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) pf_resample_plan_kernel(T* __restrict__ w, int np, const T* __restrict__ select,
+                                                                double n_effective, int resample_status,
+                                                                T* __restrict__ cum, int* __restrict__ keep,
+                                                                double* __restrict__ info, int* __restrict__ enable,
+                                                                int report)
+{
+    __shared__ double s1[256], s2[256];
+    __shared__ int    s_do;
+    pf_plan_sums<T>(w, np, s1, s2);
     const double ws = s1[0], ws2r = s2[0];
-    const T      scale = (T)(1.0 / ws); // PF.cpp:482-487
-    for (int i = threadIdx.x; i < np; i += 256)
+    // PF.cpp:482-487; (workgroup-uniform) by division where the sum is fine and the scale is no normal number of T
+    if (pf_use_scale<T>(ws, report))
     {
-        w[i] = w[i] * scale;
+        const T scale = (T)(1.0 / ws);
+        for (int i = threadIdx.x; i < np; i += 256)
+        {
+            w[i] = w[i] * scale;
+        }
+    }
+    else
+    {
+        for (int i = threadIdx.x; i < np; i += 256)
+        {
+            w[i] = pf_divide_weight<T>(w[i], ws);
+        }
     }
     // Neff from the raw sums, as the host path does: 1 / sum (w/ws)^2 = ws^2 / sum w^2  (PF.cpp:549-554)
-    const double neff = (ws2r > 0.0) ? (ws * ws) / ws2r : 0.0;
+    double neff = pf_neff_raw(ws, ws2r, report);
+    if (sizeof(T) == 8 && pf_sum_usable(ws) && !pf_neff_from_raw_sums(ws, ws2r))
+    {
+        // (f64 only) from the normalised weights; every thread re-reads the weights it has just written itself
+        __syncthreads();
+        pf_plan_sums<T>(w, np, s1, s2);
+        neff = (s1[0] * s1[0]) / s2[0];
+    }
     if (threadIdx.x == 0)
     {
         const int go = (neff < n_effective && resample_status) ? 1 : 0; // PF.cpp:490

@@ -481,6 +481,16 @@ class ParticleShard:
     def scale_weights(self, scale: float):
         check(self._L.cslam_pf_scale_weights(self._h, C.c_double(float(scale))))
 
+    def set_degenerate_policy(self, report: bool):
+        """What the resample calls do with a weight sum that is not a positive finite number
+        (cslam_pf_set_degenerate_policy): report=True, the rule -- no resample, Neff NaN, weights w / sum w; False (what a
+        new shard starts with), the former repair onto particle 0.  resample_particles follows `report_degenerate`."""
+        check(self._L.cslam_pf_set_degenerate_policy(self._h, C.c_int(1 if report else 0)))
+        self.report_degenerate = bool(report)
+
+    def divide_weights(self, ws: float):
+        check(self._L.cslam_pf_divide_weights(self._h, C.c_double(float(ws))))
+
     def set_uniform_weight(self, w0: float):
         check(self._L.cslam_pf_set_uniform_weight(self._h, C.c_double(float(w0))))
 
@@ -828,6 +838,26 @@ class ParticleShard:
 # ------------------------------------------------------------------------------------------------
 # PF::resampleParticles over a sharded particle set
 # ------------------------------------------------------------------------------------------------
+def _sum_usable(ws: float) -> bool:
+    return 0.0 < ws <= float(np.finfo(np.float64).max)
+
+
+def normalise_weights(shard, ws: float):
+    """w / ws on the shard by the device's rule (pf_kernels.hpp, at pf_use_scale): the scale 1/ws where it is a normal
+    number of the particle dtype, as ever; a division where it overflows (a subnormal sum) or is subnormal (a sum near
+    the top of the range), and for a sum that is not a positive finite number on a shard whose `report_degenerate` is set
+    (the IEEE quotients NaN / 0 are the answer).  Such a sum is scaled as ever otherwise."""
+    fi = np.finfo(np.dtype(shard.dtype))
+    if _sum_usable(ws):
+        if not float(fi.tiny) <= 1.0 / ws <= float(fi.max):
+            shard.divide_weights(ws)
+            return
+    elif getattr(shard, "report_degenerate", False):
+        shard.divide_weights(ws)
+        return
+    shard.scale_weights(1.0 / ws)
+
+
 def resample_particles(shard, comm, n_effective: int, resample_status: bool, select: np.ndarray | None = None,
                        uniforms: np.ndarray | None = None, step: int | None = None):
     """PF::resampleParticles(particles, numEffective, resampleStatus) -- PF.cpp:473-500 -- for the particle set
@@ -859,8 +889,14 @@ def resample_particles(shard, comm, n_effective: int, resample_status: bool, sel
         return shard.resample_sharded(comm, select, n_effective, resample_status)
     s1, s2 = shard.weight_sums()
     ws, ws2 = comm.all_reduce_sum([s1, s2])          # collective 1: two scalars
-    shard.scale_weights(1.0 / ws)                     # PF.cpp:482-487
+    normalise_weights(shard, ws)                      # PF.cpp:482-487
+    if not _sum_usable(ws) and getattr(shard, "report_degenerate", False):
+        return float("nan"), False                   # cslam.h, DEGENERATE SUMS: no Neff, no resample
     neff = (ws * ws) / ws2 if ws2 > 0 else 0.0        # 1 / sum (w/ws)^2, PF.cpp:549-554
+    fmax, fmin = float(np.finfo(np.float64).max), float(np.finfo(np.float64).tiny)
+    if np.dtype(shard.dtype).itemsize == 8 and _sum_usable(ws) and not (fmin <= ws2 <= fmax and ws * ws <= fmax):
+        s1, s2 = comm.all_reduce_sum(list(shard.weight_sums()))  # f64: the raw squares left the range of double,
+        neff = (s1 * s1) / s2                                    # those of the normalised weights have not
     if not (neff < n_effective and resample_status):  # PF.cpp:490
         return neff, False
     if comm.world == 1:

@@ -561,6 +561,22 @@ int cslam_pf_feature_update_assoc(cslam_pf_t h, const void* Z, int m, const void
 int cslam_pf_weight_sums(cslam_pf_t h, double* sums);
 /* w *= scale (the 1/ws of PF.cpp:482-487 with ws the GLOBAL sum) */
 int cslam_pf_scale_weights(cslam_pf_t h, double scale);
+/* w = w / ws, each quotient rounded once to the particle dtype.  The normalisation at the ends of the range: a driver
+ * scales by 1/ws as long as that scale, rounded to the particle dtype, is a NORMAL number (ws in (2^-128, 2^126] for
+ * f32, (2^-1024, 2^1022] for f64) and divides otherwise -- below, the scale overflows; above, it is subnormal and
+ * short of bits.  cslam_pf_resample_local and cslam_pf_resample_sharded apply this rule themselves. */
+int cslam_pf_divide_weights(cslam_pf_t h, double ws);
+/* What the resample calls of this handle do with a weight sum that is not a positive finite number (DEGENERATE SUMS at
+ * cslam_pf_resample_local).  CSLAM_PF_REPORT: the rule.  CSLAM_PF_REPAIR: what the engine did before the rule existed and
+ * a KNOWN DEFECT -- Neff comes out as 0, the call resamples, no stratum lies below a NaN running sum, so every slot becomes
+ * a copy of particle 0 and the weights are reset to 1/N: the degeneracy is erased.  REPAIR is still what a new handle
+ * starts with, because a filter that runs two observation steps in a row without anything that restores Pv between them
+ * (PF.cpp:537 zeroes it, the next predict leaves it singular) has NaN weights from its second step and runs on only
+ * through that repair; the default becomes REPORT once such drivers are gone.  Every rank of a sharded set must use the
+ * same policy. */
+#define CSLAM_PF_REPAIR 0
+#define CSLAM_PF_REPORT 1
+int cslam_pf_set_degenerate_policy(cslam_pf_t h, int policy);
 /* device pointer to the owned weights (n_particles scalars) for an all-gather */
 int cslam_pf_weights_device_ptr(cslam_pf_t h, void** dptr);
 int cslam_pf_get_weights(cslam_pf_t h, void* w_host); /* synchronises */
@@ -578,7 +594,17 @@ int cslam_pf_unpack(cslam_pf_t h, const int* dst_idx, int count, const void* d_r
  * the particle moves all run on the device; `select` are the N strata positions (PF.cpp:557, host pointer).
  * neff / resampled may be NULL (then nothing returns to the host). Same results as weight_sums + scale_weights +
  * host keep[] + gather_local.  Any particle count (the running sum is sequential, as in the reference: 8192 weights
- * are staged in LDS at a time). */
+ * are staged in LDS at a time).
+ * THE RANGE OF THE SUM: sum w is formed in double, and every positive finite sum normalises correctly, subnormal sums
+ * and sums beyond the particle dtype's largest number included (see cslam_pf_divide_weights); in f64, where the squares
+ * of the weights leave the range of double, Neff is formed from the normalised weights.  The same holds for
+ * cslam_pf_observation_step, cslam_pf_resample_sharded and the drawn forms.
+ * DEGENERATE SUMS: when sum w is NOT a positive finite number -- 0 after total underflow, a NaN or +inf weight in the
+ * set -- the rule is the reference's arithmetic (PF.cpp:482-490): the weights become the IEEE quotients w / sum w (NaN,
+ * or 0 under an infinite sum), Neff is NaN, NOTHING is resampled whatever n_effective is, *resampled = 0, and every pose,
+ * covariance and feature is left as it was.  The degeneracy is reported, not repaired: cslam_pf_resample_stats counts
+ * the call and no resample with a NaN last Neff, cslam_pf_estimate returns NaN moments afterwards and cslam_pf_score
+ * counts POSE_BAD.  A handle follows the rule after cslam_pf_set_degenerate_policy(h, CSLAM_PF_REPORT). */
 int cslam_pf_resample_local(cslam_pf_t h, const void* select, double n_effective, int resample_status, double* neff,
                             int* resampled);
 int cslam_pf_gather_local(cslam_pf_t h, const int* keep, double w_new);
@@ -604,7 +630,8 @@ int cslam_pf_resample_stats(cslam_pf_t h, double* calls, double* resamples, doub
  *        and the shared strata positions
  *     3. one grouped send/recv of the packed particle records whose source rank differs from the destination rank
  * `select`: the world * n_particles strata positions of PF.cpp:557 (host pointer), identical on every rank.
- * neff / resampled may be NULL.  The librccl of the process is bound at run time (dlopen): there is no link-time
+ * neff / resampled may be NULL.  The range of the sum and DEGENERATE SUMS: as stated at cslam_pf_resample_local (every
+ * rank sees the same sum and, under one policy, decides alike: Neff = NaN and no rank resamples under CSLAM_PF_REPORT).  The librccl of the process is bound at run time (dlopen): there is no link-time
  * dependency, and a process that never shards never loads it.
  * A communicator is made the RCCL way: rank 0 calls cslam_comm_unique_id, distributes the CSLAM_COMM_ID_BYTES bytes by
  * whatever means the application has (MPI_Bcast, a file, torch.distributed), every rank calls cslam_comm_create. */
