@@ -169,6 +169,18 @@ PF_CONTROL_SYMBOLS = ("cslam_pf_control_run", "cslam_pf_control_launches", "csla
                       "cslam_pf_assoc_cycle_drawn")
 PF_CONTROL_MAX = 16  # kPfControlMax of csrc/pf_control_kernels.hpp: control steps of one launch
 
+# The FastSLAM-1.0 step (slam.h:102): the control run with per-particle control noise (slam.h:149-159), its normals, the
+# likelihood weights with the feature update riding along (PF.cpp:343-359, 222-277) and the iteration block in one call.
+_PROTOTYPES.update({
+    "cslam_pf_control_run_sampled": [C.c_void_p] + _CONTROL_ARGS + [C.c_longlong],
+    "cslam_pf_get_control_draws": [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p],
+    "cslam_pf_likelihood_update": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int],
+    "cslam_pf_fs1_cycle_drawn": [C.c_void_p] + _CONTROL_ARGS + [C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                                C.c_int, C.c_void_p, C.c_longlong, C.c_double, C.c_int],
+})
+PF_FS1_SYMBOLS = ("cslam_pf_control_run_sampled", "cslam_pf_get_control_draws", "cslam_pf_likelihood_update",
+                  "cslam_pf_fs1_cycle_drawn")
+
 
 # The particle filter's score and trajectory log kept on the device (test/main.cpp:330, slam.h:493-511, 513-539): the
 # totals use the SCORE_* indices above; a series record is 4 floats, a track record 5 doubles.

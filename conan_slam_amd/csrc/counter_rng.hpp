@@ -10,7 +10,8 @@
 namespace cslam
 {
 
-__device__ inline unsigned long long splitmix64(unsigned long long seed, unsigned long long idx)
+// (also on the host: the seed of the particle filter's control stream, pf_control_seed, is derived there once per call)
+__host__ __device__ inline unsigned long long splitmix64(unsigned long long seed, unsigned long long idx)
 {
     unsigned long long z = seed * 0x9E3779B97F4A7C15ull + idx + 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;

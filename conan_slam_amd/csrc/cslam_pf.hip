@@ -21,6 +21,7 @@
 #include "pf_control_kernels.hpp"
 #include "pf_draw_kernels.hpp"
 #include "pf_estimate_kernels.hpp"
+#include "pf_fs1_kernels.hpp"
 #include "pf_kernels.hpp"
 #include "pf_new_feature_kernels.hpp"
 #include "pf_score_kernels.hpp"
@@ -131,6 +132,14 @@ struct PfBase
                                   const double* phi, int use, const void* Z, int m, const void* R, double gate1,
                                   double gate2, double new_fraction, double miss_likelihood, long long step, double n_eff,
                                   int status, int* q_out)                                                           = 0;
+    // the FastSLAM-1 step (pf_fs1_kernels.hpp): per-particle control noise, likelihood weights, the whole block
+    virtual int control_run_sampled(int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                                    const double* phi, int use, long long ctl_step)                                 = 0;
+    virtual int get_control_draws(long long ctl_step, int k, void* normals)                                         = 0;
+    virtual int likelihood_update(const void* Z, int m, const int* idf, const void* R, int update_features, int zero_pv) = 0;
+    virtual int fs1_cycle_drawn(int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                                const double* phi, int use, long long ctl_step, const void* ZF, int mf, const int* idf,
+                                const void* ZN, int mn, const void* R, long long step, double n_eff, int status)    = 0;
 };
 
 // Pf<T> sequences the runtime calls of every entry point; what it sequences them over lives in parts with one job each
@@ -2034,6 +2043,224 @@ struct Pf : PfBase
         CSLAM_TRY(resample_local_drawn(step, n_eff, status, nullptr, nullptr));
         return add_features_voted(Rv, q_out);
     }
+    // ------------------------------------------------------------------------------------------------
+    // The FastSLAM-1 step (pf_fs1_kernels.hpp): the control run with every particle's own noisy controls (slam.h:149-159,
+    // PF.cpp:419-471, 382-417), the likelihood weights with the feature update riding along (PF.cpp:343-359, 222-277), and
+    // the iteration block made of them (test/main.cpp:249-334 with the proposal switched off, slam.h:102).  Every refusal
+    // is decided by the plain functions of pf_host_parts.hpp before the first launch.  Slots do not move in the first two
+    // calls: the association memo and the vote are left as cslam_pf_predict and cslam_pf_feature_update leave them.
+    // ------------------------------------------------------------------------------------------------
+    int refuse_fs1(PfFs1Refusal r, const char* who, int k, long long ctl_step, const int* idf, int index, int mf,
+                   int mn)
+    {
+        switch (r)
+        {
+        case PfFs1Refusal::none:
+            return CSLAM_OK;
+        case PfFs1Refusal::bad_k:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: k=%d control steps", who, k);
+        case PfFs1Refusal::null_control:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: v, swa, Q or the output is null (k=%d)", who, k);
+        case PfFs1Refusal::null_phi:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: the heading is observed and phi is null (k=%d)", who, k);
+        case PfFs1Refusal::bad_step:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: ctl_step=%lld", who, ctl_step);
+        case PfFs1Refusal::bad_q:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: Q[0,0] and Q[1,1] must not be negative", who);
+        case PfFs1Refusal::bad_idf:
+            return fail(CSLAM_ERR_BAD_ARG, "%s: idf[%d]=%d outside 1..%d", who, index, idf[index], nf);
+        case PfFs1Refusal::capacity:
+            return fail(CSLAM_ERR_CAPACITY, "%s: %d features would exceed max_features=%d", who, nf + mn, nfcap);
+        case PfFs1Refusal::bad_scan:
+            break;
+        }
+        return fail(CSLAM_ERR_BAD_ARG, "%s: bad arguments (mf=%d, mn=%d: a negative count, or observations without Z, idf or R)", who,
+                    mf, mn);
+    }
+    int check_fs1_control(int k, const double* v, const double* swa, const void* Qv, const double* phi, int use,
+                          long long ctl_step, const char* who)
+    {
+        const T*     Q      = static_cast<const T*>(Qv);
+        const double qd[2]  = {Q ? (double)Q[0] : 0.0, Q ? (double)Q[3] : 0.0};
+        return refuse_fs1(pf_fs1_control_check(k, v != nullptr, swa != nullptr, Q ? qd : nullptr, phi != nullptr, use != 0,
+                                               ctl_step),
+                          who, k, ctl_step, nullptr, -1, 0, 0);
+    }
+    // the launches of a checked sampled run: launch_control_run's chunks, chunk c from control step ctl_step + 16 c
+    int launch_control_run_sampled(int k, const double* v, const double* swa, const void* Qv, double wb, double dt,
+                                   const double* phi, int use, long long ctl_step)
+    {
+        const T* Q     = static_cast<const T*>(Qv);
+        const T  sigma = (T)(((double)0.01f * kPi) / 180.0); // PF.cpp:391
+        int      first = 0, count = 0;
+        for (int c = 0; pf_control_chunk(k, c, &first, &count); c++)
+        {
+            PfControls<T> ctl;
+            std::memset(&ctl, 0, sizeof(ctl));
+            for (int j = 0; j < count; j++)
+            {
+                ctl.v[j]   = (T)v[first + j];
+                ctl.swa[j] = (T)swa[first + j];
+                ctl.phi[j] = use ? (T)phi[first + j] : (T)0;
+            }
+            const PfControlNoise<T> nz{pf_control_seed(draws.seed), (unsigned long long)pf_fs1_chunk_step(ctl_step, c),
+                                       (unsigned long long)draws.first, std::sqrt(Q[0]), std::sqrt(Q[3])};
+            hipLaunchKernelGGL(pf_control_run_sampled_kernel<T>, dim3((np + 63) / 64), dim3(64), 0, stream, store(), count,
+                               ctl, nz, Q[0], Q[1], Q[2], Q[3], (T)wb, (T)dt, use ? 1 : 0, sigma * sigma);
+            CSLAM_HIP_TRY(hipGetLastError());
+            control_launches++;
+        }
+        return CSLAM_OK;
+    }
+
+    int control_run_sampled(int k, const double* v, const double* swa, const void* Qv, double wb, double dt,
+                            const double* phi, int use, long long ctl_step) override
+    {
+        const char* who = "pf_control_run_sampled";
+        CSLAM_TRY(check_fs1_control(k, v, swa, Qv, phi, use, ctl_step, who));
+        CSLAM_TRY(need_draws(who));
+        if (k == 0)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_TRY(use_device());
+        return launch_control_run_sampled(k, v, swa, Qv, wb, dt, phi, use, ctl_step);
+    }
+
+    // normals [k][2][np]: one launch and one copy per control step through the buffer of cslam_pf_get_draws
+    int get_control_draws(long long ctl_step, int k, void* normals) override
+    {
+        const char* who = "pf_get_control_draws";
+        CSLAM_TRY(refuse_fs1(pf_fs1_draws_check(k, ctl_step, normals != nullptr), who, k, ctl_step, nullptr, -1, 0, 0));
+        CSLAM_TRY(need_draws(who));
+        if (k == 0)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_TRY(use_device());
+        T*           dn    = draws.out.get(); // (3 np + strata elements: room for 2 np)
+        const size_t bytes = (size_t)2 * np * sizeof(T);
+        for (int j = 0; j < k; j++)
+        {
+            hipLaunchKernelGGL(pf_control_draws_kernel<T>, dim3((np + 255) / 256), dim3(256), 0, stream,
+                               pf_control_seed(draws.seed), (unsigned long long)(ctl_step + j),
+                               (unsigned long long)draws.first, dn, np);
+            CSLAM_HIP_TRY(hipGetLastError());
+            CSLAM_HIP_TRY(hipMemcpyAsync(static_cast<char*>(normals) + (size_t)j * bytes, dn, bytes, hipMemcpyDeviceToHost,
+                                         stream));
+        }
+        CSLAM_HIP_TRY(hipStreamSynchronize(stream));
+        return CSLAM_OK;
+    }
+
+    // behind Z | idf in the staging area; the update rides unless the list names a feature twice (cycle_drawn's rule)
+    int launch_likelihood_update(int m, const int* idf, const T* R, int update_features, int zero_pv)
+    {
+        const int fu = (update_features && !pf_has_duplicate(idf, m)) ? fused_update_gain() : 0;
+        hipLaunchKernelGGL(pf_likelihood_update_kernel<T>, dim3((np + 63) / 64), dim3(64, kPfFs1Obs), 0, stream, store(),
+                           obs.z(), obs.dIdf(), m, R[0], R[1], R[2], R[3], fu, zero_pv ? 1 : 0);
+        CSLAM_HIP_TRY(hipGetLastError());
+        if (update_features && fu == 0)
+        {
+            CSLAM_TRY(launch_feature_update(m, R));
+        }
+        return CSLAM_OK;
+    }
+
+    int likelihood_update(const void* Z, int m, const int* idf, const void* Rv, int update_features, int zero_pv) override
+    {
+        const char* who   = "pf_likelihood_update";
+        int         index = -1;
+        // (pf_fs1_scan_check is the whole rule: counts, NULLs -- R only where it is read -- and idf within 1..nf)
+        CSLAM_TRY(refuse_fs1(pf_fs1_scan_check(m, Z != nullptr, idf, 0, false, Rv != nullptr, nf, nfcap, &index), who, 0, 0, idf,
+                             index, m, 0));
+        if (m == 0)
+        {
+            return CSLAM_OK;
+        }
+        CSLAM_TRY(use_device());
+        CSLAM_TRY(stage(Z, m, idf));
+        return launch_likelihood_update(m, idf, static_cast<const T*>(Rv), update_features, zero_pv);
+    }
+
+    // One iteration block of the FastSLAM-1 loop for a handle that holds the whole seeded set: the sampled run, then --
+    // known features seen -- the likelihood weights with the feature update and Pv = 0, the resample on the strata of
+    // `step`, and the new features at every particle's own pose (the particle IS the sample: no pose is drawn).  Z of
+    // the known and of the new features travel as cycle_drawn sends them.
+    int fs1_cycle_drawn(int k, const double* v, const double* swa, const void* Qv, double wb, double dt, const double* phi,
+                        int use, long long ctl_step, const void* ZF, int mf, const int* idf, const void* ZN, int mn,
+                        const void* Rv, long long step, double n_eff, int status) override
+    {
+        const char* who   = "pf_fs1_cycle_drawn";
+        int         index = -1;
+        CSLAM_TRY(check_fs1_control(k, v, swa, Qv, phi, use, ctl_step, who));
+        CSLAM_TRY(need_whole_set(who));
+        CSLAM_TRY(refuse_fs1(pf_fs1_scan_check(mf, ZF != nullptr, idf, mn, ZN != nullptr, Rv != nullptr, nf, nfcap, &index), who,
+                             k, ctl_step, idf, index, mf, mn));
+        CSLAM_TRY(use_device());
+        const bool together = mf > 0 && mn > 0 && mf + mn <= kPfDrawObsMax;
+        if (mf > 0 || mn > 0)
+        {
+            CSLAM_TRY(ensure_m(together ? mf + mn : std::max(mf, mn)));
+        }
+        if (mf > 0)
+        {
+            CSLAM_TRY(rs.ensure(np, stream));
+        }
+        CSLAM_TRY(launch_control_run_sampled(k, v, swa, Qv, wb, dt, phi, use, ctl_step));
+        if (mf == 0 && mn == 0)
+        {
+            return CSLAM_OK;
+        }
+        const T* R = static_cast<const T*>(Rv);
+        obs.forget();
+        const T* zn = obs.z();
+        if (mf > 0)
+        {
+            if (together)
+            {
+                T   zz[2 * kPfDrawObsMax];
+                int ii[kPfDrawObsMax];
+                std::memset(ii, 0, sizeof(ii));
+                std::memcpy(zz, ZF, (size_t)2 * mf * sizeof(T));
+                std::memcpy(zz + 2 * mf, ZN, (size_t)2 * mn * sizeof(T));
+                std::memcpy(ii, idf, (size_t)mf * sizeof(int));
+                CSLAM_TRY(launch_draw(step, nullptr, obs.dSelect(), np, mf + mn, zz, ii));
+                zn = obs.z() + 2 * mf;
+            }
+            else
+            {
+                const bool by_copy = mf > kPfDrawObsMax;
+                if (by_copy)
+                {
+                    CSLAM_TRY(stage(ZF, mf, idf));
+                }
+                CSLAM_TRY(launch_draw(step, nullptr, obs.dSelect(), np, by_copy ? 0 : mf, ZF, idf));
+            }
+            CSLAM_TRY(launch_likelihood_update(mf, idf, R, 1, 1));
+            CSLAM_TRY(launch_resample(obs.dSelect(), n_eff, status));
+        }
+        if (mn > 0)
+        {
+            if (!together)
+            {
+                if (mn > kPfDrawObsMax)
+                {
+                    CSLAM_TRY(stage(ZN, mn, nullptr));
+                }
+                else // (a producer launch that only carries Z: no draw is taken)
+                {
+                    CSLAM_TRY(launch_draw(step, nullptr, nullptr, 0, mn, ZN, nullptr));
+                }
+            }
+            hipLaunchKernelGGL(pf_add_features_kernel<T>, dim3((np + 63) / 64, mn), dim3(64), 0, stream, store(), zn, mn,
+                               R[0], R[1], R[2], R[3]);
+            CSLAM_HIP_TRY(hipGetLastError());
+            nf += mn;
+        }
+        obs.forget(); // (the area holds this cycle's mix, not the Z || idf of one call)
+        return CSLAM_OK;
+    }
 };
 
 inline PfBase* B(cslam_pf_t h)
@@ -2739,6 +2966,41 @@ int cslam_pf_assoc_cycle_drawn(cslam_pf_t h, int k, const double* v, const doubl
     CSLAM_NEED(h);
     return B(h)->assoc_cycle_drawn(k, v, swa, Q, wb, dt, phi, use_heading, Z, m, R, gate1, gate2, new_fraction,
                                    miss_likelihood, step, n_effective, resample_status, q);
+}
+
+/* slam.h:102, the FastSLAM-1.0 sibling of test/main.cpp:277-286: k iterations with every particle's own noisy controls
+   (slam.h:149-159, then PF.cpp:419-471 and PF.cpp:382-417) in one launch per 16 steps */
+int cslam_pf_control_run_sampled(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb,
+                                 double dt, const double* phi, int use_heading, long long ctl_step)
+{
+    CSLAM_NEED(h);
+    return B(h)->control_run_sampled(k, v, swa, Q, wb, dt, phi, use_heading, ctl_step);
+}
+
+/* the normals slam.h:149-159 consumes in cslam_pf_control_run_sampled */
+int cslam_pf_get_control_draws(cslam_pf_t h, long long ctl_step, int k, void* normals)
+{
+    CSLAM_NEED(h);
+    return B(h)->get_control_draws(ctl_step, k, normals);
+}
+
+/* PF.cpp:343-359 (PF.cpp:279-317 per observation) at every particle's pose, with PF.cpp:222-277 riding along */
+int cslam_pf_likelihood_update(cslam_pf_t h, const void* Z, int m, const int* idf, const void* R, int update_features,
+                               int zero_pv)
+{
+    CSLAM_NEED(h);
+    return B(h)->likelihood_update(Z, m, idf, R, update_features, zero_pv);
+}
+
+/* test/main.cpp:249-334 with the proposal switched off (slam.h:102): the sampled run, PF.cpp:343-359 + 222-277,
+   PF.cpp:473-500, PF.cpp:9-60, in one call */
+int cslam_pf_fs1_cycle_drawn(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                             const double* phi, int use_heading, long long ctl_step, const void* ZF, int mf, const int* idf,
+                             const void* ZN, int mn, const void* R, long long step, double n_effective, int resample_status)
+{
+    CSLAM_NEED(h);
+    return B(h)->fs1_cycle_drawn(k, v, swa, Q, wb, dt, phi, use_heading, ctl_step, ZF, mf, idf, ZN, mn, R, step,
+                                 n_effective, resample_status);
 }
 
 } // extern "C"

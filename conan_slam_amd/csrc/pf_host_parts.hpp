@@ -1,9 +1,9 @@
 // pf_host_parts.hpp -- the arithmetic and bookkeeping of the particle handle that needs no GPU: the layout of the device
 // staging area, the memo of what it holds, the validity of the association tables and of the vote on new features, and
 // the small host loops of the fused step, the sharded exchange and the strata table, the chunk split and the refusal
-// rule of the control run, and the book of the device-side score.  No HIP include:
-// tests/host/pf_host_parts_check.cpp, pf_control_check.cpp and pf_score_book_check.cpp build it with plain g++ (and under
-// the address and undefined-behaviour sanitizers).
+// rule of the control run, the refusal rules of the FastSLAM-1 step, and the book of the device-side score.  No HIP include:
+// tests/host/pf_host_parts_check.cpp, pf_control_check.cpp, pf_fs1_check.cpp and pf_score_book_check.cpp build it with
+// plain g++ (and under the address and undefined-behaviour sanitizers).
 #pragma once
 
 #include <algorithm>
@@ -286,6 +286,90 @@ inline PfControlRefusal pf_control_check(int k, bool has_v, bool has_swa, bool h
     }
     return PfControlRefusal::none;
 }
+
+// why a call of the FastSLAM-1 step (cslam_pf_control_run_sampled, cslam_pf_get_control_draws, cslam_pf_likelihood_update,
+// cslam_pf_fs1_cycle_drawn) is refused; every refusal comes before the first launch and changes nothing
+enum class PfFs1Refusal
+{
+    none,
+    bad_k,        // k < 0
+    null_control, // k > 0 without v, swa or Q
+    null_phi,     // k > 0 and the heading observed, without phi
+    bad_step,     // ctl_step < 0
+    bad_q,        // Q[0,0] or Q[1,1] negative (or NaN): the control noise has no standard deviation
+    bad_scan,     // a negative count, or observations without Z, idf or R
+    bad_idf,      // idf[*index] outside 1..nf
+    capacity      // nf + mn > max_features
+};
+
+// The arguments of a sampled control run of k steps from control step ctl_step.  q_diag: {Q[0,0], Q[1,1]} as doubles, or
+// nullptr where Q is absent; with k = 0 nothing is read and only k and ctl_step are looked at.
+inline PfFs1Refusal pf_fs1_control_check(int k, bool has_v, bool has_swa, const double* q_diag, bool has_phi, bool use_heading,
+                                         long long ctl_step)
+{
+    switch (pf_control_check(k, has_v, has_swa, q_diag != nullptr, has_phi, use_heading))
+    {
+    case PfControlRefusal::none:
+        break;
+    case PfControlRefusal::bad_k:
+        return PfFs1Refusal::bad_k;
+    case PfControlRefusal::null_control:
+        return PfFs1Refusal::null_control;
+    case PfControlRefusal::null_phi:
+        return PfFs1Refusal::null_phi;
+    }
+    if (ctl_step < 0)
+    {
+        return PfFs1Refusal::bad_step;
+    }
+    if (k > 0 && (!(q_diag[0] >= 0.0) || !(q_diag[1] >= 0.0)))
+    {
+        return PfFs1Refusal::bad_q;
+    }
+    return PfFs1Refusal::none;
+}
+
+// cslam_pf_get_control_draws: k steps from ctl_step into `normals`
+inline PfFs1Refusal pf_fs1_draws_check(int k, long long ctl_step, bool has_out)
+{
+    if (k < 0)
+    {
+        return PfFs1Refusal::bad_k;
+    }
+    if (ctl_step < 0)
+    {
+        return PfFs1Refusal::bad_step;
+    }
+    return (k > 0 && !has_out) ? PfFs1Refusal::null_control : PfFs1Refusal::none;
+}
+
+// The scan of the FastSLAM-1 step: mf observations of known features (Z, idf, 1-based, on a store of nf features) and mn
+// of new ones (room for nfcap features), R for either.  cslam_pf_likelihood_update is the case mn = 0.
+inline PfFs1Refusal pf_fs1_scan_check(int mf, bool has_ZF, const int* idf, int mn, bool has_ZN, bool has_R, int nf, int nfcap,
+                                      int* index)
+{
+    *index = -1;
+    if (mf < 0 || mn < 0 || (mf > 0 && (!has_ZF || idf == nullptr)) || (mn > 0 && !has_ZN) || ((mf > 0 || mn > 0) && !has_R))
+    {
+        return PfFs1Refusal::bad_scan;
+    }
+    for (int i = 0; i < mf; i++)
+    {
+        if (idf[i] < 1 || idf[i] > nf)
+        {
+            *index = i;
+            return PfFs1Refusal::bad_idf;
+        }
+    }
+    if (mn > nfcap - nf)
+    {
+        return PfFs1Refusal::capacity;
+    }
+    return PfFs1Refusal::none;
+}
+
+// the control step chunk c of a sampled run starts at: the chunks are those of pf_control_chunk
+inline long long pf_fs1_chunk_step(long long ctl_step, int c) { return ctl_step + (long long)kPfControlChunk * c; }
 
 // The record counts of a sharded exchange: hc[r] records go to rank r, hc[world + r] come from it; both buffers hold
 // them grouped by rank.  Where the records for / from `rank` start:

@@ -472,6 +472,45 @@ class ParticleShard:
         check(rc)
         return q.value
 
+    # ---- the FastSLAM-1.0 step (slam.h:102): per-particle control noise, likelihood weights, the block in one call
+    def control_run_sampled(self, v, swa, Q, wb, dt, ctl_step: int, phi=None, use_heading=False):
+        """control_run with every particle's own noisy controls (slam.h:149-159 per particle, Q taken as diagonal): step j
+        uses the normals of control step ctl_step + j (synth.pf_control_normals / pf_control_noise restate them).  Any
+        shard of a seeded set (cslam_pf_control_run_sampled)."""
+        keep, args = self._controls(v, swa, Q, wb, dt, phi, use_heading)
+        check(self._L.cslam_pf_control_run_sampled(self._h, *args, C.c_longlong(int(ctl_step))))
+
+    def control_draws(self, ctl_step: int, k: int) -> np.ndarray:
+        """-> normals [k, 2, n_local] that control_run_sampled consumes for control steps ctl_step .. ctl_step + k - 1."""
+        out = np.zeros((max(int(k), 0), 2, self.n_local), self.dtype)
+        check(self._L.cslam_pf_get_control_draws(self._h, C.c_longlong(int(ctl_step)), C.c_int(int(k)), _vp(out)))
+        return out
+
+    def likelihood_update(self, Z, idf, R, update_features: bool = True, zero_pv: bool = True):
+        """PF::likelihood at every particle's own pose, w <- w * like (PF.cpp:343-359), in one launch; update_features:
+        PF::featureUpdate rides along (PF.cpp:222-277); zero_pv: Pv = 0 afterwards (cslam_pf_likelihood_update)."""
+        Zc, m = self._z(Z)
+        idf = np.ascontiguousarray(idf, dtype=np.int32)
+        check(self._L.cslam_pf_likelihood_update(self._h, _vp(Zc), C.c_int(m), _vp(idf) if m else None,
+                                                 _vp(self._m22(R)), C.c_int(1 if update_features else 0),
+                                                 C.c_int(1 if zero_pv else 0)))
+
+    def fs1_cycle_drawn(self, v, swa, Q, wb, dt, ctl_step: int, ZF, idf, ZN, R, step: int, n_effective: float,
+                        resample_status: bool, phi=None, use_heading=False):
+        """One iteration block of the FastSLAM-1 loop on a shard that holds the whole seeded set, in one C call
+        (cslam_pf_fs1_cycle_drawn): control_run_sampled from ctl_step, then -- known features seen (ZF, idf) --
+        likelihood_update(update_features, zero_pv) and resample_local_drawn(step) with nothing returned, then
+        add_features(ZN) at every particle's own pose."""
+        keep, args = self._controls(v, swa, Q, wb, dt, phi, use_heading)
+        ZFc, mf = self._z(ZF if ZF is not None else [])
+        ZNc, mn = self._z(ZN if ZN is not None else [])
+        idf = np.ascontiguousarray(idf if mf else [], dtype=np.int32)
+        Rc = None if R is None else self._m22(R)
+        check(self._L.cslam_pf_fs1_cycle_drawn(self._h, *args, C.c_longlong(int(ctl_step)), _vp(ZFc), C.c_int(mf),
+                                               _vp(idf) if mf else None, _vp(ZNc), C.c_int(mn),
+                                               _vp(Rc) if Rc is not None else None, C.c_longlong(int(step)),
+                                               C.c_double(float(n_effective)), C.c_int(1 if resample_status else 0)))
+
     # ---- pieces of the resample step
     def weight_sums(self) -> Tuple[float, float]:
         s = (C.c_double * 2)()

@@ -71,6 +71,44 @@ def pf_draw_select(seed: int, step: int, n: int, dtype=np.float32) -> np.ndarray
     return stratified_random(n, pf_draw_uniforms(seed, step, n), dtype)
 
 
+PF_CONTROL_STREAM = 0x4354524C  # "CTRL"
+
+
+def pf_control_seed(seed: int) -> int:
+    """Seed of the particle filter's control-noise stream: splitmix64(seed, 0x4354524C).  Independent of the proposal /
+    strata stream of the same `seed`, which uses `seed` itself."""
+    return int(splitmix64(int(seed) & 0xFFFFFFFFFFFFFFFF, PF_CONTROL_STREAM))
+
+
+def pf_control_normals(seed: int, ctl_step: int, k: int, first: int, count: int, dtype=np.float32) -> np.ndarray:
+    """The [k, 2, count] control normals of the global particle slots first .. first + count - 1 for control steps
+    ctl_step .. ctl_step + k - 1 (what cslam_pf_control_run_sampled consumes): component 0 perturbs the velocity, 1 the
+    steering.  normal(pf_control_seed(seed), pf_draw_key(t, c, g)) in f64, then one rounding to the particle dtype."""
+    cs = pf_control_seed(seed)
+    g = np.uint64(first) + np.arange(count, dtype=np.uint64)
+    out = np.zeros((max(int(k), 0), 2, count), np.float64)
+    for j in range(int(k)):
+        for c in range(2):
+            out[j, c] = normal(cs, pf_draw_key(int(ctl_step) + j, c, g))
+    return out.astype(dtype)
+
+
+def pf_control_noise(normals, v, swa, Q, dtype=np.float32):
+    """The noisy controls of every particle (slam.h:149-159 per particle, Q taken as diagonal) from normals [k, 2, count]:
+    vn = T(v) + n0 * sqrt(T(Q[0,0])), swan = T(swa) + n1 * sqrt(T(Q[1,1])), every operation rounded in T, the product
+    first -- control_noise's arithmetic.  v, swa: scalars or k values.  -> (vn[k, count], swan[k, count])."""
+    T = np.dtype(dtype).type
+    n = np.asarray(normals, dtype=dtype)
+    k = n.shape[0]
+    vv = np.broadcast_to(np.asarray(v, np.float64).astype(dtype), (k,))[:, None]
+    ss = np.broadcast_to(np.asarray(swa, np.float64).astype(dtype), (k,))[:, None]
+    Q = np.asarray(Q, dtype=dtype).reshape(2, 2)
+    s0, s1 = np.sqrt(T(Q[0, 0])), np.sqrt(T(Q[1, 1]))
+    vn = (vv + (n[:, 0, :] * s0).astype(dtype)).astype(dtype)
+    swan = (ss + (n[:, 1, :] * s1).astype(dtype)).astype(dtype)
+    return vn, swan
+
+
 def noise_matrices(dtype=np.float32):
     """Q, R (slam.h:72-81, test/main.cpp:93-103) and the inflated QE = 2Q, RE = 8R (main.cpp:125-129)."""
     f = np.float32

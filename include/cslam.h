@@ -848,6 +848,56 @@ int cslam_pf_assoc_cycle_drawn(cslam_pf_t h, int k, const double* v, const doubl
                                const double* phi, int use_heading, const void* Z, int m, const void* R, double gate1,
                                double gate2, double new_fraction, double miss_likelihood, long long step,
                                double n_effective, int resample_status, int* q);
+
+/* ---- the FastSLAM-1.0 step ----
+ * The reference declares the switch between its two particle loops, mSwitchSampleProposal (slam.h:102), and runs only
+ * the FastSLAM-2 one (test/main.cpp:249-334).  The pieces of the other lie next to it: addControlNoise (slam.h:149-159),
+ * PF::likelihood (PF.cpp:343-359 over PF.cpp:279-317), PF::featureUpdate (PF.cpp:222-277), PF::resampleParticles
+ * (PF.cpp:473-500) and PF::addOneNewFeature (PF.cpp:9-60).  The calls below make that loop: sample the motion per
+ * particle, weight by the observation likelihood at the particle's own pose, update the features, resample.  Nothing in
+ * them inverts Pv, so two scans may follow each other with Pv = 0 in between.
+ *
+ * The control draws are a stream of their own, a pure function of (seed of cslam_pf_seed_draws, control step, component,
+ * GLOBAL particle slot): normal = T(counter_normal(splitmix64(seed, 0x4354524C), key(ctl_step, c, g))) with the key of
+ * the proposal draws, c = 0 for the velocity and c = 1 for the steering.  A shard sees the noise of the unsharded set.
+ *
+ * cslam_pf_control_run_sampled  cslam_pf_control_run (test/main.cpp:277-286) with every particle's own noisy controls
+ *                               (slam.h:149-159, Q taken as diagonal): step j of the run uses
+ *                               vn = T(v[j]) + n0 * sqrt(T(Q[0,0])), swan = T(swa[j]) + n1 * sqrt(T(Q[1,1])), every
+ *                               operation rounded in T, with the normals of control step ctl_step + j; then PF.cpp:419-471
+ *                               with (vn, swan) and PF.cpp:382-417.  One launch per 16 steps, counted by
+ *                               cslam_pf_control_launches.  Bit for bit cslam_pf_control_run of one particle with its
+ *                               (vn, swan); Q = 0 is cslam_pf_control_run.  Any shard of a seeded set.  k = 0 returns
+ *                               CSLAM_OK and launches nothing.  What cslam_pf_control_run refuses, ctl_step < 0, a negative
+ *                               Q[0,0] or Q[1,1], an unseeded handle: CSLAM_ERR_BAD_ARG, nothing changes.
+ * cslam_pf_get_control_draws    the normals of control steps ctl_step .. ctl_step + k - 1 for the owned particles,
+ *                               [k][2][np] in the handle's dtype (for tests and for host restatements).  Synchronises.
+ * cslam_pf_likelihood_update    PF.cpp:343-359 in one launch: for every owned particle and every observation i the
+ *                               Jacobians at the particle's pose (PF.cpp:70-135), V = Z - ZP with the bearing wrapped, the
+ *                               factor of PF.cpp:279-317, like = ((1 l_0) l_1) ... l_{m-1}, w <- w like.  update_features:
+ *                               PF.cpp:222-277 rides along, bit for bit cslam_pf_feature_update(Z, m, idf, R) with the
+ *                               handle's gain quirk (a list that names a feature twice gets that call behind the weights
+ *                               instead).  zero_pv: Pv = 0 afterwards, the state PF.cpp:537 leaves, so FastSLAM-2 calls may
+ *                               follow.  xv is never written.  m = 0 returns CSLAM_OK and touches nothing (nothing is read:
+ *                               R may be NULL then).  Any shard; needs no draws.  NULL arrays with m > 0, m < 0, idf outside
+ *                               1..nf: CSLAM_ERR_BAD_ARG before any launch.
+ * cslam_pf_fs1_cycle_drawn      one iteration block for a handle that holds the whole seeded set: bit for bit
+ *                               cslam_pf_control_run_sampled(.., ctl_step); mf > 0: cslam_pf_likelihood_update(ZF, mf, idf,
+ *                               R, 1, 1) and cslam_pf_resample_local_drawn(step) with nothing returned (PF.cpp:473-500);
+ *                               then cslam_pf_add_features(ZN, mn, R) at every particle's own pose (PF.cpp:9-60) -- no pose
+ *                               is sampled: the particle is the sample.  With mf <= 32 and mn <= 32 no copy command is
+ *                               enqueued.  Everything that can refuse does so before the first launch -- the refusals of
+ *                               cslam_pf_control_run_sampled, a shard of a larger set, NULL arrays, idf outside 1..nf:
+ *                               CSLAM_ERR_BAD_ARG; nf + mn > max_features: CSLAM_ERR_CAPACITY -- and a refused cycle
+ *                               changes nothing. */
+int cslam_pf_control_run_sampled(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb,
+                                 double dt, const double* phi /* k or NULL */, int use_heading, long long ctl_step);
+int cslam_pf_get_control_draws(cslam_pf_t h, long long ctl_step, int k, void* normals /* [k][2][np], T */);
+int cslam_pf_likelihood_update(cslam_pf_t h, const void* Z, int m, const int* idf, const void* R, int update_features,
+                               int zero_pv);
+int cslam_pf_fs1_cycle_drawn(cslam_pf_t h, int k, const double* v, const double* swa, const void* Q, double wb, double dt,
+                             const double* phi, int use_heading, long long ctl_step, const void* ZF, int mf, const int* idf,
+                             const void* ZN, int mn, const void* R, long long step, double n_effective, int resample_status);
 /* download one particle (host buffers; any may be NULL): w (1), Xv (3), Pv (9), XF (2*nf), PF (4*nf) */
 int cslam_pf_get_particle(cslam_pf_t h, int index, void* w, void* Xv, void* Pv, void* XF, void* PF);
 /* upload one particle with nf features (nf must equal the current feature count, or set it when the

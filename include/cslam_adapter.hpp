@@ -35,6 +35,9 @@
 //   HipPF::controlRunAll / cycleAll / cycleUnknownAll   (the control steps between two scans, test/main.cpp:279-286, in one
 //                            launch per 16, and the whole iteration block of test/main.cpp:249-334 in one call)
 //                                                                    -> cslam_pf_control_run / _cycle_drawn / _assoc_cycle_drawn
+//   HipPF::controlRunSampledAll / likelihoodUpdateAll / cycleFastSlam1All   (the FastSLAM-1.0 loop behind slam.h:102:
+//                            slam.h:149-159 per particle, PF.cpp:343-359, 222-277, 473-500, 9-60)
+//                                                                    -> cslam_pf_control_run_sampled / _likelihood_update / _fs1_cycle_drawn
 //
 // Ownership: the reference passes X and P by reference into every call; here the handle owns them in HBM.  X is
 // refreshed after every call (the driver reads it every iteration, test/main.cpp:136); P is refreshed on demand
@@ -621,6 +624,71 @@ class HipPF : public PF
                    "HipPF::cycleUnknown");
         }
         return q;
+    }
+
+    // ---- the FastSLAM-1.0 step: the loop the reference's mSwitchSampleProposal (slam.h:102) would select when false
+    /// controlRunAll with every particle's own noisy controls (addControlNoise, slam.h:149-159, per particle; Q taken as
+    /// diagonal), the normals of control steps ctlStep .. ctlStep + k - 1 drawn on the device: needs seedDraws().
+    void controlRunSampledAll(const Eigen::VectorXf& v, const Eigen::VectorXf& swa, const Eigen::MatrixXf& Q, const float& wb,
+                              const float& dt, const Eigen::VectorXf& phi, bool useHeading, long long ctlStep)
+    {
+        std::vector<double> c;
+        if (controls(v, swa, phi, useHeading, c, "controlRunSampled"))
+        {
+            const int k = static_cast<int>(v.rows());
+            report(cslam_pf_control_run_sampled(h_, k, c.data(), c.data() + k, Q.data(), wb, dt,
+                                                useHeading ? c.data() + 2 * k : nullptr, useHeading ? 1 : 0, ctlStep),
+                   "HipPF::controlRunSampled");
+        }
+    }
+    /// PF::likelihood at every particle's own pose, w <- w * like (PF.cpp:343-359), with featureUpdate (PF.cpp:222-277)
+    /// riding along and P <- 0 afterwards, in one launch
+    void likelihoodUpdateAll(const Eigen::MatrixXf& Z, const Eigen::VectorXi& idf, const Eigen::MatrixXf& R,
+                             bool updateFeatures = true, bool zeroP = true)
+    {
+        report(cslam_pf_likelihood_update(h_, Z.data(), static_cast<int>(Z.cols()), idf.data(), R.data(),
+                                          updateFeatures ? 1 : 0, zeroP ? 1 : 0),
+               "HipPF::likelihoodUpdate");
+    }
+    /// One iteration block of the FastSLAM-1 loop: the sampled control run from ctlStep, then -- known features seen --
+    /// likelihoodUpdateAll, resampleParticles with the strata of the step set with setStep() (PF.cpp:473-500), then
+    /// addOneNewFeature (PF.cpp:9-60) of ZN at every particle's own pose.  No pose is sampled.  Needs seedDraws().
+    void cycleFastSlam1All(const Eigen::VectorXf& v, const Eigen::VectorXf& swa, const Eigen::MatrixXf& Q, const float& wb,
+                           const float& dt, const Eigen::VectorXf& phi, bool useHeading, long long ctlStep,
+                           const Eigen::MatrixXf& ZF, const Eigen::VectorXi& idf, const Eigen::MatrixXf& ZN,
+                           const Eigen::MatrixXf& R, int numEffective, bool resampleStatus = false)
+    {
+        const int mf = static_cast<int>(ZF.cols()), mn = static_cast<int>(ZN.cols());
+        if (comm_ == nullptr)
+        {
+            std::vector<double> c;
+            if (controls(v, swa, phi, useHeading, c, "cycleFastSlam1"))
+            {
+                const int k = static_cast<int>(v.rows());
+                report(cslam_pf_fs1_cycle_drawn(h_, k, c.data(), c.data() + k, Q.data(), wb, dt,
+                                                useHeading ? c.data() + 2 * k : nullptr, useHeading ? 1 : 0, ctlStep, ZF.data(),
+                                                mf, idf.data(), ZN.data(), mn, R.data(), step_, numEffective,
+                                                resampleStatus ? 1 : 0),
+                       "HipPF::cycleFastSlam1");
+            }
+            return;
+        }
+        // a sharded set: the same calls one by one, the resample over the communicator (as cycleAll)
+        controlRunSampledAll(v, swa, Q, wb, dt, phi, useHeading, ctlStep);
+        if (mf > 0)
+        {
+            double neff      = 0.0;
+            int    resampled = 0;
+            likelihoodUpdateAll(ZF, idf, R, true, true);
+            report(cslam_pf_resample_sharded_drawn(h_, comm_, step_, numEffective, resampleStatus ? 1 : 0, &neff, &resampled),
+                   "HipPF::cycleFastSlam1");
+            lastNeff_      = static_cast<float>(neff);
+            lastResampled_ = resampled != 0;
+        }
+        if (mn > 0)
+        {
+            addNewFeaturesAll(ZN, R);
+        }
     }
 
     /// the strata positions of PF.cpp:557 (stratifiedRandom): supplied by the caller so that runs are reproducible
